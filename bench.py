@@ -5,14 +5,18 @@ Workload at every N: BASELINE.json configs[1] per GPU -- batch=32 512x512x3 fp32
 postprocess (threshold -> external components -> quads).  A "step" = one pass of that path over one
 synthetic batch already resident in HBM.  Multi-GPU: images shard by rank with no data-path
 collective (replicas), weak scaling (32 images per GPU), value = all ranks' images / max-over-ranks
-time.
+time.  A plain run sets up, settles the clocks, runs W warm-up steps, times exactly K steps (ms_per_step = their time / K)
+and prints the headline line; --dump-outputs DIR then also writes the last timed step's results as DIR/<name>.npy.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line, with --full only (none of them changes the headline):
+  ms_per_step_spread -- five more blocks of K steps, and the median of all six
   roofline     -- the dominant kernel (dense dilated 3x3 conv; Winograd with bf16 split products since round 6), timed live with HIP events
   cpu_baseline -- the torch-CPU restatement (oracle/, kind "port") on a bounded sample, rank 0, N=1
   parts        -- net-only / postprocess-only timings of the same step
   latency_batch1 -- the reference's own metric (predict.py:73-78): one timed predict of zeros (1,S,S,1) after one warm-up
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N>1 either the driver starts the ranks
+  train_step*, forward_fp16_cfg5, pcie_inclusive_host_numpy -- the other configs, precisions and the host path; for N>1 the
+                  data-parallel train leg
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  For N>1 either the driver starts the ranks
 (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...) or, when no WORLD_SIZE is set, this script
 starts them itself as child processes BEFORE anything touches the GPU and relays rank 0's JSON line.  Every rank
 counts the ranks RCCL really connected (all-reduce of ones -> "n_ranks_rccl") and exits non-zero if that is not N.
@@ -125,7 +129,32 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-train", action="store_true", help="skip the extra train-step measurement")
     ap.add_argument("--train-batch", type=int, default=64)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: spread over more blocks, other paths / sizes / precisions, train legs, batch-1 latency, "
+                         "PCIe-inclusive host path, parts, roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0), e.g. bench_outputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(path, out):
+    """The arrays a caller of the timed path receives from its last step (ModelRunner.predict_on_device, complete after the flush):
+    logits, binary map, object counts, and the quads of every image's list up to its count (entries behind a list's end are
+    unspecified, so they are not written).  float32 / float64, about 4 MB."""
+    logits, bmap, quads, classes, counts = out
+    os.makedirs(path, exist_ok=True)
+    counts_h = counts.cpu().numpy()
+    n_kept = np.minimum(counts_h, quads.shape[1])
+    arrays = {"logits": logits.cpu().numpy().astype(np.float32), "binary_map": bmap.cpu().numpy().astype(np.float32),
+              "counts": counts_h.astype(np.float64),
+              "quads": np.concatenate([q[:k] for q, k in zip(quads.cpu().numpy(), n_kept)]).astype(np.float64).reshape(-1, 8)}
+    if classes is not None:
+        arrays["classes"] = np.concatenate([c[:k] for c, k in zip(classes.cpu().numpy(), n_kept)]).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -388,7 +417,7 @@ def dry_run(args, world, rank):
                 "ms_per_step": round(float(t) / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": "f32", "data": "synthetic", "dry_run": True,
                 "config": {"workload": "DRY RUN on CPU/gloo: launch + collective plumbing only, no GPU work"}}
-    if world > 1:
+    if world > 1 and args.full:
         # the N > 1 train leg's control flow with a stubbed trainer (UBD_BENCH_DRY_FAULT injects the failures it must survive):
         #   attach_fail -- the last rank cannot create its native communicator: ALL ranks must drop theirs and fall back together
         #   stall       -- the last rank never arrives: the watchdog prints the line with the reason and the run exits non-zero
@@ -481,7 +510,6 @@ def main():
           for k in range(RING)]
     labels, x = ring_labels[0], xs[0]
     input_ring_mb = round(sum(t.numel() * t.element_size() for t in xs) / 1e6, 1)
-    rect_logits = [torch.from_numpy(synthetic.logits_from_maps(ring_labels[k], 0, seed=5 + k)).to(dev) for k in range(2)]
     step_no = [0]
 
     def step():
@@ -526,15 +554,36 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    first_block_ms = elapsed / args.steps * 1e3
-    # The timed region of K steps is short (20 steps = 7 ms in the driver's run): five more blocks of K steps follow, each with the same
-    # brackets (barrier + synchronize on both sides, MAX over ranks), and `ms_per_step` / `value` are the MEDIAN of the six blocks
-    # (VERDICT r5 item 9); the first block's own figure stays on the line as `ms_per_step_first_block`.
-    block_ms = [timed_wall(step, args.steps) / args.steps * 1e3 for _ in range(5)]
-    ms_per_step = float(np.median([first_block_ms] + block_ms))
+    # `ms_per_step` / `value` come from exactly the K timed steps above
+    ms_per_step = elapsed / args.steps * 1e3
     value = world * BATCH / (ms_per_step * 1e-3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)                      # before anything else reuses the runner's result slots
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "images/sec (512x512) fwd+CCL", "value": round(value, 1), "unit": "images/s",
+            "n_gpus": world, "n_ranks_rccl": n_ranks_rccl, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "clock_settle_steps": settle, "input_ring_MB": input_ring_mb,
+            "config": {"workload": "configs[1]: batch=32 512x512x3 fp32 forward + CCL postprocess per GPU "
+                                   "(stripe-textured rectangle images, random-init weights)",
+                       "batch_per_gpu": BATCH, "image": [SIDE, SIDE, C_IN], "parallelism": f"replicas x{world}, no collective"}}
+    if not args.full:
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if line is not None:
+            print(json.dumps(line), flush=True)
+        return 0
+
+    # ---- --full only: everything below is reported beside the headline and never changes it
+    # The timed region of K steps can be short (20 steps = 7 ms): five more blocks of K steps follow, each with the same brackets
+    # (barrier + synchronize on both sides, MAX over ranks); their spread and the median of all six blocks are reported.
+    block_ms = [timed_wall(step, args.steps) / args.steps * 1e3 for _ in range(5)]
     # the same step re-fed ONE tensor (rounds 1-3 measured this): x + activations fit the Infinity Cache, the images come from MALL
     single_ms = timed_wall(lambda: runner.predict_on_device(model, x), args.steps) / args.steps * 1e3
+    rect_logits = [torch.from_numpy(synthetic.logits_from_maps(ring_labels[k], 0, seed=5 + k)).to(dev) for k in range(2)]
     # the same pipelined step with the in-stem postprocess job fed RECTANGLE maps (1-8 objects per map) instead of
     # the previous batch's logits (random-init weights: one blob per image): forward(batch k) + postprocess(rectangle maps) enqueued
     # together through ubd_forward_postprocess, exactly as the runner does
@@ -759,7 +808,6 @@ def main():
 
     host_path = time_host_path() if (world == 1 and rank == 0) else None
 
-    line = None
     if rank == 0:
         # ---- parts: net only / postprocess only (rectangle maps) -- HIP events on the launch stream
         timed = timed_events                                  # SETTLE_STEPS untimed calls in front of every timed region
@@ -830,19 +878,12 @@ def main():
             if latency is not None:
                 latency["cpu_baseline_4_threads"] = run_cpu_child("latency", 0, 4)
 
-        line = {
-            "metric": "images/sec (512x512) fwd+CCL", "value": round(value, 1), "unit": "images/s",
-            "n_gpus": world, "n_ranks_rccl": n_ranks_rccl, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "ms_per_step_first_block": round(first_block_ms, 4),
+        line.update({
+            "ms_per_step_median_of_six_blocks": round(float(np.median([ms_per_step] + block_ms)), 4),
             "ms_per_step_spread": {"blocks_of_K_steps_after_the_timed_one": [round(v, 4) for v in block_ms],
                                    "min": round(min(block_ms), 4), "median": round(float(np.median(block_ms)), 4), "max": round(max(block_ms), 4)},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "clock_settle_steps": max(0, SETTLE_STEPS - args.warmup), "input_ring_MB": input_ring_mb,
             "ms_per_step_single_tensor": round(single_ms, 4),
             "ms_per_step_rect_maps": round(rect_ms, 4), "ms_per_step_many_object_maps": round(many_ms, 4),
-            "config": {"workload": "configs[1]: batch=32 512x512x3 fp32 forward + CCL postprocess per GPU "
-                                   "(stripe-textured rectangle images, random-init weights)",
-                       "batch_per_gpu": BATCH, "image": [SIDE, SIDE, C_IN], "parallelism": f"replicas x{world}, no collective"},
             "roofline": roofline, "roofline_forward_pass": fwd_hbm, "cpu_baseline": cpu, "train_step": train, "train_step_8_classes": train_cls8, "train_step_f32": train_f32, "forward_fp16_cfg5": cfg5, "latency_batch1": latency, "pcie_inclusive_host_numpy": host_path,
             "parts": {"net_ms": round(net_ms, 4), "net_ms_single_tensor": round(net_single_ms, 4), "postprocess_ms_on_net_maps": round(post_ms, 4),
                       "postprocess_ms_on_rectangle_maps": round(post_rect_ms, 4),
@@ -850,7 +891,7 @@ def main():
                       "rect_maps_objects_found_mean": float(rect_counts.mean()), "rect_maps_objects_found_max": int(rect_counts.max()),
                       "many_object_maps_objects_found_mean": float(many_counts.mean()), "many_object_maps_objects_found_max": int(many_counts.max()),
                       "clock_settle_launches": SETTLE_STEPS},
-        }
+        })
     if dist is not None and not args.no_train:
         # configs[3].  The headline number above must not depend on this leg: if the multi-rank exchange stalls (it cannot be
         # exercised before the run on a one-GPU development box), every rank gives up after TRAIN_DP_TIMEOUT_S, rank 0 prints the

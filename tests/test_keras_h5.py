@@ -108,39 +108,19 @@ def test_batchnorm_model_file_is_read_and_folded(golden_dir):
 
 
 # ------------------------------------------------------------------------------------------------ the writer (net.py:418-427)
-H5PY_PYTHON = "/opt/conda/bin/python3.9"          # an interpreter with the real h5py / libhdf5 (build container; not a dependency)
-
-_H5PY_CHECK = r"""
-import sys, json, h5py, numpy as np
-path, want_model = sys.argv[1], sys.argv[2] == "1"
-f = h5py.File(path, "r")
-out = {"root_attrs": sorted(f.attrs.keys())}
-g = f["model_weights"] if want_model else f
-out["layer_names"] = [n.decode() for n in g.attrs["layer_names"]]
-out["backend"] = g.attrs["backend"].decode(); out["keras_version"] = g.attrs["keras_version"].decode()
-names, sums, shapes = [], [], []
-for n in out["layer_names"]:
-    for w in g[n].attrs["weight_names"]:
-        d = g[n][w.decode()]
-        assert d.dtype == np.float32
-        names.append(w.decode()); shapes.append(list(d.shape)); sums.append(float(np.asarray(d[()], np.float64).sum()))
-out["weight_names"], out["shapes"], out["sums"] = names, shapes, sums
-if want_model:
-    cfg = json.loads(f.attrs["model_config"].decode())
-    out["classes"] = [l["class_name"] for l in cfg["config"]["layers"]]
-    out["cfg_names"] = [l["name"] for l in cfg["config"]["layers"]]
-    out["model_class"] = cfg["class_name"]; out["outputs"] = cfg["config"]["output_layers"]
-print(json.dumps(out))
-"""
+# what the real libhdf5 / h5py read from the writer's file for each case below, with the sha256 of the bytes it read
+# (tests/golden/make_keras_writer_golden.py, run once with an interpreter that has h5py)
+H5PY_RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "keras_writer_h5py.json")
+WRITER_CASES = [(3, 0, True, True), (1, 2, False, False), (3, 3, True, True), (1, 0, True, True)]
 
 
-@pytest.mark.parametrize("c_in,n_cls,fml,whole", [(3, 0, True, True), (1, 2, False, False), (3, 3, True, True), (1, 0, True, True)])
+@pytest.mark.parametrize("c_in,n_cls,fml,whole", WRITER_CASES)
 def test_writer_round_trip_and_real_h5py(tmp_path, c_in, n_cls, fml, whole):
     """ubdvss_amd.keras_h5_writer emits what keras.Model.save / save_weights emit (net.py:418-427): read back by this package's
-    reader, and -- where an interpreter with the real h5py exists -- by libhdf5 itself: same layer names, weight names, shapes,
-    values and attributes as Keras writes; model_config parses into the layer list of net.py:278-314."""
+    reader, and byte for byte the file that libhdf5 itself read (H5PY_RECORD): same layer names, weight names, shapes, values and
+    attributes as Keras writes; model_config parses into the layer list of net.py:278-314."""
+    import hashlib
     import json
-    import subprocess
     from ubdvss_amd import keras_h5_writer
     shapes = weight_shapes(c_in, n_cls)
     w = _expected(200 + c_in + n_cls, shapes)
@@ -151,11 +131,11 @@ def test_writer_round_trip_and_real_h5py(tmp_path, c_in, n_cls, fml, whole):
     assert names[0] == "separable_conv2d_1/depthwise_kernel:0" and names[-1] == "conv2d_7/bias:0"
     with pytest.raises(ValueError):
         keras_h5_writer.write_keras_model(path + "x", w[:-1], c_in, n_cls, fml, whole)
-    if not os.path.exists(H5PY_PYTHON):
-        pytest.skip("no interpreter with h5py here: the libhdf5 half of the check needs one")
-    r = subprocess.run([H5PY_PYTHON, "-c", _H5PY_CHECK, path, "1" if whole else "0"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = json.loads(r.stdout.strip().splitlines()[-1])
+    with open(H5PY_RECORD) as f:
+        rec = json.load(f)["cases"][f"{c_in},{n_cls},{int(fml)},{int(whole)}"]
+    with open(path, "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == rec["sha256"], "the writer's bytes changed: re-check them with make_keras_writer_golden.py"
+    got = rec["h5py"]
     assert got["weight_names"] == names and got["shapes"] == [list(s) for s in shapes]
     assert np.allclose(got["sums"], [float(a.astype(np.float64).sum()) for a in w], rtol=0, atol=1e-9)
     assert got["backend"] == "tensorflow" and got["keras_version"] == "2.2.4"

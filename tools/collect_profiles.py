@@ -1,10 +1,10 @@
-"""Copies the outputs of tools/gpu_profile_set.sh from gpurun_out/ into profiles/<round>_*: the bench line = the MEDIAN (by value) of the
-three default runs, the line measured with the driver's flags, kernel stats, traffic tables; then writes the profile meta (fingerprint of the
+"""Copies the outputs of tools/gpu_profile_set.sh from prof_out/ into profiles/<round>_*: the bench line = the MEDIAN (by value) of the
+three --full runs, the line measured with the driver's flags, kernel stats, traffic tables; then writes the profile meta (fingerprint of the
 kernel sources).  usage: python tools/collect_profiles.py r05"""
 import json, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rnd = sys.argv[1]
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, "prof_out"), os.path.join(ROOT, "profiles")
 lines = []
 for i in (1, 2, 3):
     txt = open(os.path.join(G, f"bench_default_{i}.json")).read().strip().splitlines()

@@ -1,9 +1,11 @@
 #!/bin/bash
 # HBM traffic (FETCH_SIZE, WRITE_SIZE: separate --pmc passes, kernel-trace only) of EVERY kernel of one pass:
-# UBD_PMC_DTYPE=float32|bfloat16|float16, UBD_PMC_TRAIN=1 for a train step at batch 64 (forward passes: batch 32).  Table -> gpurun_out/pmc_traffic_<tag>.txt
+# UBD_PMC_DTYPE=float32|bfloat16|float16, UBD_PMC_TRAIN=1 for a train step at batch 64 (forward passes: batch 32).
+# Table -> prof_out/pmc_traffic_<tag>.txt under the repository root (another folder: UBD_PMC_OUT)
 TAG=${UBD_PMC_DTYPE:-float32}${UBD_PMC_TRAIN:+_train}
-OUT="$GRAFT_REPO_ROOT/gpurun_out/pmc_traffic_${TAG}.txt"
-mkdir -p $GRAFT_REPO_ROOT/gpurun_out; rm -f "$OUT"
+OUT_DIR=${UBD_PMC_OUT:-$(cd "$(dirname "$0")/.." && pwd)/prof_out}
+OUT="$OUT_DIR/pmc_traffic_${TAG}.txt"
+mkdir -p "$OUT_DIR"; rm -f "$OUT"
 cd /tmp && export TMPDIR=/tmp
 cat > /tmp/fwd_once.py <<'PY'
 import sys, os, torch
