@@ -15,9 +15,14 @@
 //       (the chunk-rotated layout stem23's phase A reads)
 //   A   L2 on 9 x 32 positions (as stem23.h, CARRY variant; wave 7 first moves the inherited 33rd L2 column into place);
 //   B   L3 (waves 0-3), 16-byte stores.
+// The pointwise products of L2 and L3 (K = 24) are exact three-way bf16 split products (split3.h, as the Winograd layer):
+// 12 v_mfma_f32_16x16x32_bf16 of 16 cycles per unit of 16 positions instead of 12 v_mfma_f32_16x16x4_f32 of 32 cycles that no
+// vector instruction issues beside.  L1's (K = 3: two fp32 MFMAs per unit) stays fp32.  stem23_kernel / sepconv_kernel keep the
+// fp32 MFMAs: the reference side of tests/test_gpu_forward.py::test_fused_stem_path.
 // Two block barriers per tile, one 8-wave block per CU: phase B of tile t shares its barrier interval with phase 0b of tile
 // t + 1 (waves 4-7, which have no L3 row, take twice the L1 units).  Training keeps the separate kernels (it needs a1 and a2).
 #pragma once
+#include "split3.h"
 
 // a1 patch image of this kernel: pixel pitch 24 dwords = six 16-byte chunks; chunk c of the pixel in patch column `col` sits in
 // slot c ^ bit2(col) (c < 4) / 4 + ((c - 4) ^ bit3(col)) (c = 4, 5).  Found by enumerating swizzles under the LDS bank map of
@@ -46,7 +51,8 @@ template <int CIN> struct s123_cfg {
     static constexpr int UPW = (UNITS + NW - 1) / NW;              // units per wave
     static constexpr int W1_FLOATS = 64 * 12 + 64 + 4;              // L1 per-lane weights (9 depthwise taps, 2 pointwise, pad) + biases of L1 / L3 (2 x 32) + the ring of strip ids
     static constexpr int LUT_FLOATS = 256;                          // uint8 input: the 256 preprocessed values (one lookup per element instead of a subtract + an exact division)
-    static constexpr int STEM_FLOATS = A1_FLOATS + B::L2_FLOATS + XP_FLOATS + B::W3PW_FLOATS + B::W3DW_FLOATS + B::CARRY_FLOATS + W1_FLOATS + LUT_FLOATS;
+    static constexpr int PWS_U32 = 2 * 3 * 64 * 4;                 // pointwise weights of L2 / L3 as bf16 pieces: [nt][piece][lane] x 16 B (wino6.hip's fragment form)
+    static constexpr int STEM_FLOATS = A1_FLOATS + B::L2_FLOATS + XP_FLOATS + 2 * PWS_U32 + B::W3DW_FLOATS + B::CARRY_FLOATS + W1_FLOATS + LUT_FLOATS;
     static constexpr int PP_FLOATS = (PP_LDS_MAX_BYTES + 3) / 4;   // the postprocess job some blocks run first (pp_lds.h) uses the same LDS
     static constexpr int SMEM_FLOATS = STEM_FLOATS > PP_FLOATS ? STEM_FLOATS : PP_FLOATS;
     static_assert(XCH <= 64 && (A1_FLOATS % 4) == 0 && (B::L2_FLOATS % 4) == 0, "patch rows are single 16-byte-aligned DMA pieces");
@@ -108,21 +114,42 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     float *a1p = smem;
     float *l2 = a1p + X::A1_FLOATS;
     float *xp = l2 + C::L2_FLOATS;
-    float *w3pw = xp + X::XP_FLOATS, *w3dw = w3pw + C::W3PW_FLOATS;
+    unsigned *pws = (unsigned *)(xp + X::XP_FLOATS);             // [layer (L2, L3)][X::PWS_U32]
+    float *w3dw = (float *)(pws + 2 * X::PWS_U32);
     float *carry_buf = w3dw + C::W3DW_FLOATS;
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = lane & 15, q = lane >> 4;
 
-    // ---- weights.  L2's 66 per-lane values live in VGPRs (hot phase); L1's eleven too; L3's come from LDS tables.
-    float dwk2[9][6], pwf2[6][2];
+    // ---- weights.  L2's 54 depthwise per-lane values live in VGPRs (hot phase); its pointwise pieces and L1's and L3's weights
+    // come from LDS tables.
+    float dwk2[9][6];
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         const int ch = s < 4 ? 4 * q + s : 16 + 2 * q + (s - 4);
         const int src_lane = 16 * (ch / 6) + i, ss = ch % 6;
 #pragma unroll
         for (int t = 0; t < 9; ++t) dwk2[t][s] = frag2[UBD_SEP_FRAG_FLOATS + (t * 6 + ss) * 64 + src_lane];
-        pwf2[s][0] = frag2[(ss * 2 + 0) * 64 + src_lane]; pwf2[s][1] = frag2[(ss * 2 + 1) * 64 + src_lane];
     }
+    // Pointwise product of one unit (16 positions x 24 channels -> 24 channels): the lane's six depthwise sums (channels 4q .. 4q+3,
+    // 16+2q, 17+2q = k-slots 0..5 of k-group q) split into three bf16 pieces P1..P3, the weights' pieces U1..U3 read from a table
+    // filled below (ds_read_b128 per piece and N tile), and six of the nine piece products per N tile chained into accumulators
+    // that hold the bias: U3 P1, U2 P2, U2 P1, U1 P3, U1 P2, U1 P1 -- grouped by weight piece, so that only one piece of the
+    // weights (8 registers) is live at a time.  The large product is last: rounded once.  The two tiles' chains alternate (no back-to-back dependent pair).
+    auto pw_split = [&](const unsigned *tab, f32x4 v4, f32x2 v2, f32x4 &acc0, f32x4 &acc1) {
+        const u32x4 *w = (const u32x4 *)tab + lane;
+        const f32x4 r4 = resid(v4), t4 = resid(r4);
+        const f32x2 r2 = resid(v2), t2 = resid(r2);
+        const u32x4 P1 = pack6(v4, v2), P2 = pack6(r4, r2), P3 = pack6(t4, t2);
+        u32x4 U0 = w[2 * 64], U1 = w[5 * 64];                                        // piece 3 of N tiles 0, 1
+        acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
+        U0 = w[1 * 64]; U1 = w[4 * 64];                                              // piece 2
+        acc0 = mfma16(U0, P2, acc0); acc1 = mfma16(U1, P2, acc1);
+        acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
+        U0 = w[0]; U1 = w[3 * 64];                                                   // piece 1
+        acc0 = mfma16(U0, P3, acc0); acc1 = mfma16(U1, P3, acc1);
+        acc0 = mfma16(U0, P2, acc0); acc1 = mfma16(U1, P2, acc1);
+        acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
+    };
     // L1's eleven per-lane values (lane (i, q): input channel q, zero weights for q >= C_in) sit in an LDS table and are
     // re-read at the start of every phase 0b: kept in VGPRs across phase A they cost 11 spilled registers
     float *w1t = carry_buf + C::CARRY_FLOATS;
@@ -251,6 +278,15 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
         const int ar = (live ? p : 0) / X::AC, ac = (live ? p : 0) - ar * X::AC + 1;
         u_rc[k] = live ? ((ar << 8) | ac) : -1;
     }
+    // Register-fed variants (!PLAIN): the offsets derived from u_rc are rebuilt in every phase 0b -- the empty asm (no instruction)
+    // hides the value's loop invariance.  Hoisted out of the tile loop by the compiler, ~24 of them per lane were spilled to scratch
+    // and reloaded every tile once the split products (pw_split) raised phase A's register pressure beside the staged patch
+    // (xreg).  The PLAIN variants do not spill them, and rebuilding them there cost the whole gain of the split products.
+    auto u_rc_tile = [&](int k) {
+        int rc = u_rc[k];
+        if constexpr (!PLAIN) asm volatile("" : "+v"(rc));
+        return rc;
+    };
     const int qc = q < CIN ? q : CIN - 1;                         // lanes without a channel (zero weights) read what their neighbours read: an LDS broadcast, not a second address on the same banks
     // ---- phase A constants (stem23.h, CARRY variant)
     const int half = wid & 1, rg = wid >> 1;
@@ -319,7 +355,8 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     // the FMA chains side by side, the MFMAs back to back, the epilogues -- and the waves that also own an L3 row put that
     // row between their tap reads and the rest (l1_finish), so the reads are long complete when they are consumed.
     auto l1_taps = [&](int k, float (&tap)[9]) {
-        const int rc0 = u_rc[k] < 0 ? 1 : u_rc[k];                                   // lanes without a pixel compute on pixel (0, 1) and store nothing
+        const int rck = u_rc_tile(k);
+        const int rc0 = rck < 0 ? 1 : rck;                                           // lanes without a pixel compute on pixel (0, 1) and store nothing
         const int ar0 = rc0 >> 8, ac0 = rc0 & 255;
         const int u_rd = (2 * ar0) * X::XS + (2 * (ac0 - 1) + 1) * CIN + qc;
 #pragma unroll
@@ -352,7 +389,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
         }
 #pragma unroll
         for (int k = 0; k < NU; ++k) {
-            const int rc = u_rc[k0 + k];
+            const int rc = u_rc_tile(k0 + k);
             const int ar = rc >> 8, ac = rc & 255;
             const bool inside = rc >= 0 && (unsigned)(A0y + ar) < (unsigned)H2 && (unsigned)(A0x + ac) < (unsigned)W2;
             const float cap = inside ? __builtin_inff() : 0.f;                       // outside L1's map: L2's zero padding
@@ -382,19 +419,28 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     };
 
     // ---- first tile: patch -> LDS, L1.  The LDS weight tables are filled while the patch is on its way (and not at all by a block
-    // that found no strip left).  L1's eleven per-lane values, the biases of L1 / L3, L3's pointwise and depthwise tables:
+    // that found no strip left; after the postprocess job, which uses the same LDS).  L1's eleven per-lane values, the biases of
+    // L1 / L3, the pointwise pieces of L2 / L3 and L3's depthwise table:
     if constexpr (PLAIN) dma_x(cur); else load_x(cur);
     {   // every thread's (up to) six table entries: all loads first, then the stores -- one memory round trip (as loops of
         // load -> store the fills took 1.8 us of the prologue)
-        static_assert(64 * 12 <= 2 * C::NT && C::W3PW_FLOATS <= 2 * C::NT && C::W3DW_FLOATS <= C::NT, "table entries per thread");
+        static_assert(64 * 12 <= 2 * C::NT && 2 * X::PWS_U32 / 3 == 2 * C::NT && C::W3DW_FLOATS <= C::NT, "table entries per thread");
         auto w1_entry = [&](int e) {
             const int ln = e / 12, k = e - ln * 12;
             return k < 9 ? frag1[UBD_SEP_FRAG_FLOATS + (k * 6) * 64 + ln] : (k < 11 ? frag1[(k - 9) * 64 + ln] : 0.f);
         };
-        auto w3pw_entry = [&](int e) {
-            const int nt = e >> 9, ln = (e >> 3) & 63, s = e & 7, lq = ln >> 4, li = ln & 15;
+        // pointwise item e = (layer, nt, lane, dword d): the weights of k-slots 2d, 2d + 1 (zero for slots 6, 7)
+        auto pw_weight = [&](int e, int s) {
+            const int nt = (e >> 8) & 1, ln = (e >> 2) & 63, lq = ln >> 4, li = ln & 15;
             const int ch = s < 4 ? 4 * lq + s : 16 + 2 * lq + (s - 4);
-            return s < 6 ? frag3[((ch % 6) * 2 + nt) * 64 + 16 * (ch / 6) + li] : 0.f;
+            return s < 6 ? ((e >> 9) ? frag3 : frag2)[((ch % 6) * 2 + nt) * 64 + 16 * (ch / 6) + li] : 0.f;
+        };
+        auto pw_store = [&](int e, float lo, float hi) {                             // the three piece dwords of item e
+            unsigned bl[3], bh[3];
+            split3_bits(lo, bl); split3_bits(hi, bh);
+            unsigned *dst = pws + (e >> 9) * X::PWS_U32 + (((e >> 8) & 1) * 3 * 64 + ((e >> 2) & 63)) * 4 + (e & 3);
+#pragma unroll
+            for (int pc = 0; pc < 3; ++pc) dst[pc * 64 * 4] = (bl[pc] >> 16) | bh[pc];
         };
         auto w3dw_entry = [&](int e) {
             const int lq = e / 72, r = e - lq * 72, t = r >> 3, s = r & 7;
@@ -402,10 +448,13 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
             return s < 6 ? frag3[UBD_SEP_FRAG_FLOATS + (t * 6 + ch % 6) * 64 + 16 * (ch / 6)] : 0.f;
         };
         const int t = (int)threadIdx.x;
-        const int e1 = t + C::NT < 64 * 12 ? t + C::NT : t, e3 = t + C::NT < C::W3PW_FLOATS ? t + C::NT : t, ed = t < C::W3DW_FLOATS ? t : 0;
-        const float v0 = w1_entry(t), v1 = w1_entry(e1), v2 = w3pw_entry(t), v3 = w3pw_entry(e3), v4 = w3dw_entry(ed);
+        const int e1 = t + C::NT < 64 * 12 ? t + C::NT : t, ed = t < C::W3DW_FLOATS ? t : 0;
+        const float v0 = w1_entry(t), v1 = w1_entry(e1), v4 = w3dw_entry(ed);
+        const int d0 = 2 * (t & 3), d1 = d0 + 1;
+        const float p0 = pw_weight(t, d0), p1 = pw_weight(t, d1), p2 = pw_weight(t + C::NT, d0), p3 = pw_weight(t + C::NT, d1);
         const float v5 = (t & 31) < UBD_C ? (t < 32 ? bias1 : bias3)[t & 31] : 0.f;
-        w1t[t] = v0; w1t[e1] = v1; w3pw[t] = v2; w3pw[e3] = v3; w3dw[ed] = v4;
+        w1t[t] = v0; w1t[e1] = v1; w3dw[ed] = v4;
+        pw_store(t, p0, p1); pw_store(t + C::NT, p2, p3);
         if (t < 64) bt[t] = v5;
         if constexpr (IN_U8) { if (t < 256) lut[t] = ((float)t - pre_sub) / pre_div; }     // the expression the conversion applied per element: same bits
     }
@@ -477,11 +526,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                     if (yy >= 2) {
                         const int o = yy - 2;
                         f32x4 acc0 = b2A, acc1 = b2B;
-#pragma unroll
-                        for (int s = 0; s < 6; ++s) {
-                            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(pwf2[s][0], dwv[o][s], acc0, 0, 0, 0);
-                            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pwf2[s][1], dwv[o][s], acc1, 0, 0, 0);
-                        }
+                        pw_split(pws, (f32x4){dwv[o][0], dwv[o][1], dwv[o][2], dwv[o][3]}, (f32x2){dwv[o][4], dwv[o][5]}, acc0, acc1);
                         float cap = __builtin_inff();
                         if (mask_needed) {
                             const bool ok = (unsigned)(C0 + pos) < (unsigned)W2 && (unsigned)(R0 + rb + o) < (unsigned)H2;
@@ -528,14 +573,8 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                     dv[2] = fmaf(v4[2], w4[2], dv[2]); dv[3] = fmaf(v4[3], w4[3], dv[3]);
                     dv[4] = fmaf(v2[0], w2[0], dv[4]); dv[5] = fmaf(v2[1], w2[1], dv[5]);
                 }
-            const f32x4 pa0 = *(const f32x4 *)(w3pw + lane * 8), pa1 = *(const f32x4 *)(w3pw + 512 + lane * 8);
-            const f32x2 pb0 = *(const f32x2 *)(w3pw + lane * 8 + 4), pb1 = *(const f32x2 *)(w3pw + 512 + lane * 8 + 4);
             f32x4 acc0 = *(const f32x4 *)(bt + 32 + 4 * q), acc1 = *(const f32x4 *)(bt + 48 + 4 * q);
-#pragma unroll
-            for (int s = 0; s < 6; ++s) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(s < 4 ? pa0[s] : pb0[s - 4], dv[s], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(s < 4 ? pa1[s] : pb1[s - 4], dv[s], acc1, 0, 0, 0);
-            }
+            pw_split(pws + X::PWS_U32, (f32x4){dv[0], dv[1], dv[2], dv[3]}, (f32x2){dv[4], dv[5]}, acc0, acc1);
             store_tile_relu_nb(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, COLD && cur.tx > 0 && i == 0);   // bias already in
             S123_STAMP(5);
             if (!has_next) break;

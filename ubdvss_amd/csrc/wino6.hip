@@ -21,12 +21,7 @@
 // (v_and / v_sub / v_perm: 5.5 instructions per value) beside the MFMAs.  Scaling the input by a power of two scales every
 // piece by it: f(2x) = 2 f(x) stays bit-exact.
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "split3.h"
 
 // U fragments of one layer: [xi = a*4+b (16)][nt (2)][piece (3)][lane (64)] x 4 dwords (8 bf16 k-slots of the lane's k-group)
 //   lane = (m = lane & 15 : output channel co = m + 16 nt, zero rows for co >= 24;  q = lane >> 4 : k-group)
@@ -51,16 +46,12 @@ __global__ void pack_wino6_kernel(const float *__restrict__ params, unsigned *__
                 for (int ky = 0; ky < 3; ++ky)
                     for (int kx = 0; kx < 3; ++kx)
                         v += G[ta][ky] * G[tb][kx] * wk[((ky * 3 + kx) * UBD_C + ci) * UBD_C + co];
-                // exact three-way truncation split
-                const unsigned b1 = __float_as_uint(v) & 0xffff0000u;
-                const float r1 = v - __uint_as_float(b1);
-                const unsigned b2 = __float_as_uint(r1) & 0xffff0000u;
-                const float r2 = r1 - __uint_as_float(b2);
-                const unsigned b3 = __float_as_uint(r2) & 0xffff0000u;
+                unsigned b[3];
+                split3_bits(v, b);                             // exact three-way truncation split
                 const int sh = (e & 1) ? 0 : 16;              // even slot: low half of the dword
-                p[0][e >> 1] |= b1 >> sh;
-                p[1][e >> 1] |= b2 >> sh;
-                p[2][e >> 1] |= b3 >> sh;
+                p[0][e >> 1] |= b[0] >> sh;
+                p[1][e >> 1] |= b[1] >> sh;
+                p[2][e >> 1] |= b[2] >> sh;
             }
         }
         unsigned *o = out + ((size_t)(idx >> 6) * 3 * 64 + lane) * 4;      // idx >> 6 = (L * 16 + xi) * 2 + nt
@@ -87,16 +78,7 @@ void ubd_launch_pack_wino6(const ubd_handle *h, const float *params, unsigned *o
 //     packed form for the opposite reason: beside fp32 MFMAs it sits in the MFMA's shadow at one wave per SIMD).
 //   Other per-instruction prices that shaped the code (same file): v_perm_b32 / v_cvt_pk_bf16_f32 / v_max_f32 / v_add3_u32 / any
 //   instruction with an SGPR source ~1.95 ns, v_and_b32 with a literal 1.05 ns, s_nop and scalar ALU ~1.9 ns of the wave's time.
-// residual of the truncation to bf16: v - hi16(v), exact
-__device__ __forceinline__ f32x4 resid(f32x4 v) { return v - __builtin_bit_cast(f32x4, __builtin_bit_cast(u32x4, v) & 0xffff0000u); }
-__device__ __forceinline__ f32x2 resid(f32x2 v) { return v - __builtin_bit_cast(f32x2, __builtin_bit_cast(u32x2, v) & 0xffff0000u); }
-// {hi16(lo), hi16(hi)} as one dword of two bf16 k-slots
-__device__ __forceinline__ unsigned pack_hi(float lo, float hi) { return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u); }
-__device__ __forceinline__ u32x4 pack6(f32x4 a, f32x2 b) { return (u32x4){pack_hi(a[0], a[1]), pack_hi(a[2], a[3]), pack_hi(b[0], b[1]), 0u}; }
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+// resid / pack_hi / pack6 / mfma16: split3.h
 
 #ifdef UBD_STAMPS   // diagnostic build only (tools/build_diag.sh)
 static unsigned long long *g_wino6_stamps = nullptr;
