@@ -35,6 +35,7 @@ struct ubd_handle {
     int use_wino;             // 1: Winograd F(2x2,3x3) dilated layers (default), 0: direct implicit GEMM (UBD_DILCONV=direct)
     int loss_chain;           // UBD_LOSS=chain: the loss as its five dependent launches (the batch-global mode's form) instead of the one-launch kernel (diagnostics / tests)
     int wino_x6;              // forward Winograd products as three-way bf16 split products on the bf16 MFMA (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
+    int wino6_natural;        // UBD_WINO6_LAYOUT=natural: the fp32 inference pass keeps every activation in the natural column order (wino6.hip)
 };
 
 static const int UBD_DILATIONS[UBD_NUM_DIL] = {1, 2, 4, 8, 16, 1};
@@ -231,7 +232,8 @@ void ubd_launch_dilconv_wino(const ubd_handle *h, int epi, const float *frag, co
                              const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head = nullptr);
 void ubd_launch_pack_wino6(const ubd_handle *h, const float *params, unsigned *out, hipStream_t st);
 void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag, const float *bias, int dilation,
-                              const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head = nullptr);
+                              const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head = nullptr,
+                              int lay_in = 1, int lay_out = 1);
 void ubd_launch_pack_direct(const ubd_handle *h, const float *params, float *wfrag, hipStream_t st);
 size_t ubd_forward16_workspace_bytes(int n, int H, int W);
 int ubd_pack16_workspace(ubd_handle *h, const float *params, char *ws, size_t ws_bytes, hipStream_t st);

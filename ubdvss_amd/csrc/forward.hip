@@ -91,20 +91,22 @@ __device__ __forceinline__ void store_tile_relu_t(float *__restrict__ y, size_t 
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o1), rs, (int)base1, 0, 0);
 }
 
-// same with the bias already in the accumulators (it rode in as the MFMA's C operand): ReLU in one instruction per value
+// same with the bias already in the accumulators (it rode in as the MFMA's C operand): ReLU in one instruction per value.
+// l2p: the row is stored in column layout P_(2^l2p) of width ow (wino6.hip; 0 = natural order)
 __device__ __forceinline__ void store_tile_relu_nb(float *__restrict__ y, size_t row_base_elems, int x0, int ow,
-                                                   int lane, f32x4 acc0, f32x4 acc1, bool drop = false /* this lane's pixel is not stored */)
+                                                   int lane, f32x4 acc0, f32x4 acc1, bool drop = false /* this lane's pixel is not stored */,
+                                                   int l2p = 0)
 {
     const int i = lane & 15, q = lane >> 4;
-    const unsigned long long rp = (unsigned long long)(y + (row_base_elems + (size_t)x0) * UBD_C);
+    const unsigned long long rp = (unsigned long long)(y + row_base_elems * UBD_C);
     const unsigned rlo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rp);
     const unsigned rhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rp >> 32));
     float *rowp = (float *)(((unsigned long long)rhi << 32) | rlo);
-    int npx = ow - x0 < 16 ? ow - x0 : 16;
-    npx = npx < 0 ? 0 : npx;
-    const unsigned bytes = (unsigned)__builtin_amdgcn_readfirstlane(npx * UBD_C * 4);
+    const unsigned bytes = (unsigned)__builtin_amdgcn_readfirstlane(ow * UBD_C * 4);
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)rowp, 0, (int)bytes, 0x00020000);
-    const unsigned base = drop ? 0x40000000u : (unsigned)i * (UBD_C * 4u) + 16u * (unsigned)q;
+    const int x = x0 + i, r = x & ((1 << l2p) - 1), wr = ow & ((1 << l2p) - 1);
+    const int pos = r * (ow >> l2p) + (r < wr ? r : wr) + (x >> l2p);
+    const unsigned base = (drop || x >= ow) ? 0x40000000u : (unsigned)pos * (UBD_C * 4u) + 16u * (unsigned)q;
     const unsigned base1 = (q < 2 && !drop) ? base + 64u : 0x40000000u;
     const float cap = __builtin_inff();
     f32x4 o0, o1;
@@ -693,12 +695,13 @@ void ubd_launch_dilconv(const ubd_handle *h, int epi, const float *frag, const f
         hipLaunchKernelGGL(dilconv_f32_kernel<1>, dim3(grid), dim3(256), 0, st, in, out, frag, aux, n, H4, W4, dilation, in_bytes);
 }
 
+// lay_in / lay_out: column layout periods of the layer's input and output rows (wino6.hip; 1 = natural, the only layout of the other kernels)
 static void launch_dil(const ubd_handle *h, const float *params, const float *wfrag, int k, const float *in, float *out,
-                       int n, int H4, int W4, hipStream_t st)
+                       int n, int H4, int W4, hipStream_t st, int lay_in = 1, int lay_out = 1)
 {
     if (h->wino_x6) {
         ubd_launch_dilconv_wino6(h, 0, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
-                                 UBD_DILATIONS[k], in, out, n, H4, W4, st);
+                                 UBD_DILATIONS[k], in, out, n, H4, W4, st, nullptr, lay_in, lay_out);
         return;
     }
     if (h->use_wino) {
@@ -794,6 +797,14 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     const bool fuse_all = inference && fused_stem_applies(h, n, H);
     UBD_REQUIRE(!pp_job || fuse_all, "ubd_forward: a postprocess job needs the fused stem kernel (internal error)");
     const bool cold_all = inference && !fuse_all && !pp_job && cold_stem_applies(h, n, H);
+    // Column layouts of a3 and L4..L8's outputs (wino6.hip, P_p): L4, L5 and L9 (dilation d = 1, 2, 1) read P_2d, where one sample load
+    // covers one run of 16 pixels instead of 16 pixels d apart.  L4 stores P_4 (runs of 8), L5 stores the natural order (16 pixels 4
+    // apart) that L6..L8 read as before (d >= 4: runs of 4..16 already), L8 stores P_2 (runs of 8) for L9, and L9 stores natural logits
+    // or activations.  L6 reading P_8 (runs of 8 from L5, 16 pixels 8 apart in its own stores) measured 0.8 us slower per pass.  Only with
+    // the one-kernel stem, which writes a3, and the bf16-split Winograd layers; every other path keeps the natural order throughout.
+    static const int phase_lay[UBD_NUM_DIL + 1] = {2, 4, 1, 1, 1, 2, 1};
+    const bool phase_major = h->wino_x6 && !h->wino6_natural && (fuse_all || cold_all);
+    const int a3_l2p = phase_major ? 1 : 0;
     if (cold_all) {
         // L1 -> L2 -> L3 in one kernel, one cold-started tile per work unit (stem123.h COLD): tiles of a row 15 L3 columns apart
         const long tiles = (long)n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3) * (W4 <= 16 ? 1 : 1 + (W4 - 16 + 14) / 15);
@@ -808,7 +819,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
 #else
 #define S123C_STAMP_ARG
 #endif
-#define UBD_LAUNCH_S123C(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV, true>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj S123C_STAMP_ARG)
+#define UBD_LAUNCH_S123C(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV, true>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p S123C_STAMP_ARG)
         const bool plain = !u8 && sc == 0.f && sh == 1.f && (size_t)H * W * h->cfg.c_in * 4 < (1ull << 30) && ((uintptr_t)images & 15) == 0;
         if (h->cfg.c_in == 1) { if (u8) UBD_LAUNCH_S123C(1, 1, 0); else if (plain) UBD_LAUNCH_S123C(1, 0, 1); else UBD_LAUNCH_S123C(1, 0, 0); }
         else { if (u8) UBD_LAUNCH_S123C(3, 1, 0); else if (plain) UBD_LAUNCH_S123C(3, 0, 1); else UBD_LAUNCH_S123C(3, 0, 0); }
@@ -828,7 +839,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
 #else
 #define S123_STAMP_ARG
 #endif
-#define UBD_LAUNCH_S123(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj S123_STAMP_ARG)
+#define UBD_LAUNCH_S123(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p S123_STAMP_ARG)
         const bool plain = !u8 && sc == 0.f && sh == 1.f && (size_t)H * W * h->cfg.c_in * 4 < (1ull << 30) && ((uintptr_t)images & 15) == 0;   // fp32 fed as it is: 16-byte LDS-DMA path (offsets of one image in 30 bits, 16-byte aligned base)
         if (h->cfg.c_in == 1) { if (u8) UBD_LAUNCH_S123(1, 1, 0); else if (plain) UBD_LAUNCH_S123(1, 0, 1); else UBD_LAUNCH_S123(1, 0, 0); }
         else { if (u8) UBD_LAUNCH_S123(3, 1, 0); else if (plain) UBD_LAUNCH_S123(3, 0, 1); else UBD_LAUNCH_S123(3, 0, 0); }
@@ -865,7 +876,8 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
         float *nxt = (float *)(ws + L.off_acts[k + 1]);
         if (fuse_head && k == UBD_NUM_DIL - 1 && h->wino_x6) {
             ubd_launch_dilconv_wino6(h, 2, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
-                                     UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k);
+                                     UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k,
+                                     phase_major ? phase_lay[k] : 1, 1);
             UBD_CHECK_HIP(hipGetLastError());
             return 0;
         }
@@ -875,7 +887,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
             UBD_CHECK_HIP(hipGetLastError());
             return 0;
         }
-        launch_dil(h, params, wfrag, k, cur, nxt, n, H4, W4, st);
+        launch_dil(h, params, wfrag, k, cur, nxt, n, H4, W4, st, phase_major ? phase_lay[k] : 1, phase_major ? phase_lay[k + 1] : 1);
         cur = nxt;
     }
     const long npix = (long)n * H4 * W4;

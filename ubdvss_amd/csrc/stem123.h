@@ -74,7 +74,8 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                                                                 const float *__restrict__ frag2, const float *__restrict__ bias2,
                                                                 const float *__restrict__ frag3, const float *__restrict__ bias3,
                                                                 int n, int H, int W, int H2, int W2, int H4, int W4,
-                                                                float pre_sub, float pre_div, int *__restrict__ ticket, pp_lds_args pj
+                                                                float pre_sub, float pre_div, int *__restrict__ ticket, pp_lds_args pj,
+                                                                int a3_l2p /* L3's output rows in column layout P_(2^a3_l2p) (wino6.hip) */
 #ifdef UBD_STAMPS
                                                                 , unsigned long long *__restrict__ stamps
 #endif
@@ -575,7 +576,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                 }
             f32x4 acc0 = *(const f32x4 *)(bt + 32 + 4 * q), acc1 = *(const f32x4 *)(bt + 48 + 4 * q);
             pw_split(pws + X::PWS_U32, (f32x4){dv[0], dv[1], dv[2], dv[3]}, (f32x2){dv[4], dv[5]}, acc0, acc1);
-            store_tile_relu_nb(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, COLD && cur.tx > 0 && i == 0);   // bias already in
+            store_tile_relu_nb(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, COLD && cur.tx > 0 && i == 0, a3_l2p);   // bias already in
             S123_STAMP(5);
             if (!has_next) break;
             float tap[2][9];

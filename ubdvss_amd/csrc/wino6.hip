@@ -95,6 +95,12 @@ struct w6samples {
     f32x4 v4[4][4];
     f32x2 v2[4][4];
 };
+// Column layouts of the activation rows.  P_p (p a power of two) keeps pixel x of a row at position
+//     (x mod p) floor(W / p) + min(x mod p, W mod p) + floor(x / p):
+// the row's pixels phase by phase, an exact permutation (P_1 = natural order).  A layer of dilation d that reads P_2d groups the 16
+// tiles of one sub-grid phase (phase grouping): each column-b sample load then covers ONE run of 16 pixels, where the natural grouping
+// spreads it over 16 pixels 2 apart at d = 1 (~20 cache lines per instruction instead of ~12; d >= 4 already reads runs of 4 or more).
+// Stores go to any P_p; the Winograd arithmetic of a tile does not depend on which lane holds it, so the results are bit-identical.
 // launch geometry (host): everything the group decode needs, so that the loop holds no integer division
 struct w6geom {
     int n, h, w, d, log2d;
@@ -102,6 +108,8 @@ struct w6geom {
     unsigned groups_x, half_rows, total;
     unsigned magic_gx, magic_hr;      // floor(v / groups_x) = umulhi(v, magic_gx) for v < total (ubd_tile_decoder's rule)
     int wpb;                          // waves per block that take groups (1..8): small launches spread over more CUs (all 8 waves copy the weights)
+    int phase;                        // 1: input in layout P_2d and every group confined to one sub-grid phase; 0: natural input and grouping
+    int l2po;                         // log2 of the output layout's period (0: natural)
 };
 // addresses of one group: wave-uniform row terms (scalar registers; they ride in the buffer instructions' soffset, which IS part of
 // the hardware range check: tools/ubench/buf_soffset.hip) and per-lane column terms.  An invalid row or column is 2^30 (host: tensor
@@ -111,10 +119,12 @@ struct w6addr {
     unsigned lrow[2];     // EPI 2: byte offset of logit (output row rr, x = 0)
     unsigned c4[4];       // column b: this lane's 16-byte chunk (channels 4q ..)
     unsigned c2[4];       // column b: this lane's 8-byte chunk (channels 16 + 2q, 17 + 2q)
+    unsigned oc[2];       // output column c (pixel of sample column 1 + c) in the output layout: this lane's 16-byte chunk
 };
 
 // EPI 0: y = relu(conv + bias);  EPI 2: logits = head(relu(conv + bias)) (one output channel; y is never written)
-template <int EPI>
+// LAY: false = natural input and output (layout terms compiled out), true = the layouts of G.phase / G.l2po
+template <int EPI, bool LAY>
 __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const float *__restrict__ x, float *__restrict__ y,
                                                                      const unsigned *__restrict__ ufrag,
                                                                      const float *__restrict__ bias, w6geom G, const float *__restrict__ head
@@ -171,15 +181,38 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
             A.row[a] = ok ? (img_row + (unsigned)iy) * (unsigned)w * (unsigned)(UBD_C * 4) : BIG;
             if (EPI == 2 && (a == 1 || a == 2)) A.lrow[a - 1] = ok ? (img_row + (unsigned)iy) * (unsigned)w * 4u : BIG;
         }
-        const int tcol = (int)gx * 16 + i;
+        // natural grouping: tile columns tcol = 16 gx + i;  phase grouping: gx = (block, phase ph), the 16 tiles k = 16 block + i of
+        // sub-grid phase ph (tile column xj = 2d k + ph), whose column-b samples sit at positions k + const of ONE phase of P_2d
+        const int ph = (int)(gx & (unsigned)dm1);
+        const int tk = (int)((gx >> log2d) << 4) + i;
+        const bool phase = LAY && G.phase;
+        const int tcol = phase ? (tk << log2d) + ph : (int)gx * 16 + i;
         const int xj = ((tcol >> log2d) << (log2d + 1)) + (tcol & dm1);   // this lane's tile column (pixel x of output (., 0))
+        const int tl = phase ? tk : xj;                                  // lane term of the input positions
+        const int l2p = log2d + 1, wq = w >> l2p, wr = w & (2 * d - 1);
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int ix = xj + (b - 1) * d;
             const bool ok = (unsigned)ix < (unsigned)w;
-            const unsigned cb = (unsigned)ix * (unsigned)(UBD_C * 4);
+            // wave-uniform position offset: P_2d phase (ph + (b - 1) d) mod 2d, one tile on for b = 3, one back for b = 0
+            const int r = ph + (b - 1) * d, rb = r & (2 * d - 1);
+            const int sb = phase ? rb * wq + (rb < wr ? rb : wr) + (r >> l2p) : (b - 1) * d;
+            const unsigned cb = (unsigned)(tl + sb) * (unsigned)(UBD_C * 4);
             A.c4[b] = ok ? cb + lane4 : BIG;
             A.c2[b] = ok ? cb + lane2 : BIG;
+        }
+        // outputs x = xj + c d, c = 0, 1, at their positions in P_(2^l2po): (x mod p) floor(w / p) + min(x mod p, w mod p) + floor(x / p)
+        if constexpr (LAY) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int ox = xj + c * d;
+                const int r = ox & ((1 << G.l2po) - 1);
+                const int wrp = w & ((1 << G.l2po) - 1);
+                const int pos = r * (w >> G.l2po) + (r < wrp ? r : wrp) + (ox >> G.l2po);
+                A.oc[c] = ox < w ? (unsigned)pos * (unsigned)(UBD_C * 4) + lane4 : BIG;
+            }
+        } else {
+            A.oc[0] = A.c4[1]; A.oc[1] = A.c4[2];
         }
     };
     auto load_row = [&](w6samples &D, const w6addr &A, int a) {
@@ -355,16 +388,16 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                         for (int r = 0; r < 4; ++r) part = fmaf(v1[r], hB[r], part);      // hB = 0 for q >= 2
                         part += __shfl_xor(part, 16, 64);                                   // sum over the four channel quarters
                         part += __shfl_xor(part, 32, 64);
-                        // logit offset = pixel * 4: the column term is (c4 - 16q) / 24 for lane quarter 0
-                        const unsigned lcol = (q == 0 && A.c4[1 + c] != BIG) ? A.c4[1 + c] / (unsigned)UBD_C : BIG;
+                        // logit offset = position * 4: the column term is (oc - 16q) / 24 for lane quarter 0
+                        const unsigned lcol = (q == 0 && A.oc[c] != BIG) ? A.oc[c] / (unsigned)UBD_C : BIG;
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, part + hbias), yrsrc, (int)(lcol + A.lrow[rr]), 0, 0);
                     } else {
-                        const unsigned st1 = (q < 2 && A.c4[1 + c] != BIG) ? A.c4[1 + c] + 64u : BIG;
+                        const unsigned st1 = (q < 2 && A.oc[c] != BIG) ? A.oc[c] + 64u : BIG;
                         // Stores take the row term in the VECTOR offset: with it in soffset, hipcc's hazard recogniser assumes that a wide
                         // store followed at once by a vector write to its data registers is safe (true of older chips) and inserts no
                         // wait state; on gfx950 ~0.1 % of the pixels of a 32 x 128 x 128 launch then carried a LATER value (an address
                         // integer) in one dword, different ones run to run (tools/wino6_chk_bias.py, round 6).
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v0), yrsrc, (int)(A.c4[1 + c] + A.row[1 + rr]), 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v0), yrsrc, (int)(A.oc[c] + A.row[1 + rr]), 0, 0);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v1), yrsrc, (int)(st1 + A.row[1 + rr]), 0, 0);
                     }
                 }
@@ -389,15 +422,19 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // frag: this layer's UBD_WINO6_FRAG_U32 packed dwords; epi 0 / 2 as in ubd_launch_dilconv_wino
+// lay_in / lay_out: column layout periods of the input and output rows (powers of two, 1: natural; lay_in is 1 or 2 * dilation)
 void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag, const float *bias, int dilation,
-                              const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head)
+                              const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head,
+                              int lay_in, int lay_out)
 {
     const int d = dilation;
     const long half_rows = ((H4 + 2 * d - 1) / (2 * d)) * d, half_cols = ((W4 + 2 * d - 1) / (2 * d)) * d;
-    const long groups_x = (half_cols + 15) / 16;
+    // phase grouping: d phases x blocks of 16 of the ceil(W4 / 2d) tiles of a phase
+    const long groups_x = lay_in == 1 ? (half_cols + 15) / 16 : (long)d * ((half_cols / d + 15) / 16);
     const long groups = (long)n * half_rows * groups_x;
     w6geom G;
     G.n = n; G.h = H4; G.w = W4; G.d = d; G.log2d = ilog2(d);
+    G.phase = lay_in != 1; G.l2po = ilog2(lay_out);
     G.in_bytes = (unsigned)((size_t)n * H4 * W4 * UBD_C * 4);
     G.groups_x = (unsigned)groups_x; G.half_rows = (unsigned)half_rows; G.total = (unsigned)groups;
     // floor(v / D) = (v * m) >> 32 with m = floor((2^32 - 1) / D) + 1, exact while v * D < 2^32: v < groups <= 2^30 / 96 / 4 pixels
@@ -413,8 +450,13 @@ void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag
     G.wpb = wpb;
     int grid = ubd_grid_for(groups, h->num_cus, wpb, 1);
     grid = (grid + 7) / 8 * 8;
-    if (epi == 2)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<2>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head WSTAMP_ARG);
+    const bool lay = lay_in != 1 || lay_out != 1;
+    if (epi == 2 && lay)
+        hipLaunchKernelGGL((dilconv_wino6_kernel<2, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head WSTAMP_ARG);
+    else if (epi == 2)
+        hipLaunchKernelGGL((dilconv_wino6_kernel<2, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head WSTAMP_ARG);
+    else if (lay)
+        hipLaunchKernelGGL((dilconv_wino6_kernel<0, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr WSTAMP_ARG);
     else
-        hipLaunchKernelGGL((dilconv_wino6_kernel<0>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr WSTAMP_ARG);
+        hipLaunchKernelGGL((dilconv_wino6_kernel<0, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr WSTAMP_ARG);
 }
