@@ -161,6 +161,17 @@ int ubd_adam_step(float *params, const float *grads, float *m, float *v, size_t 
 int ubd_build_label_maps(const double *quads, const int32_t *values, const int32_t *counts, int n, int cap,
                          int map_h, int map_w, int scale, int32_t *labels, void *stream);
 
+/* --- image preparation ------------------------------------------------------
+ * Replaces Image.resize((dst_w, dst_h), Image.BICUBIC) of SegmapManager._rescale_image_and_markup (segmap_manager.py:135-173)
+ * and, for dst_c == 1 from RGB, the Image.convert('L') of data_generators.py:177, for n uint8 images of any sizes to one size.
+ * src + src_offsets[i] (HOST int64 byte offsets) = image i, (src_hw[2i], src_hw[2i+1]) (HOST) rows x cols, rows packed (pitch w*src_c).
+ * dst: uint8 NHWC (n, dst_h, dst_w, dst_c).  Bit-identical to Pillow's 8-bit BICUBIC resampler.
+ * (src_c, dst_c): (1,1), (3,3), (3,1) = resize then convert('L'), (1,3) = the grey result in three channels.
+ * Limits: source sides 1..16384, destination sides 1..8192, n >= 1, n*dst_h*dst_w*dst_c < 2^31 (non-zero return otherwise).
+ * Enqueues one launch per 64 images; no host synchronisation, capturable in a HIP graph. */
+int ubd_resize_images(const uint8_t *src, const int64_t *src_offsets, const int32_t *src_hw, int src_c, int n,
+                      uint8_t *dst, int dst_h, int dst_w, int dst_c, void *stream);
+
 /* --- data parallelism (no reference counterpart: the reference is single-device) -------------------
  * One process per GPU, per-replica loss (losses.py:86-126 applied to the rank's own images), ONE sum all-reduce of the flat
  * fp32 gradient vector per step over RCCL / xGMI, 1/world applied by ubd_adam_step's grad_scale, parameters broadcast once.

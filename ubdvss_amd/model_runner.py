@@ -104,6 +104,12 @@ class ModelRunner:
                                f"(max found {int(counts_h.max())}); raise the capacity")
         detection_logits = bmap_h.astype(np.int64)[..., None]
         classification_logits = np.array(logits_h[..., 1:]) if copy else logits_h[..., 1:]
+        found_objects = self._object_lists(counts_h, quads_h, classes_h)
+        if rescale:
+            found_objects = self.rescale(found_objects, meta_infos)
+        return detection_logits, classification_logits, found_objects
+
+    def _object_lists(self, counts_h, quads_h, classes_h):
         with_cls = self._net_config.is_classification_supported()
         found_objects = []
         for i in range(len(counts_h)):
@@ -113,9 +119,42 @@ class ModelRunner:
                 found_objects.append([ClassifiedObjectMarkup(boxes[j], classes_h[i, j]) for j in range(n)])
             else:
                 found_objects.append([ObjectMarkup(boxes[j]) for j in range(n)])
-        if rescale:
-            found_objects = self.rescale(found_objects, meta_infos)
-        return detection_logits, classification_logits, found_objects
+        return found_objects
+
+    def predict_images(self, model, images, batch_size=None):
+        """Raw images of any sizes -> found objects in ORIGINAL-image coordinates, in input order: the lists the reference's
+        ``run`` evaluates (model_runner.py:65-72) after its host chain reader -> resize -> convert('L') -> predict -> rescale.
+        ``images``: PIL images, HxW / HxWx3 uint8 numpy arrays or uint8 device tensors (SegmapManager.rescale_images_on_device).
+        The images are grouped by ``SegmapManager.target_size`` (the reference batches by resized shape,
+        data_generators.py:133-140); per group (and per ``batch_size`` images of it) they are resized on the device
+        (ubd_resize_images, Pillow's BICUBIC bit for bit) and fed as uint8 to ``predict_on_device`` (the NetConfig
+        preprocessing fused into the first layer); the boxes are scaled back by the MetaInfo scales (``rescale``)."""
+        from .segmap_manager import SegmapManager
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelRunner.predict_images needs an MI355X; there is no CPU fallback")
+        groups = {}
+        for k, im in enumerate(images):
+            if isinstance(im, torch.Tensor) or isinstance(im, np.ndarray):
+                h, w = int(im.shape[0]), int(im.shape[1])
+            else:
+                w, h = im.size
+            groups.setdefault(SegmapManager.target_size(w, h, self._net_config), []).append(k)
+        found = [None] * len(images)
+        for idx in groups.values():
+            step = len(idx) if not batch_size else int(batch_size)
+            for b0 in range(0, len(idx), step):
+                part = idx[b0:b0 + step]
+                x, metas = SegmapManager.rescale_images_on_device([images[k] for k in part], self._net_config, device=model.device)
+                _, _, quads, classes, counts = self.predict_on_device(model, x)
+                self.flush()                            # pipelined runner: this batch's postprocess now, the copies below wait for it
+                counts_h = counts.cpu().numpy()
+                if (counts_h > self._cap).any():
+                    raise RuntimeError(f"more than max_objects_per_image={self._cap} objects in an image "
+                                       f"(max found {int(counts_h.max())}); raise the capacity")
+                objs = self._object_lists(counts_h, quads.cpu().numpy(), classes.cpu().numpy() if classes is not None else None)
+                for k, o in zip(part, self.rescale(objs, metas)):
+                    found[k] = o
+        return found
 
     def predict_stream(self, model, batches, rescale=False, meta_infos=None, copy_threads=8):
         """The loop of the reference's ``ModelRunner.run`` (model_runner.py:60-67: ``predict`` batch after batch) as ONE pipeline:

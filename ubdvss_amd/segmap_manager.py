@@ -3,8 +3,10 @@
 Same static-method signature as the reference; the work (external components, contourArea
 filter, minAreaRect, boxPoints, class vote) runs in libubd_hip.so on the MI355X.
 """
+import collections
 import ctypes
 import logging
+import os
 
 import numpy as np
 import torch
@@ -41,6 +43,81 @@ def _handle(n_classes, device):
             _lib.check(lib.ubd_create(ctypes.byref(cfg), ctypes.byref(h)), "ubd_create")
         _handles[key] = h
     return _handles[key]
+
+
+# per image: the scales of the reference's MetaInfo (data_generators.py:42-55, :189), original / rescaled, read by ModelRunner.rescale
+ResizeMeta = collections.namedtuple("ResizeMeta", ["xscale", "yscale"])
+_staging = {}   # device -> [pinned uint8 tensor, event of the transfer that last read it]
+
+
+def _image_source(image, device):
+    """One source image as an (H, W, C) uint8 array: numpy on the host, or a tensor on ``device`` (read in place)."""
+    if isinstance(image, Image.Image):
+        return np.asarray(image.convert("RGB"))          # the reference's readers (markup_readers.py:97,170)
+    if isinstance(image, torch.Tensor) and image.is_cuda:
+        if image.device != device:
+            raise ValueError(f"image tensor on {image.device}, expected {device}")
+        a = image
+    else:
+        a = image.numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    if a.dtype not in (np.uint8, torch.uint8):
+        raise ValueError(f"images must be uint8, got {a.dtype}")
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3 or a.shape[2] not in (1, 3):
+        raise ValueError(f"images must be HxW, HxWx1 or HxWx3, got shape {tuple(a.shape)}")
+    return a.contiguous() if isinstance(a, torch.Tensor) else np.ascontiguousarray(a)
+
+
+def _stage_host(arrays, device):
+    """Host arrays -> one device buffer through one pinned staging buffer (filled by native threads) and one transfer.
+    Returns (device buffer, byte offsets)."""
+    lib = _lib.load()
+    offsets = np.cumsum([0] + [a.nbytes for a in arrays])
+    total = int(offsets[-1])
+    entry = _staging.get(str(device))
+    if entry is None or entry[0].numel() < total:
+        entry = [torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True), None]
+        _staging[str(device)] = entry
+    elif entry[1] is not None:
+        entry[1].synchronize()                           # the previous transfer out of the staging buffer is over
+    base = entry[0].numpy().ctypes.data
+    try:
+        threads = max(1, min(8, len(os.sched_getaffinity(0)) // 2))
+    except (AttributeError, OSError):
+        threads = 1
+    for a, off in zip(arrays, offsets):
+        lib.ubd_host_memcpy_mt(base + int(off), a.ctypes.data, a.nbytes, threads)
+    buf = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
+    buf[:total].copy_(entry[0][:total], non_blocking=True)
+    entry[1] = torch.cuda.Event()
+    entry[1].record(torch.cuda.current_stream(device))
+    return buf, offsets[:-1]
+
+
+def _resize_sources(srcs, new_h, new_w, dst_c, device):
+    """ubd_resize_images of every source (host arrays and device tensors alike) into one (N, new_h, new_w, dst_c) tensor."""
+    lib = _lib.load()
+    src_c = 3 if any(s.shape[2] == 3 for s in srcs) else 1
+    if src_c == 3:                                       # a grey source among RGB ones: convert('RGB') replicates it
+        srcs = [s if s.shape[2] == 3 else (s.expand(-1, -1, 3).contiguous() if isinstance(s, torch.Tensor) else np.repeat(s, 3, axis=2))
+                for s in srcs]
+    host = [k for k, s in enumerate(srcs) if not isinstance(s, torch.Tensor)]
+    ptrs = [s.data_ptr() if isinstance(s, torch.Tensor) else 0 for s in srcs]
+    staged = None
+    if host:
+        staged, offs = _stage_host([srcs[k] for k in host], device)
+        for k, off in zip(host, offs):
+            ptrs[k] = staged.data_ptr() + int(off)
+    base = min(ptrs)
+    offsets = np.array([p - base for p in ptrs], np.int64)
+    hw = np.array([[s.shape[0], s.shape[1]] for s in srcs], np.int32)
+    out = torch.empty((len(srcs), new_h, new_w, dst_c), dtype=torch.uint8, device=device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(lib.ubd_resize_images(ctypes.c_void_p(base), offsets.ctypes.data, hw.ctypes.data, src_c, len(srcs),
+                                         out.data_ptr(), new_h, new_w, dst_c, stream), "ubd_resize_images")
+    return out
 
 
 class SegmapManager:
@@ -177,15 +254,11 @@ class SegmapManager:
         return int(folded.sum())
 
     @staticmethod
-    def _rescale_image_and_markup(image, markup, net_config, max_side=None):
-        """Image and markup at the size the network wants (behaviour of segmap_manager.py:135-173): if the longer side exceeds
-        ``max_side`` (default ``net_config.get_max_side()``) it becomes exactly ``max_side`` and the other side is scaled
-        in proportion and rounded to a multiple of ``net_config.get_side_multiple()``; otherwise both sides are rounded to
-        that multiple.  Rounding is Python 3's ``round`` (half to even), at least one multiple.  The image is resampled
-        with ``Image.BICUBIC``; every quad is multiplied by (new_w / w, new_h / h) and rewrapped with
-        ``create_same_markup`` (so it stays fractional, float64).  Empty / None markup is returned as it is.  Host-side
-        by nature (a PIL image in, a PIL image out), like the reference."""
-        w, h = image.size
+    def target_size(w, h, net_config, max_side=None):
+        """The size rule of ``_rescale_image_and_markup`` (segmap_manager.py:135-173) for an image of w x h pixels: if the
+        longer side exceeds ``max_side`` (default ``net_config.get_max_side()``) it becomes exactly ``max_side`` and the other
+        side is scaled in proportion and rounded to a multiple of ``net_config.get_side_multiple()``; otherwise both sides are
+        rounded to that multiple.  Rounding is Python 3's ``round`` (half to even), at least one multiple.  Returns (new_w, new_h)."""
         multiple = net_config.get_side_multiple()
         if max_side is None:
             max_side = net_config.get_max_side()
@@ -195,14 +268,74 @@ class SegmapManager:
 
         if max(w, h) > max_side:
             shrink = max_side / max(h, w)
-            new_w, new_h = (max_side, to_multiple(h * shrink)) if w > h else (to_multiple(w * shrink), max_side)
-        else:
-            new_w, new_h = to_multiple(w), to_multiple(h)
+            return (max_side, to_multiple(h * shrink)) if w > h else (to_multiple(w * shrink), max_side)
+        return to_multiple(w), to_multiple(h)
+
+    @staticmethod
+    def _rescale_image_and_markup(image, markup, net_config, max_side=None):
+        """Image and markup at the size the network wants (behaviour of segmap_manager.py:135-173): the size is
+        ``target_size``'s, the image is resampled with ``Image.BICUBIC``; every quad is multiplied by (new_w / w, new_h / h)
+        and rewrapped with ``create_same_markup`` (so it stays fractional, float64).  Empty / None markup is returned as it
+        is.  A PIL image in, a PIL image out, like the reference; ``rescale_images_on_device`` is the batch form on the MI355X."""
+        w, h = image.size
+        new_w, new_h = SegmapManager.target_size(w, h, net_config, max_side)
         resized = image.resize(size=(new_w, new_h), resample=Image.BICUBIC)
+        return resized, SegmapManager._rescale_markup(markup, w, h, new_w, new_h)
+
+    @staticmethod
+    def _rescale_markup(markup, w, h, new_w, new_h):
         if not markup:
-            return resized, markup
+            return markup
         factors = np.array([[new_w / w, new_h / h]])
-        return resized, [m.create_same_markup((np.array(m.bbox).reshape((-1, 2)) * factors).reshape((-1,))) for m in markup]
+        return [m.create_same_markup((np.array(m.bbox).reshape((-1, 2)) * factors).reshape((-1,))) for m in markup]
+
+    @staticmethod
+    def rescale_images_on_device(images, net_config, device=None, max_side=None):
+        """Batch form of the image half of ``_rescale_image_and_markup`` + the ``convert('L')`` of grey nets
+        (data_generators.py:164-180) on the MI355X (ubd_resize_images, bit-identical to Pillow's BICUBIC resize).
+        ``images``: PIL images (taken through ``.convert('RGB')`` like the reference's readers), HxW / HxWx1 / HxWx3 uint8
+        numpy arrays or uint8 device tensors of those shapes (read in place, no copy), of any sizes that share one
+        ``target_size``.  Host images are staged through one pinned buffer and one transfer.
+        Returns (uint8 device tensor (N, new_h, new_w, c_in of the net), [ResizeMeta(xscale, yscale)] per image) where
+        xscale = w / new_w and yscale = h / new_h: the ``MetaInfo`` scales of data_generators.py:189 that ``ModelRunner.rescale``
+        reads.  Raises ValueError if the images do not share one target size."""
+        out, sizes = SegmapManager._rescale_images(images, net_config, device, max_side)
+        new_h, new_w = int(out.shape[1]), int(out.shape[2])
+        return out, [ResizeMeta(w / new_w, h / new_h) for w, h in sizes]
+
+    @staticmethod
+    def _rescale_images(images, net_config, device, max_side=None):
+        """rescale_images_on_device -> (device tensor, [(w, h) of every source image])"""
+        if not torch.cuda.is_available():
+            raise RuntimeError("SegmapManager.rescale_images_on_device needs an MI355X; there is no CPU fallback")
+        device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        srcs = [_image_source(im, device) for im in images]
+        if not srcs:
+            raise ValueError("no images")
+        sizes = [(int(s.shape[1]), int(s.shape[0])) for s in srcs]
+        targets = {SegmapManager.target_size(w, h, net_config, max_side) for w, h in sizes}
+        if len(targets) != 1:
+            raise ValueError(f"the images do not share one target size ({sorted(targets)}); group them by "
+                             "SegmapManager.target_size first (ModelRunner.predict_images does)")
+        new_w, new_h = targets.pop()
+        return _resize_sources(srcs, new_h, new_w, 1 if net_config.is_grey() else 3, device), sizes
+
+    @staticmethod
+    def prepare_batch_on_device(images, markups, net_config, device=None):
+        """Training form of ``prepare_image_and_target`` (+ ``convert('L')`` for grey nets) for a batch on the MI355X:
+        returns (uint8 images (N, h, w, c_in) of ``rescale_images_on_device``, int32 label maps (N, h/scale, w/scale) of
+        ``build_segmentation_maps_on_device``, the markups scaled by (new_w / w, new_h / h) exactly as
+        ``_rescale_image_and_markup`` scales them).  Images as in ``rescale_images_on_device``."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("SegmapManager.prepare_batch_on_device needs an MI355X; there is no CPU fallback")
+        if len(images) != len(markups):
+            raise ValueError("one markup per image is required")
+        x, sizes = SegmapManager._rescale_images(images, net_config, device)
+        new_h, new_w = int(x.shape[1]), int(x.shape[2])
+        rescaled = [SegmapManager._rescale_markup(m, w, h, new_w, new_h) for m, (w, h) in zip(markups, sizes)]
+        labels = SegmapManager.build_segmentation_maps_on_device((new_w, new_h), [m or [] for m in rescaled],
+                                                                 scale=net_config.get_scale(), device=x.device)
+        return x, labels, rescaled
 
     @staticmethod
     def _proper_round(markup_bbox):
