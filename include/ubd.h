@@ -1,6 +1,7 @@
 /* ubd.h -- C ABI of libubd_hip.so: the MI355X (gfx950) implementation of the
  * ubdvss hot path (dilated-FCN forward -> threshold map -> external components ->
- * rotated quads; train step = forward + loss + backward + Adam).
+ * rotated quads; train step = forward + loss + backward + Adam; training input:
+ * geometric augmentation warps, bicubic resize, label rasteriser).
  *
  * The reference (asmekal/ubdvss) has no FFI: the path sits behind three Python
  * seams.  Each entry point below names the seam it replaces (paths relative to
@@ -171,6 +172,36 @@ int ubd_build_label_maps(const double *quads, const int32_t *values, const int32
  * Enqueues one launch per 64 images; no host synchronisation, capturable in a HIP graph. */
 int ubd_resize_images(const uint8_t *src, const int64_t *src_offsets, const int32_t *src_hw, int src_c, int n,
                       uint8_t *dst, int dst_h, int dst_w, int dst_c, void *stream);
+
+/* --- geometric augmentation ---------------------------------------------------
+ * The image half of SegLinksImageAugmentation (augmentation.py:50-85): Image.rotate(angle, BILINEAR, expand=True) (:167),
+ * Image.crop (:117), the quarter turns that Image.rotate performs as Image.transpose (:80), and
+ * Image.transform(size, PERSPECTIVE, coeffs, BILINEAR) (:201), for n uint8 images of `channels` (1 or 3) channels, every image
+ * with its own source and destination size.  Bit-identical to Pillow's generic transform with the bilinear filter.
+ * Image i is read through a signed strided VIEW of the source buffer: view pixel (x, y) is at
+ * src + src_offset + x * src_xpitch + y * src_ypitch (bytes; a packed image has pitches channels and src_w * channels), so a
+ * crop (offset, smaller size) and a quarter turn (pitches swapped / negated) cost no pass of their own.  The destination image is
+ * written packed (row pitch dst_w * channels) at dst + dst_offset; dword stores are used where that address is a multiple
+ * of 4.  mode: UBD_WARP_COPY writes the view out as it is (dst size = view size); UBD_WARP_AFFINE maps destination pixel
+ * centres through coeffs[0..5] (Pillow's AFFINE data: the matrix Image.rotate computes), UBD_WARP_PERSPECTIVE through
+ * coeffs[0..7] (Pillow's PERSPECTIVE data); destination pixels whose source position is outside the view are 0.
+ * descs: HOST array of n descriptors.  src_bytes / dst_bytes: sizes of the two buffers; every view and every destination
+ * must lie inside them.  Source and destination must not overlap.
+ * Limits: sides 1..16384 (so an image stays below 2^31 bytes), n >= 1, finite coefficients (non-zero return otherwise, nothing launched).
+ * Enqueues one launch per 32 images; no host synchronisation, capturable in a HIP graph. */
+enum { UBD_WARP_COPY = 0, UBD_WARP_AFFINE = 1, UBD_WARP_PERSPECTIVE = 2 };
+typedef struct ubd_warp_desc {
+    int64_t src_offset;              /* bytes from src to the view's pixel (0, 0) */
+    int64_t dst_offset;              /* bytes from dst to the destination image */
+    int32_t src_xpitch, src_ypitch;  /* signed bytes per view column / view row */
+    int32_t src_w, src_h;            /* view size */
+    int32_t dst_w, dst_h;
+    int32_t mode;                    /* UBD_WARP_* */
+    int32_t reserved;                /* 0 */
+    double coeffs[8];
+} ubd_warp_desc;
+int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes, const ubd_warp_desc *descs,
+                    int channels, int n, void *stream);
 
 /* --- data parallelism (no reference counterpart: the reference is single-device) -------------------
  * One process per GPU, per-replica loss (losses.py:86-126 applied to the rank's own images), ONE sum all-reduce of the flat

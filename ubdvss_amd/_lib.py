@@ -14,6 +14,7 @@ UBD_COMM_FUSED = 1
 UBD_COMM_GLOBAL_LOSS = 2
 UBD_UNIQUE_ID_BYTES = 128
 ABI_VERSION = 3
+UBD_WARP_COPY, UBD_WARP_AFFINE, UBD_WARP_PERSPECTIVE = 0, 1, 2
 
 
 class UbdConfig(ctypes.Structure):
@@ -48,6 +49,7 @@ SIGNATURES = {
     "ubd_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _f, _f, _f, _f, _f, _vp]),
     "ubd_build_label_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_resize_images": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
+    "ubd_warp_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_comm_unique_id": (_i, [_vp]),
     "ubd_comm_init": (_i, [_vp, _vp, _i, _i, _i]),
     "ubd_comm_destroy": (_i, [_vp]),

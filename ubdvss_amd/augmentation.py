@@ -1,0 +1,437 @@
+"""Geometric augmentation on the MI355X -- host mirror of semantic_segmentation/augmentation.py.
+
+The reference augments every training image on the host with Pillow at full source resolution (augmentation.py:50-85): a
+random rotation in +-45 degrees, a random crop that keeps all markup, a quarter turn (+-90 / 180 degrees), a random
+perspective distortion, and an imgaug photometric stage.  Here the parameters are drawn on the host (``sample_plan``,
+the reference's draws in the reference's order), every image size follows from them on the host, the markup is transformed
+on the host in float64 (``apply_plan_to_markup``), and the pixels are warped on the device by ``ubd_warp_images``
+(csrc/warp.hip), bit-identical to Pillow: at most two passes per image (rotation; perspective or a final copy) -- crops and
+quarter turns are signed strided views that the next pass reads through.
+
+THE PHOTOMETRIC (imgaug) STAGE IS NOT BUILT.  Its draw is consumed so that the parameter stream stays the reference's, and
+the plan records that it was requested (``photometric_requested``); the pixels are left as the geometric chain made them.
+Flips have probability 0 in the reference: their draws are consumed, they are never applied.
+"""
+import collections
+import ctypes
+import logging
+import math
+import random as _random
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import _lib
+
+# kind: 'rotate' {angle}, 'crop' {box: unrounded (left, top, right, bottom), window: Pillow's rounded (x0, y0, x1, y1)},
+# 'quarter' {angle: 90 | -90 | 180}, 'perspective' {coeffs: 8 floats}; size: (w, h) after the stage
+Stage = collections.namedtuple("Stage", ["kind", "params", "size"])
+# size: (w, h) of the source image; original: the 10 % "feed the original" branch was taken (no further draws);
+# photometric_requested: the reference would have run its imgaug stage here (not built, see the module docstring)
+AugmentationPlan = collections.namedtuple("AugmentationPlan", ["size", "stages", "original", "photometric_requested"])
+
+FEED_ORIGINAL_P, ROTATE_P, CROP_P, HFLIP_P, VFLIP_P, ROTATE_90_P, PERSPECTIVE_P, PHOTOMETRIC_P = 0.1, 0.5, 0.5, 0, 0, 0.5, 0.5, 0.7
+ROTATION_90_ANGLES = [90, -90, 180]
+MAX_CROP_MARGIN = 0.4
+PERSPECTIVE_MEAN = np.array([1, 0, 0, 0, 1, 0, 0, 0], np.float64)
+PERSPECTIVE_HALF = np.array([0.1, 0.1, 50, 0.1, 0.1, 50, 0.0002, 0.0002], np.float64)
+
+
+def identity_plan(size):
+    return AugmentationPlan((int(size[0]), int(size[1])), (), False, False)
+
+
+# ---------------------------------------------------------------------------------------------------------------- sizes
+def rotate_matrix_and_size(angle, size):
+    """What ``Image.rotate(angle, BILINEAR, expand=True)`` does with an image of ``size`` = (w, h) (Pillow's Image.py, restated):
+    returns (kind, matrix, (new_w, new_h)) with kind 'copy' (angle % 360 == 0), 'quarter' (90 / 180 / 270: an exact
+    ``Image.transpose``; matrix is the angle) or 'affine' (matrix: the six AFFINE coefficients, destination -> source)."""
+    w, h = size
+    angle = angle % 360.0
+    if angle == 0:
+        return "copy", None, (w, h)
+    if angle == 180:
+        return "quarter", 180, (w, h)
+    if angle in (90, 270):
+        return "quarter", int(angle), (h, w)
+    center = (w / 2, h / 2)
+    angle = -math.radians(angle)
+    matrix = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+              round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+
+    def transform(x, y, matrix):
+        a, b, c, d, e, f = matrix
+        return a * x + b * y + c, d * x + e * y + f
+
+    matrix[2], matrix[5] = transform(-center[0] - 0, -center[1] - 0, matrix)
+    matrix[2] += center[0]
+    matrix[5] += center[1]
+    xx, yy = [], []
+    for x, y in ((0, 0), (w, 0), (w, h), (0, h)):
+        tx, ty = transform(x, y, matrix)
+        xx.append(tx)
+        yy.append(ty)
+    nw = math.ceil(max(xx)) - math.floor(min(xx))
+    nh = math.ceil(max(yy)) - math.floor(min(yy))
+    matrix[2], matrix[5] = transform(-(nw - w) / 2.0, -(nh - h) / 2.0, matrix)
+    return "affine", matrix, (nw, nh)
+
+
+def crop_window(box):
+    """``Image.crop``'s integer window for a float box: Python's ``round`` (half to even) of every coordinate."""
+    return tuple(int(round(v)) for v in box)
+
+
+# --------------------------------------------------------------------------------------------------------------- markup
+def _shapely_cos_sin(angle_degrees):
+    """cosine and sine as shapely.affinity.rotate takes them: values below 2.5e-16 in magnitude are exactly zero, so quarter
+    turns move integer markup to integers (12.000000000000002 would be ceiled to 13 by _proper_round)."""
+    a = angle_degrees * math.pi / 180.0
+    c, s = math.cos(a), math.sin(a)
+    return (0.0 if abs(c) < 2.5e-16 else c), (0.0 if abs(s) < 2.5e-16 else s)
+
+
+def _rotate_points(pts, image_angle, size, new_size):
+    """augmentation.py:165-176, :248-260: the image turns by ``image_angle`` (counter-clockwise on the screen), so the points
+    turn by -image_angle in the y-down frame, about the old centre, and move to the new centre."""
+    c, s = _shapely_cos_sin(-image_angle)
+    x = pts[:, 0] - size[0] / 2
+    y = pts[:, 1] - size[1] / 2
+    return np.stack([c * x - s * y + new_size[0] / 2, s * x + c * y + new_size[1] / 2], axis=1)
+
+
+def perspective_point_matrix(coeffs):
+    """augmentation.py:203-208: Pillow's PERSPECTIVE data maps destination to source, so points move by the inverse 3x3"""
+    return np.linalg.inv(np.reshape(list(coeffs) + [1], (3, 3)).astype(np.float64))
+
+
+def _perspective_points(pts, coeffs):
+    m = perspective_point_matrix(coeffs)
+    res = np.vstack((pts.T, np.ones((1, pts.shape[0]))))
+    res = np.dot(m, res)
+    res /= res[-1, :]
+    return res[:-1].T
+
+
+def _stage_points(stage, pts, size):
+    """(n, 2) float64 points of an image of ``size`` through one stage"""
+    if stage.kind in ("rotate", "quarter"):
+        return _rotate_points(pts, stage.params["angle"], size, stage.size)
+    if stage.kind == "crop":
+        left, top = stage.params["box"][0], stage.params["box"][1]
+        return pts + np.array([[-left, -top]])
+    if stage.kind == "perspective":
+        return _perspective_points(pts, stage.params["coeffs"])
+    raise ValueError(f"unknown stage kind {stage.kind!r}")
+
+
+def _markup_points(markup):
+    return [np.array(m.bbox, dtype=np.float64).reshape(-1, 2) for m in markup]
+
+
+def apply_plan_to_markup(plan, markup):
+    """The markup of an image after ``plan``: new objects of the same type (``create_same_markup``) around float64 boxes;
+    the caller's objects are not touched.  Empty / None markup is returned as it is."""
+    if not markup:
+        return markup
+    boxes = _markup_points(markup)
+    size = plan.size
+    for stage in plan.stages:
+        boxes = [_stage_points(stage, b, size) for b in boxes]
+        size = stage.size
+    return [m.create_same_markup(b.reshape(-1)) for m, b in zip(markup, boxes)]
+
+
+# -------------------------------------------------------------------------------------------------------------- sampler
+def _normalize_rect(rect, image_size):
+    """augmentation.py:126-162: the markup bounds clipped to the image and widened along one axis when their aspect is
+    far from the image's.  Raises ZeroDivisionError for bounds of zero height."""
+    r = list(rect)
+    r[0] = max(0, r[0])
+    r[1] = max(0, r[1])
+    r[2] = min(image_size[0], r[2])
+    r[3] = min(image_size[1], r[3])
+    rect_width = r[2] - r[0]
+    rect_height = r[3] - r[1]
+    ratio = rect_width / rect_height
+    image_ratio = image_size[0] / image_size[1]
+    if ratio < image_ratio * 0.7:
+        new_width = image_ratio * rect_height
+        if r[0] < (image_size[0] - new_width) / 2:
+            r[2] = r[0] + new_width
+        elif r[2] > (image_size[0] + new_width) / 2:
+            r[0] = r[2] - new_width
+        else:
+            r[0] = (image_size[0] - new_width) / 2
+            r[2] = r[0] + new_width
+    elif ratio > image_ratio * 1.3:
+        new_height = rect_width / image_ratio
+        if r[1] < (image_size[1] - new_height) / 2:
+            r[3] = r[1] + new_height
+        elif r[3] > (image_size[1] + new_height) / 2:
+            r[1] = r[3] - new_height
+        else:
+            r[1] = (image_size[1] - new_height) / 2
+            r[3] = r[1] + new_height
+    return r
+
+
+def _sample_crop(boxes, size, rng):
+    """augmentation.py:94-117: the four draws of the crop (left, top, right, bottom).  Returns the stage, or None (nothing
+    drawn) when the markup bounds have no width or no height."""
+    allp = np.concatenate(boxes, axis=0)
+    bounds = [float(allp[:, 0].min()), float(allp[:, 1].min()), float(allp[:, 0].max()), float(allp[:, 1].max())]
+    if not (bounds[2] > bounds[0] and bounds[3] > bounds[1]):
+        logging.warning("augmentation: markup bounds %s have no width or no height; crop skipped", bounds)
+        return None
+    try:
+        rect = _normalize_rect(bounds, size)
+    except ZeroDivisionError:
+        logging.warning("augmentation: markup bounds %s have no height inside the %d x %d image; crop skipped", bounds, size[0], size[1])
+        return None
+    w, h = size
+    max_left = min(MAX_CROP_MARGIN * w, rect[0])
+    max_right = min(MAX_CROP_MARGIN * w, w - rect[2])
+    max_top = min(MAX_CROP_MARGIN * h, rect[1])
+    max_bottom = min(MAX_CROP_MARGIN * h, h - rect[3])
+    left = rng.uniform(0, max_left)
+    top = rng.uniform(0, max_top)
+    right = w - rng.uniform(0, max_right)
+    bottom = h - rng.uniform(0, max_bottom)
+    box = (left, top, right, bottom)
+    x0, y0, x1, y1 = crop_window(box)
+    if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):
+        logging.warning("augmentation: crop box %s rounds to the window %s, which is empty or leaves the %d x %d image; crop skipped",
+                        box, (x0, y0, x1, y1), w, h)
+        return None
+    return Stage("crop", {"box": box, "window": (x0, y0, x1, y1)}, (x1 - x0, y1 - y0))
+
+
+def sample_plan(image_size, markup, rng=None, np_rng=None):
+    """Draws the parameters of the reference's ``__augment_image`` (augmentation.py:50-85) for one image of ``image_size`` =
+    (w, h) and its ``markup`` and returns an ``AugmentationPlan``: the stages with their numbers and the image size after each.
+
+    The generators are consumed in the reference's order, so seeding ``random`` and ``numpy.random`` as augmentation.py:29-31
+    invites gives the reference's parameter stream: nothing for empty markup; ``random()`` (< 0.1: feed the original, stop);
+    ``random()`` (< 0.5) -> ``uniform(-45, 45)``; ``random()`` (< 0.5) -> four ``uniform`` (left, top, right, bottom);
+    two ``random()`` for the flips (probability 0); ``random()`` (< 0.5) -> ``choice([90, -90, 180])`` and the
+    ``uniform(angle, angle)`` of the reference's ``__rotate``; ``random()`` (< 0.5) -> one ``np_rng.uniform`` of 8 numbers;
+    ``random()`` (< 0.7) for the photometric stage, WHICH IS NOT BUILT: the plan only records that it was requested.
+    ``rng`` / ``np_rng``: objects with the interface of the ``random`` / ``numpy.random`` modules (the defaults).
+    A stage whose input is degenerate (markup bounds without width or height, a crop that rounds to an empty window) is
+    skipped with a warning and the chain goes on."""
+    rng = _random if rng is None else rng
+    np_rng = np.random if np_rng is None else np_rng
+    size = (int(image_size[0]), int(image_size[1]))
+    if markup is None or len(markup) == 0:
+        return AugmentationPlan(size, (), False, False)
+    if rng.random() < FEED_ORIGINAL_P:
+        return AugmentationPlan(size, (), True, False)
+    boxes = _markup_points(markup)
+    stages = []
+    cur = size
+
+    def push(stage):
+        nonlocal boxes, cur
+        boxes = [_stage_points(stage, b, cur) for b in boxes]
+        cur = stage.size
+        stages.append(stage)
+
+    if rng.random() < ROTATE_P:
+        angle = rng.uniform(-45, 45)
+        push(Stage("rotate", {"angle": angle}, rotate_matrix_and_size(angle, cur)[2]))
+    if rng.random() < CROP_P:
+        stage = _sample_crop(boxes, cur, rng)
+        if stage is not None:
+            push(stage)
+    rng.random()                                        # horizontal flip, probability 0
+    rng.random()                                        # vertical flip, probability 0
+    if rng.random() < ROTATE_90_P:
+        angle = rng.choice(ROTATION_90_ANGLES)
+        angle = rng.uniform(angle, angle)               # the draw of the reference's __rotate; the value is `angle` exactly
+        push(Stage("quarter", {"angle": int(angle)}, rotate_matrix_and_size(angle, cur)[2]))
+    if rng.random() < PERSPECTIVE_P:
+        coeffs = np_rng.uniform(PERSPECTIVE_MEAN - PERSPECTIVE_HALF, PERSPECTIVE_MEAN + PERSPECTIVE_HALF).tolist()
+        push(Stage("perspective", {"coeffs": coeffs}, cur))
+    photometric = rng.random() < PHOTOMETRIC_P
+    return AugmentationPlan(size, tuple(stages), False, bool(photometric))
+
+
+# --------------------------------------------------------------------------------------------------------------- device
+WARP_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("src_xpitch", np.int32), ("src_ypitch", np.int32),
+                      ("src_w", np.int32), ("src_h", np.int32), ("dst_w", np.int32), ("dst_h", np.int32), ("mode", np.int32),
+                      ("reserved", np.int32), ("coeffs", np.float64, (8,))], align=True)      # ubd_warp_desc of include/ubd.h
+
+
+class _View:
+    """A signed strided view of an image in device memory: pixel (x, y) at ptr + x * xp + y * yp; ``keep`` holds the tensor alive"""
+    __slots__ = ("ptr", "xp", "yp", "w", "h", "c", "keep")
+
+    def __init__(self, ptr, w, h, c, keep):
+        self.ptr, self.xp, self.yp, self.w, self.h, self.c, self.keep = int(ptr), c, w * c, int(w), int(h), c, keep
+
+    def packed(self):
+        return self.xp == self.c and self.yp == self.w * self.c
+
+    def crop(self, x0, y0, x1, y1):
+        self.ptr += x0 * self.xp + y0 * self.yp
+        self.w, self.h = x1 - x0, y1 - y0
+
+    def quarter(self, angle):
+        """Image.transpose(ROTATE_90 / ROTATE_180 / ROTATE_270): new(x, y) = old(w-1-y, x) / old(w-1-x, h-1-y) / old(y, h-1-x)"""
+        angle = angle % 360
+        if angle == 90:
+            self.ptr += (self.w - 1) * self.xp
+            self.xp, self.yp = self.yp, -self.xp
+            self.w, self.h = self.h, self.w
+        elif angle == 180:
+            self.ptr += (self.w - 1) * self.xp + (self.h - 1) * self.yp
+            self.xp, self.yp = -self.xp, -self.yp
+        elif angle == 270:
+            self.ptr += (self.h - 1) * self.yp
+            self.xp, self.yp = -self.yp, self.xp
+            self.w, self.h = self.h, self.w
+        else:
+            raise ValueError(f"not a quarter turn: {angle}")
+
+    def span(self):
+        ex, ey = (self.w - 1) * self.xp, (self.h - 1) * self.yp
+        return self.ptr + min(ex, 0) + min(ey, 0), self.ptr + max(ex, 0) + max(ey, 0) + self.c
+
+
+def _warp_pass(jobs, c, device):
+    """One ubd_warp_images call: jobs = [(view, mode, coeffs, (dst_w, dst_h))]; the views are replaced by packed views of one
+    new device buffer."""
+    lib = _lib.load()
+    starts, pos = [], 0
+    for _, _, _, (dw, dh) in jobs:
+        starts.append(pos)
+        pos += (dw * dh * c + 255) & ~255                     # every image on a 256-byte boundary: dword stores
+    out = torch.empty(max(pos, 1), dtype=torch.uint8, device=device)
+    spans = [v.span() for v, _, _, _ in jobs]
+    base = min(lo for lo, _ in spans)
+    src_bytes = max(hi for _, hi in spans) - base
+    descs = np.zeros(len(jobs), WARP_DESC)
+    for k, (v, mode, coeffs, (dw, dh)) in enumerate(jobs):
+        d = descs[k]
+        d["src_offset"], d["dst_offset"] = v.ptr - base, starts[k]
+        d["src_xpitch"], d["src_ypitch"], d["src_w"], d["src_h"] = v.xp, v.yp, v.w, v.h
+        d["dst_w"], d["dst_h"], d["mode"] = dw, dh, mode
+        if coeffs is not None:
+            d["coeffs"][:len(coeffs)] = coeffs
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(lib.ubd_warp_images(ctypes.c_void_p(base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data, c, len(jobs),
+                                       stream), "ubd_warp_images")
+    for k, (v, _, _, (dw, dh)) in enumerate(jobs):
+        v.__init__(out.data_ptr() + starts[k], dw, dh, c, out)
+
+
+def warp_views_on_device(views, plans, device):
+    """Runs the plans' pixel chains on the device, stage by stage over all images: pass 1 -- every rotation; crops and quarter
+    turns only change the views; pass 2 -- every perspective, and a copy for images whose chain ends in a crop or a quarter
+    turn.  Stream-ordered: no host synchronisation, no device-to-host copy.  The views end up packed."""
+    c = views[0].c
+    rest = []
+    jobs = []
+    for v, plan in zip(views, plans):
+        if (v.w, v.h) != tuple(plan.size):
+            raise ValueError(f"plan made for a {plan.size[0]} x {plan.size[1]} image, the image is {v.w} x {v.h}")
+        stages = list(plan.stages)
+        if stages and stages[0].kind == "rotate":
+            kind, matrix, size = rotate_matrix_and_size(stages[0].params["angle"], (v.w, v.h))
+            if kind == "affine":
+                jobs.append((v, _lib.UBD_WARP_AFFINE, matrix, size))
+                stages = stages[1:]
+            elif kind == "copy":
+                stages = stages[1:]
+            else:
+                stages[0] = Stage("quarter", {"angle": matrix}, size)
+        rest.append(stages)
+    if jobs:
+        _warp_pass(jobs, c, device)
+    jobs = []
+    for v, stages in zip(views, rest):
+        persp = None
+        for st in stages:
+            if st.kind == "crop":
+                v.crop(*st.params["window"])
+            elif st.kind == "quarter":
+                v.quarter(st.params["angle"])
+            elif st.kind == "perspective" and persp is None:
+                persp = st.params["coeffs"]
+            else:
+                raise ValueError(f"stage {st.kind!r} out of the chain's order (rotate, crop, quarter, perspective)")
+            if (v.w, v.h) != tuple(st.size):
+                raise ValueError(f"plan says {st.size} after {st.kind}, the image is {(v.w, v.h)}")
+        if persp is not None:
+            jobs.append((v, _lib.UBD_WARP_PERSPECTIVE, persp, (v.w, v.h)))
+        elif not v.packed():
+            jobs.append((v, _lib.UBD_WARP_COPY, None, (v.w, v.h)))
+    if jobs:
+        _warp_pass(jobs, c, device)
+    return views
+
+
+def _view_tensor(v):
+    """the (h, w, c) uint8 tensor of a packed view"""
+    off = v.ptr - v.keep.data_ptr()
+    return v.keep.reshape(-1)[off:off + v.h * v.w * v.c].view(v.h, v.w, v.c)
+
+
+def augment_arrays_on_device(arrays, plans, device=None):
+    """(H, W, C) uint8 images (numpy arrays on the host, staged through one pinned buffer and one transfer, or tensors on the
+    device, read in place; all with the same C of 1 or 3) through their plans -> list of (h, w, C) uint8 device tensors.
+    The photometric stage is not built (module docstring)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("augmentation on the device needs an MI355X; there is no CPU fallback")
+    from .segmap_manager import _stage_host
+    device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+    if len(arrays) != len(plans):
+        raise ValueError("one plan per image is required")
+    if not arrays:
+        return []
+    c = int(arrays[0].shape[2])
+    if c not in (1, 3) or any(a.ndim != 3 or a.shape[2] != c for a in arrays):
+        raise ValueError("images must all be HxWx1 or all HxWx3")
+    host = [k for k, a in enumerate(arrays) if not isinstance(a, torch.Tensor)]
+    views = [None] * len(arrays)
+    if host:
+        staged, offs = _stage_host([arrays[k] for k in host], device)
+        for k, off in zip(host, offs):
+            views[k] = _View(staged.data_ptr() + int(off), arrays[k].shape[1], arrays[k].shape[0], c, staged)
+    for k, a in enumerate(arrays):
+        if views[k] is None:
+            views[k] = _View(a.data_ptr(), a.shape[1], a.shape[0], c, a)
+    warp_views_on_device(views, plans, device)
+    return [_view_tensor(v) for v in views]
+
+
+class SegLinksImageAugmentation:
+    """The reference's class (augmentation.py:34-91) for one PIL image ('L' or 'RGB') and its markup: draws a plan from the
+    ``random`` / ``numpy.random`` modules (or the given generators), runs its geometric chain on the MI355X and returns a PIL
+    image of the same mode.  Nothing is drawn and nothing changes for empty markup.  The caller's markup objects are not
+    mutated.  THE PHOTOMETRIC (imgaug) STAGE IS NOT BUILT: ``plan.photometric_requested`` says whether the reference would
+    have run it.  Needs an MI355X (RuntimeError otherwise: no CPU fallback)."""
+
+    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("SegLinksImageAugmentation needs an MI355X; there is no CPU fallback")
+        if image.mode not in ("L", "RGB"):
+            raise ValueError(f"image mode must be 'L' or 'RGB', got {image.mode!r}")
+        self.__net_config = net_config
+        self.plan = sample_plan(image.size, markup, rng, np_rng) if plan is None else plan
+        self.__aug_image, self.__aug_markup = image, markup
+        if not self.plan.stages:
+            return
+        a = np.asarray(image)
+        out = augment_arrays_on_device([np.ascontiguousarray(a[:, :, None] if a.ndim == 2 else a)], [self.plan])[0].cpu().numpy()
+        self.__aug_image = Image.fromarray(out[:, :, 0] if image.mode == "L" else out, image.mode)
+        self.__aug_markup = apply_plan_to_markup(self.plan, markup)
+
+    def get_modified_image(self):
+        return self.__aug_image
+
+    def get_modified_markup(self):
+        return self.__aug_markup

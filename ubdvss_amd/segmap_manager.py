@@ -160,12 +160,15 @@ class SegmapManager:
 
     @staticmethod
     def prepare_image_and_target(image, markup, net_config, augment=False):
-        """segmap_manager.py:24-39 without the augmentation branch (imgaug pipeline: outside the hot path):
+        """segmap_manager.py:24-39: with ``augment``, the geometric chain of the reference's augmentation first (one PIL image
+        through ``SegLinksImageAugmentation``: parameters from ``random`` / ``numpy.random``, pixels warped on the MI355X,
+        bit-identical to Pillow; the imgaug photometric stage is NOT built, see ubdvss_amd/augmentation.py), then
         rescale image + markup to the network's size rule, build the label map at ``net_config.get_scale()``.
         Returns (image, markup, label map) like the reference."""
         if augment:
-            raise ValueError("augmentation is not part of this package (SURVEY.md section 2: out of scope); augment the "
-                             "image and markup first, then call prepare_image_and_target(..., augment=False)")
+            from .augmentation import SegLinksImageAugmentation
+            aug = SegLinksImageAugmentation(image, markup, net_config)
+            image, markup = aug.get_modified_image(), aug.get_modified_markup()
         image, markup = SegmapManager._rescale_image_and_markup(image, markup, net_config)
         return image, markup, SegmapManager.build_segmentation_map(image, markup, scale=net_config.get_scale())
 
@@ -336,6 +339,50 @@ class SegmapManager:
         labels = SegmapManager.build_segmentation_maps_on_device((new_w, new_h), [m or [] for m in rescaled],
                                                                  scale=net_config.get_scale(), device=x.device)
         return x, labels, rescaled
+
+    @staticmethod
+    def prepare_batches_on_device(images, markups, net_config, augment=True, plans=None, device=None):
+        """Training form of ``prepare_image_and_target(..., augment=True)`` (+ ``convert('L')`` for grey nets) for a batch on
+        the MI355X.  Augmented images no longer share one size, and the reference groups a batch by resized shape
+        (data_generators.py:133-140), so the result is a list with one entry per target size, in order of first appearance:
+        (indices into ``images``, uint8 images (n, h, w, c_in), int32 label maps (n, h/scale, w/scale), the augmented and
+        rescaled markups, the plans), every list in the order of ``indices``.
+        Chain: the raw images are staged once -> the warp passes of all images (``ubd_warp_images``: every rotation, then every
+        perspective / final copy; crops and quarter turns are views) -> ``ubd_resize_images`` per group ->
+        ``ubd_build_label_maps`` per group; no host synchronisation and no device-to-host copy in between.
+        ``plans``: one ``AugmentationPlan`` per image to replay (tests, reproducibility); otherwise ``augment=True`` draws them
+        with ``augmentation.sample_plan`` from ``random`` / ``numpy.random`` in image order, ``augment=False`` uses empty plans.
+        The imgaug photometric stage is NOT built (ubdvss_amd/augmentation.py).  Images as in ``rescale_images_on_device``."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("SegmapManager.prepare_batches_on_device needs an MI355X; there is no CPU fallback")
+        from . import augmentation
+        if len(images) != len(markups):
+            raise ValueError("one markup per image is required")
+        if plans is not None and len(plans) != len(images):
+            raise ValueError("one plan per image is required")
+        if not len(images):
+            raise ValueError("no images")
+        device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        srcs = [_image_source(im, device) for im in images]
+        if any(s.shape[2] == 3 for s in srcs):                 # a grey source among RGB ones: convert('RGB') replicates it
+            srcs = [s if s.shape[2] == 3 else (s.expand(-1, -1, 3).contiguous() if isinstance(s, torch.Tensor) else np.repeat(s, 3, axis=2))
+                    for s in srcs]
+        if plans is None:
+            plans = [augmentation.sample_plan((s.shape[1], s.shape[0]), m) if augment else augmentation.identity_plan((s.shape[1], s.shape[0]))
+                     for s, m in zip(srcs, markups)]
+        warped = augmentation.augment_arrays_on_device(srcs, plans, device)
+        moved = [augmentation.apply_plan_to_markup(p, m) for p, m in zip(plans, markups)]
+        groups = collections.OrderedDict()
+        for i, t in enumerate(warped):
+            groups.setdefault(SegmapManager.target_size(int(t.shape[1]), int(t.shape[0]), net_config), []).append(i)
+        out = []
+        for (new_w, new_h), idx in groups.items():
+            x = _resize_sources([warped[i] for i in idx], new_h, new_w, 1 if net_config.is_grey() else 3, device)
+            rescaled = [SegmapManager._rescale_markup(moved[i], int(warped[i].shape[1]), int(warped[i].shape[0]), new_w, new_h) for i in idx]
+            labels = SegmapManager.build_segmentation_maps_on_device((new_w, new_h), [m or [] for m in rescaled],
+                                                                     scale=net_config.get_scale(), device=device)
+            out.append((idx, x, labels, rescaled, [plans[i] for i in idx]))
+        return out
 
     @staticmethod
     def _proper_round(markup_bbox):
