@@ -203,6 +203,62 @@ typedef struct ubd_warp_desc {
 int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes, const ubd_warp_desc *descs,
                     int channels, int n, void *stream);
 
+/* --- object-level evaluation ----------------------------------------------------
+ * Replaces FtMetricsCalculator (evaluation.py:168-429: areas, the G x F intersection / IoU tables :210-227, analyze :229-328, the
+ * confusion matrix increments :330-362, group IoU :379-387, precision / recall / IoU by area :389-404) for a whole batch and every
+ * IoU threshold at once, and the summing half of FtMetrics.append (:53-97): the accumulator holds SUMS, the host forms the
+ * running averages from them.  The found objects are the outputs of ubd_postprocess as they lie in device memory.
+ * Ground-truth polygons: convex, 3..UBD_EVAL_MAX_VERTS vertices, either winding (normalised on the device); found quads: 4
+ * vertices.  All geometry in fp64; areas of unions are exact boundary integrals, not rasterised (tie rules: evaluate.hip).
+ *   scales         : device (n, 2) xscale, yscale or NULL: found coordinate = trunc(coordinate * scale) (utils.py:67-69,
+ *                    model_runner.py:140-148)
+ *   gt_xy          : device, packed x,y of the vertices of all ground-truth polygons of the call (n_gt_vertices vertices)
+ *   gt_first       : device (total_gt + 1) first vertex of each polygon; total_gt = gt_image_first[n].  The device checks every
+ *                    polygon's vertex range against n_gt_vertices (a range outside it, or not 3..8 vertices, flags the image);
+ *                    the length of gt_first itself is the caller's to keep
+ *   gt_class       : device (total_gt) class index 0..n_classes-1, or NULL when n_classes == 0
+ *   gt_image_first : HOST (n + 1) first polygon of each image; max_gt >= the largest number of polygons of one image
+ *   thresholds     : HOST (n_thresholds) doubles, compared as they are (tp needs iou >= t, detection_rate iou_by_area > t)
+ *   per_image      : device (n, n_thresholds) records or NULL
+ *   accumulator    : device, ubd_evaluate_accumulator_bytes(n_thresholds, n_classes) bytes, zeroed by the caller before the first
+ *                    call, as 8-byte slots: [0] int64 images scored, [1] int64 images flagged (not scored), [2..4] double sums of
+ *                    precision / recall / IoU by area, [5..7] unused; then 10 slots per threshold: int64 tp, fp, fn, one_to_one,
+ *                    one_to_many, many_to_one, matched_boxes_count, detection_rate, double iou_sum, unused; then double
+ *                    (n_thresholds, n_classes, n_classes) confusion sums [actual][predicted].
+ * Per-image contributions are added in image order by one block: the same calls give the same bits.  An image whose counts[i]
+ * exceeds cap (a truncated list, see ubd_postprocess) or whose ground truth is malformed is NOT scored: its records carry
+ * flags != 0 and slot [1] counts it.  Limits: n >= 1, polygons per image <= UBD_EVAL_MAX_GT, cap <= UBD_EVAL_MAX_FOUND,
+ * n_thresholds <= UBD_EVAL_MAX_THRESHOLDS, n_classes <= UBD_MAX_CLASSES (non-zero return otherwise, nothing launched).
+ * Enqueues four launches per 64 images; no host synchronisation, capturable in a HIP graph. */
+#define UBD_EVAL_MAX_VERTS 8
+#define UBD_EVAL_MAX_GT 256
+#define UBD_EVAL_MAX_FOUND 256
+#define UBD_EVAL_MAX_THRESHOLDS 16
+enum { UBD_EVAL_FLAG_OVERFLOW = 1, UBD_EVAL_FLAG_BAD_GT = 2 };
+typedef struct ubd_eval_record {             /* FtMetrics of one image at one threshold (evaluation.py:262-328), sums not averages */
+    int32_t tp, fp, fn;
+    int32_t one_to_one, one_to_many, many_to_one;
+    int32_t matched_boxes_count;
+    int32_t detection_rate;                  /* 0 / 1 */
+    int32_t n_gt, n_found;
+    int32_t flags;                           /* UBD_EVAL_FLAG_*; non-zero: every other counter is 0 */
+    int32_t reserved;
+    double iou_sum;                          /* sum of the matched IoUs (average_iou * matched_boxes_count) */
+    double precision_by_area, recall_by_area, iou_by_area;
+} ubd_eval_record;
+size_t ubd_evaluate_accumulator_bytes(int n_thresholds, int n_classes);                       /* 0 for sizes outside the limits */
+size_t ubd_evaluate_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes);   /* 0 for sizes outside the limits */
+int ubd_evaluate_objects(const int32_t *quads, const int32_t *classes, const int32_t *counts, int n, int cap,
+                         const double *scales, const double *gt_xy, int n_gt_vertices, const int32_t *gt_first,
+                         const int32_t *gt_class, const int32_t *gt_image_first, int max_gt,
+                         const double *thresholds, int n_thresholds, int n_classes,
+                         ubd_eval_record *per_image, void *accumulator, void *workspace, size_t workspace_bytes, void *stream);
+/* Diagnostics: where the last ubd_evaluate_objects call with these sizes left its tables in the workspace (the arrays
+ * FtMetricsCalculator.__init__ builds, evaluation.py:210-227).  Image i starts at workspace + *offset_bytes + i * *stride_doubles * 8:
+ * double areas of the ground truths [max_gt], areas of the found quads [cap], intersections [max_gt][cap], IoU [max_gt][cap]. */
+int ubd_evaluate_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int64_t *offset_bytes,
+                               int64_t *stride_doubles);
+
 /* --- data parallelism (no reference counterpart: the reference is single-device) -------------------
  * One process per GPU, per-replica loss (losses.py:86-126 applied to the rank's own images), ONE sum all-reduce of the flat
  * fp32 gradient vector per step over RCCL / xGMI, 1/world applied by ubd_adam_step's grad_scale, parameters broadcast once.

@@ -15,11 +15,19 @@ UBD_COMM_GLOBAL_LOSS = 2
 UBD_UNIQUE_ID_BYTES = 128
 ABI_VERSION = 3
 UBD_WARP_COPY, UBD_WARP_AFFINE, UBD_WARP_PERSPECTIVE = 0, 1, 2
+UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS = 8, 256, 256, 16
+UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
 
 
 class UbdConfig(ctypes.Structure):
     _fields_ = [("c_in", ctypes.c_int32), ("n_classes", ctypes.c_int32),
                 ("fml_compatible", ctypes.c_int32), ("dtype", ctypes.c_int32)]
+
+
+class UbdEvalRecord(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("tp", "fp", "fn", "one_to_one", "one_to_many", "many_to_one", "matched_boxes_count",
+                                              "detection_rate", "n_gt", "n_found", "flags", "reserved")] + \
+               [(k, ctypes.c_double) for k in ("iou_sum", "precision_by_area", "recall_by_area", "iou_by_area")]
 
 
 # every symbol include/ubd.h declares: name -> (restype, argtypes)
@@ -50,6 +58,10 @@ SIGNATURES = {
     "ubd_build_label_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_resize_images": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
     "ubd_warp_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
+    "ubd_evaluate_accumulator_bytes": (_sz, [_i, _i]),
+    "ubd_evaluate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ubd_evaluate_objects": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ubd_evaluate_tables_layout": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_comm_unique_id": (_i, [_vp]),
     "ubd_comm_init": (_i, [_vp, _vp, _i, _i, _i]),
     "ubd_comm_destroy": (_i, [_vp]),

@@ -82,6 +82,30 @@ class ModelRunner:
         bmap, quads, classes, counts = slot["out"]
         return logits, bmap, quads, classes, counts
 
+    def evaluate_batches(self, model, batches):
+        """The device form of the evaluation loop of ModelRunner.run (model_runner.py:60-75, :102): for every
+        (images, gt_objects, meta_infos) batch the forward pass, the postprocess and the object-level evaluation
+        (ubd_evaluate_objects) are enqueued on the current stream -- the found objects never leave the device; the quads are
+        rescaled to the original images there with meta.xscale / meta.yscale (meta_infos may be None: no rescale) -- and
+        the ``scalar_logs`` of DatasetMetricCalculator.get_metrics are returned after ONE read of the device sums.
+        images: (N,H,W,C) numpy array or device tensor; gt_objects: per image a list of markup records."""
+        from .evaluation import DatasetMetricCalculator
+        evaluator = DatasetMetricCalculator(self._net_config)
+        for images, gt_objects, meta_infos in batches:
+            if not torch.is_tensor(images):
+                x = np.asarray(images)
+                if x.dtype != np.uint8:
+                    x = x.astype(np.float32, copy=False)
+                images = torch.from_numpy(np.ascontiguousarray(x))
+            images = images.to(model.device)
+            if meta_infos is not None and len(meta_infos) != len(images):
+                raise AssertionError("one meta_info per image is required")
+            _, _, quads, classes, counts = self.predict_on_device(model, images)
+            self.flush()                                # pipelined runner: this batch's postprocess before its evaluation
+            scales = None if meta_infos is None else np.array([[m.xscale, m.yscale] for m in meta_infos], dtype=np.float64)
+            evaluator.evaluate_batch(gt_objects, (quads, classes, counts), meta_infos=meta_infos, scales=scales)
+        return evaluator.get_metrics()
+
     def predict(self, model, images, rescale=False, meta_infos=None):
         """Same contract as the reference (model_runner.py:105-138): returns
         (detection map (N,h,w,1) of {0,1}, classification_logits (N,h,w,n_cls), found_objects)."""
