@@ -1,6 +1,6 @@
-"""Bit-equality of the 16-bit train step between two builds of the library (a refactoring that must not change a single bit -- round 6: the
-ReLU masks of the separable backward read as bits): each build runs in a child process on the same seeded batches (several shapes, ragged
-widths, both 16-bit types, uint8 and fp32 input, 1 and 3 input channels), prints a digest of gradients, parameters and loss per step; the
+"""Bit-equality of the train step (bf16, fp16 and fp32 activations) between two builds of the library (a refactoring that must not change a single bit):
+each build runs in a child process on the same seeded batches (several shapes, ragged
+widths, all three activation types, uint8 and fp32 input, 1 and 3 input channels), prints a digest of gradients, parameters and loss per step; the
 parent compares.   python tools/cmp_train_libs.py tools/_ab/bwd_before.so product"""
 import hashlib, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +12,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "child":
     MOBILENET_LIKE = PreprocessingType.MOBILENET_LIKE
     torch.cuda.set_device(0)
     shapes = [(2, 64, 64), (3, 72, 104), (1, 36, 52), (2, 128, 200), (5, 40, 296), (4, 256, 256), (1, 20, 28), (2, 516, 68)]
-    for dtype in ("bfloat16", "float16"):
+    for dtype in ("bfloat16", "float16", "float32"):
         for k, (n, H, W) in enumerate(shapes):
             grey, u8 = (k % 3 == 1), (k % 2 == 1)
             cfg = NetConfig(grey=grey, preprocessing=MOBILENET_LIKE) if u8 else NetConfig(grey=grey)

@@ -1,5 +1,6 @@
 // Handle lifecycle and error reporting of libubd_hip.so.
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 #include <thread>
@@ -48,6 +49,31 @@ extern "C" int ubd_host_memcpy_mt(void *dst, const void *src, size_t n, int thre
 }
 extern "C" const char *ubd_build_id(void) { return UBD_BUILD_ID; }   // sha256 over the kernel sources at build time (build.sh); bench.py compares it with the committed profiles' fingerprint
 
+// The UBD_* environment switches, read once, when ubd_create builds the handle: NAME=value stores `set` in the int field at `field`; any
+// other value is ignored.  What each field selects is written at the field (common.h).
+static const char ANY[] = "", NUMBER[] = "#";      // in place of a value: set to anything / a positive integer, which is stored itself
+struct env_switch { const char *name; size_t field; const char *value; int set; };
+#define SW(name, field, value, set) {name, offsetof(ubd_handle, field), value, set}
+static const env_switch ENV_SWITCHES[] = {
+    SW("UBD_DILCONV", use_wino, "direct", 0), SW("UBD_DILCONV", wino_x6, "direct", 0), SW("UBD_DILCONV", wino_x6, "wino32", 0),
+    SW("UBD_WINO6_LAYOUT", wino6_natural, "natural", 1),
+    SW("UBD_STEM", fuse_stem, "fused", 1), SW("UBD_STEM", fuse_force, "fused", 1),
+    SW("UBD_STEM", fuse_stem, "fused123", 2), SW("UBD_STEM", fuse_force, "fused123", 1),
+    SW("UBD_STEM", fuse_stem, "unfused", 0),
+    SW("UBD_TEST_NUM_CUS", num_cus, NUMBER, 0),
+    SW("UBD_DILBWD", split_dilbwd, "split", 1), SW("UBD_DILBWD", no_pair_dilbwd, "pair8", 1),
+    SW("UBD_SEPBWD", split_sepbwd32, "split", 1),
+    SW("UBD_STEM16", split_stem16, "split", 1), SW("UBD_STEM16", split_stem16, "fused12", 2),
+    SW("UBD_PP_GLOBAL", pp_global, ANY, 1), SW("UBD_PP_SPLIT", pp_split, ANY, 1), SW("UBD_PP_POISON", pp_poison, ANY, 1),
+    SW("UBD_PP_SERIAL_TAIL", pp_serial_tail, ANY, 1), SW("UBD_PP_THREADS_512", pp_threads_512, ANY, 1),
+    SW("UBD_HEADBWD", split_headbwd, "split", 1),
+    SW("UBD_SEPB16_X", sepb_x_regs, "regs", 1),
+    SW("UBD_REDUCE", chain_reduce, "batched", 0),
+    SW("UBD_LOSS", loss_chain, "chain", 1),
+    SW("UBD_DILCONV16", direct_dil16, "direct", 1),
+};
+#undef SW
+
 extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
 {
     UBD_REQUIRE(cfg && out, "ubd_create: null argument");
@@ -68,40 +94,16 @@ extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
     h->cfg = *cfg;
     h->k_out = 1 + cfg->n_classes;
     h->num_cus = prop.multiProcessorCount;
-    {
-        const char *e = getenv("UBD_DILCONV");
-        h->use_wino = !(e && strcmp(e, "direct") == 0);
-        h->wino_x6 = h->use_wino && !(e && strcmp(e, "wino32") == 0);
-        // UBD_WINO6_LAYOUT=natural: no phase-major activation layouts between the layers of the fp32 inference pass (the reference side
-        // of the bit-identity tests)
-        { const char *l = getenv("UBD_WINO6_LAYOUT"); h->wino6_natural = (l && strcmp(l, "natural") == 0) ? 1 : 0; }
-        // Inference runs L2 -> L3 as ONE kernel with L2's output in LDS (stem23.h) when the model uses the fml padding (the
-        // variant that inherits the 33rd L2 column from the tile to its left: 0.405 vs 0.417 ms per forward pass at
-        // 32 x 512 x 512); with TF 'same' padding the fused kernel only ties the two separate kernels and they
-        // stay the default.  UBD_STEM=fused / unfused overrides either way.  Training always runs the separate kernels.
-        const char *s = getenv("UBD_STEM");
-        h->fuse_stem = cfg->fml_compatible != 0 ? 2 : 0;        // 2: L1 -> L2 -> L3 in one kernel (stem123.h; fml padding only)
-        if (s && strcmp(s, "fused") == 0) { h->fuse_stem = 1; h->fuse_force = 1; }      // 1: L1, then L2 -> L3 fused (stem23.h)
-        if (s && strcmp(s, "fused123") == 0) { h->fuse_stem = 2; h->fuse_force = 1; }   // forced at any launch size (tests)
-        if (s && strcmp(s, "cold123") == 0 && cfg->fml_compatible != 0) { h->fuse_stem = 3; h->fuse_force = 1; }   // one kernel, one cold-started tile per work unit, at any launch size (tests; default for small launches)
-        if (s && strcmp(s, "unfused") == 0) h->fuse_stem = 0;
-        // test hooks: pretend the device has fewer CUs, so that every persistent kernel walks many tiles per block even on
-        // the small shapes the CPU oracle can check (tests/test_gpu_persistent.py; ubd_num_cus reports what was taken)
-        { const char *c = getenv("UBD_TEST_NUM_CUS"); if (c && atoi(c) > 0) h->num_cus = atoi(c); }
-        { const char *b = getenv("UBD_DILBWD"); h->split_dilbwd = (b && strcmp(b, "split") == 0) ? 1 : 0; h->no_pair_dilbwd = (b && strcmp(b, "pair8") == 0) ? 1 : 0; }
-        { const char *b = getenv("UBD_SEPBWD"); h->split_sepbwd32 = (b && strcmp(b, "split") == 0) ? 1 : 0; }
-        { const char *b = getenv("UBD_STEM16"); h->split_stem16 = (b && strcmp(b, "split") == 0) ? 1 : ((b && strcmp(b, "fused12") == 0) ? 2 : 0); }   // 0: L1 -> L2 -> L3 in one kernel, 2: L1 -> L2 fused + L3, 1: three kernels
-        // postprocess test hooks (multi-launch front end at any map size / separate tail launches / LDS poisoning + forest integrity
-        // check / one-lane box fit / the 512-thread block shape the job has inside the stem kernel)
-        h->pp_global = getenv("UBD_PP_GLOBAL") != nullptr; h->pp_split = getenv("UBD_PP_SPLIT") != nullptr;
-        h->pp_poison = getenv("UBD_PP_POISON") != nullptr; h->pp_serial_tail = getenv("UBD_PP_SERIAL_TAIL") != nullptr;
-        h->pp_threads_512 = getenv("UBD_PP_THREADS_512") != nullptr;
-        { const char *b = getenv("UBD_HEADBWD"); h->split_headbwd = (b && strcmp(b, "split") == 0) ? 1 : 0; }
-        { const char *b = getenv("UBD_SEPB16_X"); h->sepb_x_regs = (b && strcmp(b, "regs") == 0) ? 1 : 0; }
-        { const char *b = getenv("UBD_REDUCE"); h->chain_reduce = (b && strcmp(b, "batched") == 0) ? 0 : 1; }
-        { const char *b = getenv("UBD_LOSS"); h->loss_chain = (b && strcmp(b, "chain") == 0) ? 1 : 0; }
-        { const char *b = getenv("UBD_DILCONV16"); h->direct_dil16 = (b && strcmp(b, "direct") == 0) ? 1 : 0; }
+    h->use_wino = h->wino_x6 = h->chain_reduce = 1;             // the defaults that are not 0
+    h->fuse_stem = cfg->fml_compatible != 0 ? 2 : 0;
+    for (const env_switch &sw : ENV_SWITCHES) {
+        const char *e = getenv(sw.name);
+        if (!e) continue;
+        int *field = (int *)((char *)h + sw.field);
+        if (sw.value == NUMBER) { if (atoi(e) > 0) *field = atoi(e); }
+        else if (sw.value == ANY || strcmp(e, sw.value) == 0) *field = sw.set;
     }
+    { const char *s = getenv("UBD_STEM"); if (s && strcmp(s, "cold123") == 0 && cfg->fml_compatible != 0) { h->fuse_stem = 3; h->fuse_force = 1; } }      // fml padding only
     // Keras model.get_weights() order
     size_t off = 0;
     int cin = cfg->c_in;

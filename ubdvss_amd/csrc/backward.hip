@@ -14,6 +14,8 @@
 //   sep_dx       G_below = depthwise-transpose(dDW) * (X > 0)
 // Weight gradients: every block writes one row of a partial-sum matrix, reduce_partials_kernel adds the rows in a
 // fixed order into the flat gradient vector (Keras get_weights() order, same as the parameters).
+#include <algorithm>
+#include <type_traits>
 #include "common.h"
 #include "pack.h"
 
@@ -61,10 +63,6 @@ template <> __device__ __forceinline__ f32x4 mfma16<_Float16>(u32x4 a, u32x4 b, 
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-// gradient tensors between layers: bf16 for bf16 activations, fp32 otherwise (fp16 would underflow without loss scaling)
-template <typename TX> struct UBD_G16 { static constexpr bool value = false; };
-template <> struct UBD_G16<__bf16> { static constexpr bool value = true; };
-
 
 // ------------------------------------------------------------------------------------ backward weight fragments (pack.h)
 __global__ void pack_bwd_kernel(const float *__restrict__ params, float *__restrict__ out, pack_bwd_args a)
@@ -1273,10 +1271,12 @@ extern "C" size_t ubd_train_workspace_bytes(const ubd_handle *h, int n, int heig
     return T.total;
 }
 
+template <int V> using int_c = std::integral_constant<int, V>;      // a template argument chosen at run time: f(int_c<V>()) for a generic lambda f
+
 // UPS > 0: G is computed in the kernel from the layer above (G = this layer's output activation, the mask source; up_*: see the kernel)
 template <int CIN, int STRIDE, typename TX, typename TR = TX, int UPS = 0>
 static int launch_sep_bwd(const ubd_handle *h, const void *x, int in_u8, const float *G, float *dDW, const float *ffrag,
-                           const float *bfrag, float *g_dw, float *g_pw, float *g_b, rp_queue *rq, int n, int H, int W,
+                           const float *bfrag, float *grads, int s, rp_queue *rq, int n, int H, int W,
                            int OH, int OW, int pad_lo, float sub, float div, hipStream_t st,
                            const float *up_ddw = nullptr, const float *up_dw = nullptr, int up_oh = 0, int up_ow = 0, int up_pad = 0)
 {
@@ -1294,19 +1294,19 @@ static int launch_sep_bwd(const ubd_handle *h, const void *x, int in_u8, const f
     int grid = h->num_cus * (lds_bytes > 80 * 1024 ? 1 : (lds_bytes > 53 * 1024 ? 2 : (lds_bytes > 40 * 1024 || !(CIN != UBD_C && UPS > 0) ? 3 : 4)));   // 160 KB of LDS per CU
     if (grid > tiles) grid = (int)tiles;
     const int part = 9 * CIN + CIN * UBD_C + UBD_C;
-    float *partials = rp_add(rq, grid, part, g_dw, 9 * CIN, g_pw, CIN * UBD_C, g_b, st);
+    float *partials = rp_add(rq, grid, part, grads + h->off_sep_dw[s], 9 * CIN, grads + h->off_sep_pw[s], CIN * UBD_C, grads + h->off_sep_b[s], st);
     if (!partials) return -1;
-    if (in_u8)
-        hipLaunchKernelGGL((sep_bwd_kernel<CIN, STRIDE, 1, TX, TR, UPS>), dim3(grid), dim3(256), 0, st, x, G, dDW, ffrag, bfrag, partials, n, H, W, OH, OW, pad_lo, sub, div, up_ddw, up_dw, up_oh, up_ow, up_pad SB_STAMP_ARG);
-    else
-        hipLaunchKernelGGL((sep_bwd_kernel<CIN, STRIDE, 0, TX, TR, UPS>), dim3(grid), dim3(256), 0, st, x, G, dDW, ffrag, bfrag, partials, n, H, W, OH, OW, pad_lo, sub, div, up_ddw, up_dw, up_oh, up_ow, up_pad SB_STAMP_ARG);
+    auto launch = [&](auto u8) {
+        hipLaunchKernelGGL((sep_bwd_kernel<CIN, STRIDE, decltype(u8)::value, TX, TR, UPS>), dim3(grid), dim3(256), 0, st, x, G, dDW, ffrag, bfrag, partials, n, H, W, OH, OW, pad_lo, sub, div, up_ddw, up_dw, up_oh, up_ow, up_pad SB_STAMP_ARG);
+    };
+    in_u8 ? launch(int_c<1>()) : launch(int_c<0>());
     return 0;
 }
 
 template <int CIN, int STRIDE, int GSRC, typename T>
 static int launch_sepb16(const ubd_handle *h, const void *x, int in_u8, const unsigned short *D, const unsigned *mbits, unsigned *xbits,
-                          unsigned short *dDW, const float *dw_own, const float *pw_own, const float *dw_up, float *g_dw, float *g_pw,
-                          float *g_b, rp_queue *rq, int n, int H, int W, int OH, int OW, int pad_lo, int DH, int DWd, int pad_up,
+                          unsigned short *dDW, const float *dw_own, const float *pw_own, const float *dw_up, float *grads, int s,
+                          rp_queue *rq, int n, int H, int W, int OH, int OW, int pad_lo, int DH, int DWd, int pad_up,
                           float sub, float div, hipStream_t st)
 {
     using C = sepb16_cfg<CIN, STRIDE, GSRC>;
@@ -1320,59 +1320,68 @@ static int launch_sepb16(const ubd_handle *h, const void *x, int in_u8, const un
     int grid = h->num_cus * (xdma ? sepb16_cfg<CIN, STRIDE, GSRC, 1>::BLOCKS_PER_CU : C::BLOCKS_PER_CU);
     if (grid > tiles) grid = (int)tiles;
     const rp_job prev = h->chain_reduce ? rp_take_prev(rq) : rp_job{};
-    float *partials = rp_add(rq, grid, C::PART, g_dw, 9 * CIN, g_pw, CIN * UBD_C, g_b, st);
+    float *partials = rp_add(rq, grid, C::PART, grads + h->off_sep_dw[s], 9 * CIN, grads + h->off_sep_pw[s], CIN * UBD_C, grads + h->off_sep_b[s], st);
     if (!partials) return -1;
+    auto launch = [&](auto xb) {      // 0: fp32 input through registers, 1: uint8, 2: fp32 by LDS-DMA
+        hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, decltype(xb)::value, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev SB_STAMP_ARG);
+    };
     if constexpr (CIN != UBD_C) {
-        if (xdma) {
-            hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, 2, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev SB_STAMP_ARG);
-            return 0;
-        }
+        if (xdma) { launch(int_c<2>()); return 0; }
     }
-    if (in_u8)
-        hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, 1, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev SB_STAMP_ARG);
-    else
-        hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, 0, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev SB_STAMP_ARG);
+    in_u8 ? launch(int_c<1>()) : launch(int_c<0>());
     return 0;
 }
 
-template <typename TX>
+// Weight gradient of the head.  DXOUT (bf16 train step with classes): the head's data gradient as well, from the same pass over A9 --
+// g = (dlogits . hk^T) * (A9 > 0) in bf16 (head_wgrad_kernel<TX, true>)
+template <typename TX, bool DXOUT = false>
 static int launch_head_wgrad(const ubd_handle *h, const void *a9, const float *dlogits, float *grads, rp_queue *rq, long npix,
-                              hipStream_t st)
+                              hipStream_t st, const float *hk = nullptr, unsigned short *g = nullptr)
 {
-    if (h->k_out == 1) {
-        long g1 = (npix + 255) / 256;
-        if (g1 > h->num_cus * 4) g1 = h->num_cus * 4;
-        float *partials = rp_add(rq, (int)g1, UBD_C + 1, grads + h->off_head_k, UBD_C, grads + h->off_head_b, 1, nullptr, st);
+    if (!DXOUT && h->k_out == 1) {
+        const int g1 = (int)std::min<long>((npix + 255) / 256, h->num_cus * 4);
+        float *partials = rp_add(rq, g1, UBD_C + 1, grads + h->off_head_k, UBD_C, grads + h->off_head_b, 1, nullptr, st);
         if (!partials) return -1;
-        hipLaunchKernelGGL((head_wgrad1_kernel<TX>), dim3((int)g1), dim3(256), 0, st, a9, dlogits, partials, npix);
+        hipLaunchKernelGGL((head_wgrad1_kernel<TX>), dim3(g1), dim3(256), 0, st, a9, dlogits, partials, npix);
         return 0;
     }
-    long g2l = (npix + HW_TILE - 1) / HW_TILE;
-    if (g2l > h->num_cus * 4) g2l = h->num_cus * 4;
-    const int g2 = (int)g2l;
-    const int cols = (UBD_C + 1) * h->k_out;
-    float *partials = rp_add(rq, g2, cols, grads + h->off_head_k, UBD_C * h->k_out, grads + h->off_head_b, h->k_out, nullptr, st);
+    const int g2 = (int)std::min<long>((npix + HW_TILE - 1) / HW_TILE, h->num_cus * 4);
+    float *partials = rp_add(rq, g2, (UBD_C + 1) * h->k_out, grads + h->off_head_k, UBD_C * h->k_out, grads + h->off_head_b, h->k_out, nullptr, st);
     if (!partials) return -1;
-    hipLaunchKernelGGL((head_wgrad_kernel<TX>), dim3(g2), dim3(256), 0, st, a9, dlogits, partials, npix, h->k_out, (const float *)nullptr, (unsigned short *)nullptr);
-    return 0;
-}
-// bf16 train step with classes: weight gradient AND data gradient of the head in one pass over A9 (head_wgrad_kernel<TX, true>)
-template <typename TX>
-static int launch_head_bwd16(const ubd_handle *h, const void *a9, const float *dlogits, const float *hk, unsigned short *g, float *grads, rp_queue *rq,
-                             long npix, hipStream_t st)
-{
-    long g2l = (npix + HW_TILE - 1) / HW_TILE;
-    if (g2l > h->num_cus * 4) g2l = h->num_cus * 4;
-    const int g2 = (int)g2l;
-    const int cols = (UBD_C + 1) * h->k_out;
-    float *partials = rp_add(rq, g2, cols, grads + h->off_head_k, UBD_C * h->k_out, grads + h->off_head_b, h->k_out, nullptr, st);
-    if (!partials) return -1;
-    hipLaunchKernelGGL((head_wgrad_kernel<TX, true>), dim3(g2), dim3(256), 0, st, a9, dlogits, partials, npix, h->k_out, hk, g);
+    hipLaunchKernelGGL((head_wgrad_kernel<TX, DXOUT>), dim3(g2), dim3(256), 0, st, a9, dlogits, partials, npix, h->k_out, hk, g);
     return 0;
 }
 
-// Backward pass given the saved activations (element type TX): a1, a2 at half resolution, acts[0..6] = L3, L4..L9
-// outputs at quarter resolution; wfrag = forward fp32 fragments (depthwise / pointwise per-lane weights).
+// Weight gradient of a bf16 dilated layer and, with fuse_dx, its data gradient from the same staged tiles (bwd16.h).  tw: tile width;
+// pair: two 8-wide sub-grids side by side in one 16-wide tile (bwd16.h PAIR).  8-wide tiles take the M-split accumulators in both forms.
+template <typename TX>
+static void launch_dil_wgrad16(int gw, const void *X, const unsigned short *G, float *partials, int n, int H4, int W4, int dd,
+                               const unsigned *wt, unsigned short *g_out, const rp_job &prev, int tw, bool pair, bool fuse_dx, hipStream_t st)
+{
+    auto launch = [&](auto tw_c, auto dx_c, auto pair_c) {
+        constexpr int TW = decltype(tw_c)::value;
+        constexpr bool DX = decltype(dx_c)::value, PAIR = decltype(pair_c)::value;
+        hipLaunchKernelGGL((dil_wgrad16_kernel<TX, TW, DX, TW == 8, PAIR>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, G, partials, n, H4, W4, dd,
+                           DX ? (const u32x4 *)wt : nullptr, DX ? g_out : nullptr, prev, w16_geometry<TW, PAIR>(n, H4, W4, dd) WG_STAMP_ARG);
+    };
+    if (pair) launch(int_c<16>(), std::true_type(), std::true_type());
+    else if (tw == 8 && fuse_dx) launch(int_c<8>(), std::true_type(), std::false_type());
+    else if (tw == 8) launch(int_c<8>(), std::false_type(), std::false_type());
+    else if (fuse_dx) launch(int_c<16>(), std::true_type(), std::false_type());
+    else launch(int_c<16>(), std::false_type(), std::false_type());
+}
+
+// L1 reads the images, which have 1 or 3 channels: f gets the count as an int_c, so that a caller writes its launch once
+template <typename F> static int with_c_in(const ubd_handle *h, F f) { return h->cfg.c_in == 1 ? f(int_c<1>()) : f(int_c<3>()); }
+
+// what L1 does to a raw pixel before the first convolution: (x - sub) / div; u8: the images are uint8
+struct input_affine_t { float sub, div; int u8; };
+static input_affine_t input_affine(int preprocessing, int in_dtype)
+{
+    const bool mobilenet = preprocessing == UBD_PRE_MOBILENET;
+    return {mobilenet ? 127.5f : 0.f, mobilenet ? 127.5f : 1.f, in_dtype == UBD_IN_U8};
+}
+
 // One launch in front of the bf16 train step: the four weight packers (fp32 stem fragments, 16-bit dilated fragments, backward
 // fragments, transposed 16-bit fragments: 48 blocks each) + zero gradient vector + zero loss scratch -- they were four ~5-us
 // kernels and two memset kernels scattered over the step, each serialised behind its predecessor (rocprofv3: 29 us of a 1.22-ms step).
@@ -1400,198 +1409,194 @@ __global__ __launch_bounds__(256) void train_prologue16_kernel(const float *__re
     for (size_t i = gtid; i < a.loss_zero_words; i += gthreads) a.loss_zero[i] = 0u;
 }
 
-template <typename TX>
-static int backward_impl(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing, int n, int H,
-                         int W, const void *a1, const void *a2, const void *const *acts, const float *wfrag, float *dlogits,
-                         float *grads, char *ws, const train_layout &T, hipStream_t st, bool prepacked = false)
+// the part of the packers' arguments that comes from the handle (parameter offsets and counts); the buffers are the caller's
+static train_prologue_args fill_pack_args(const ubd_handle *h)
 {
-    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
-    const int act_dtype = h->cfg.dtype;
-    float *bfrag = (float *)(ws + T.off_bfrag);
-    const int per_sep = UBD_SEP_FRAG_FLOATS + UBD_SEP_DW_FLOATS;
+    train_prologue_args a = {};
+    for (int s = 0; s < 3; ++s) { a.pa.off_sep_dw[s] = h->off_sep_dw[s]; a.pa.off_sep_pw[s] = h->off_sep_pw[s]; a.pb.off_sep_pw[s] = h->off_sep_pw[s]; }
+    for (int k = 0; k < UBD_NUM_DIL; ++k) { a.pa.off_dil_k[k] = h->off_dil_k[k]; a.pb.off_dil_k[k] = h->off_dil_k[k]; }
+    a.pa.c_in = a.pb.c_in = h->cfg.c_in;
+    a.ps = ubd_pack_sep16_args(h);
+    a.off0 = h->off_dil_k[0]; a.layer_stride = h->off_dil_k[1] - h->off_dil_k[0];
+    a.n_params = h->n_params;
+    return a;
+}
+
+// end of either pass: the partial sums still queued, launch errors, the rest of the overlapped all-reduce
+static int finish_step(ubd_handle *h, rp_queue *rq, float *grads, hipStream_t st)
+{
+    rp_flush(rq, st);
+    UBD_CHECK_HIP(hipGetLastError());
+    return ubd_comm_fused(h) ? ubd_comm_finish(h, grads, st) : 0;
+}
+
+namespace {
+// A train step's backward pass.  Its data: the step's arguments, the loss gradient, the carved workspace, and what the forward pass
+// kept -- a1, a2 at half resolution and acts[0..6] = the outputs of L3, L4..L9 at quarter resolution, in the handle's dtype, and its
+// fp32 fragments wfrag (depthwise / pointwise per-lane weights).  One of backward_f32<TX> / backward_bf16 runs it.
+struct bwd_pass {
+    ubd_handle *h; const float *params; const void *images; int in_dtype, preprocessing, n, H, W;
+    float *dlogits, *grads; char *ws; const train_layout &T; hipStream_t st;
+    const void *a1, *a2, *acts[7]; const float *wfrag;      // filled in after the forward pass
+    template <typename TX> int backward_f32();
+    template <typename TX> int sep_backward_f32(const float *G3, rp_queue *rq);
+    int backward_bf16();
+};
+
+// fp32 gradient tensors between the layers: fp32 and fp16 activations (16-bit gradient tensors would underflow in fp16 without loss
+// scaling).  Head and dilated layers here, the separable layers in sep_backward_f32.
+template <typename TX>
+int bwd_pass::backward_f32()
+{
+    const int H4 = H / 4, W4 = W / 4;
     const long npix = (long)n * H4 * W4;
-    if (!prepacked) {                                          // (the bf16 step's prologue kernel has zeroed and packed everything)
-        UBD_CHECK_HIP(hipMemsetAsync(grads, 0, h->n_params * sizeof(float), st));
-        pack_bwd_args pa;
-        for (int s = 0; s < 3; ++s) pa.off_sep_pw[s] = h->off_sep_pw[s];
-        for (int k = 0; k < UBD_NUM_DIL; ++k) pa.off_dil_k[k] = h->off_dil_k[k];
-        pa.c_in = h->cfg.c_in;
-        hipLaunchKernelGGL(pack_bwd_kernel, dim3(64), dim3(256), 0, st, params, bfrag, pa);
-        if (h->use_wino && !(sizeof(TX) == 2 && UBD_G16<TX>::value)) ubd_launch_pack_wino(h, params, bfrag + UBD_BWD_DIRECT_FLOATS, 1, st);
-    }
+    float *bfrag = (float *)(ws + T.off_bfrag);
+    UBD_CHECK_HIP(hipMemsetAsync(grads, 0, h->n_params * sizeof(float), st));
+    hipLaunchKernelGGL(pack_bwd_kernel, dim3(64), dim3(256), 0, st, params, bfrag, fill_pack_args(h).pb);
+    if (h->use_wino) ubd_launch_pack_wino(h, params, bfrag + UBD_BWD_DIRECT_FLOATS, 1, st);
 
     float *gq[2] = {(float *)(ws + T.off_gq[0]), (float *)(ws + T.off_gq[1])};
-    float *ddw3 = (float *)(ws + T.off_ddw3);
-    float *gb[2] = {(float *)(ws + T.off_gb[0]), (float *)(ws + T.off_gb[1])};
     rp_queue rq;
     rp_init(&rq, (float *)(ws + T.off_partials), T.partials_floats);
-
-    int grid = (int)((npix + 255) / 256);
-    if (grid > h->num_cus * 8) grid = h->num_cus * 8;
+    const int grid = (int)std::min<long>((npix + 255) / 256, h->num_cus * 8);
     int cur = 0;
-    if constexpr (sizeof(TX) == 2 && UBD_G16<TX>::value) {
-        // ---- bf16 gradient tensors (bwd16.h): G9..G3 live in the two halves of gq[0]; G3 is widened into gq[1] for the
-        //      separable backward kernels; the transposed 16-bit fragments reuse the Winograd part of bfrag
-        unsigned short *g16[2] = {(unsigned short *)gq[0], (unsigned short *)gq[0] + (size_t)npix * UBD_C};
-        unsigned *frag16t = (unsigned *)(bfrag + UBD_BWD_DIRECT_FLOATS);
-        if (!prepacked) ubd_launch_pack16(h, params, frag16t, 1, st);
-        if (h->k_out == 1) {                                   // one pass over A9 for both head gradients
-            int g1 = (int)((npix * 3 + 255) / 256);
-            if (g1 > h->num_cus * 6) g1 = h->num_cus * 6;
-            g1 = (g1 + 2) / 3 * 3;                             // 256 g1 = 0 (mod 3): a thread keeps its channel group
-            float *partials = rp_add(&rq, g1, UBD_C + 1, grads + h->off_head_k, UBD_C, grads + h->off_head_b, 1, nullptr, st);
-            if (!partials) return -1;
-            hipLaunchKernelGGL((head_bwd1_16_kernel<TX>), dim3(g1), dim3(256), 0, st, dlogits, (const unsigned short *)acts[6], params + h->off_head_k, g16[0], partials, npix);
-        } else if (h->split_headbwd) {                        // UBD_HEADBWD=split: the two kernels (diagnostics / tests)
-            hipLaunchKernelGGL((head_dx16_kernel<TX>), dim3(grid), dim3(256), 0, st, dlogits, (const unsigned short *)acts[6], params + h->off_head_k, g16[0], npix, h->k_out);
-            if (launch_head_wgrad<TX>(h, acts[6], dlogits, grads, &rq, npix, st)) return -1;
-        } else {
-            if (launch_head_bwd16<TX>(h, acts[6], dlogits, params + h->off_head_k, g16[0], grads, &rq, npix, st)) return -1;
-        }
-        for (int k = UBD_NUM_DIL - 1; k >= 0; --k) {
-            const void *X = acts[k];
-            const int dd = UBD_DILATIONS[k];
-            const int sw = (W4 + dd - 1) / dd, tw = sw <= 8 ? 8 : 16;              // narrow sub-grids: 8-wide tiles
-            // sub-grids exactly 8 columns wide and at most 8 rows high (dilation 16 on 128 x 128 maps): two of them side by side in one 16-wide tile
-            // (bwd16.h PAIR; UBD_DILBWD=pair8 keeps the 8-wide form)
-            const bool pair = !h->split_dilbwd && !h->no_pair_dilbwd && tw == 8 && sw == 8 && (dd & 1) == 0 && W4 % dd == 0 && (H4 + dd - 1) / dd <= 8;
-            const long items = pair ? (long)n * dd * (dd / 2)
-                                    : (long)n * dd * dd * (((H4 + dd - 1) / dd + W16_TH(tw) - 1) / W16_TH(tw)) * ((sw + tw - 1) / tw);
-            int gw = h->num_cus * ((tw == 8 && !pair) ? 3 : 2);     // 16 x 16 tiles: two blocks per CU (LDS, registers); 8-wide tiles: three; the same grid in the split mode (same order of the partial sums)
-            if (gw > items) gw = (int)items;
-            gw = (gw + 7) / 8 * 8;                                  // the item ranges are cut per XCD: all eight need a block
-            const rp_job prev = h->chain_reduce ? rp_take_prev(&rq) : rp_job{};   // the head's / the layer above's partial rows: totalled at the end of this kernel
-            float *partials = rp_add(&rq, gw, 217 * UBD_C, grads + h->off_dil_k[k], 216 * UBD_C, grads + h->off_dil_b[k], UBD_C, nullptr, st);
-            if (!partials) return -1;
-            // weight gradient AND data gradient of the layer from the same staged tiles (bwd16.h); UBD_DILBWD=split (a diagnostic / test
-            // switch) keeps the separate data-gradient kernel
-            const unsigned *wt = frag16t + (size_t)k * UBD_DIL16_FRAG_U32;
-            const bool fuse_dx = !h->split_dilbwd;                 // 8-wide tiles (dilation 16 on 128-wide maps) too since round 4: the fused form with M-split accumulators     // 8-wide tiles (dilation 16 on 128-wide maps): fused 75 us vs 38 + 33 us apart (two blocks per CU instead of three)
-            if (pair)
-                hipLaunchKernelGGL((dil_wgrad16_kernel<TX, 16, true, false, true>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, g16[cur], partials, n, H4, W4, dd, (const u32x4 *)wt, g16[cur ^ 1], prev, w16_geometry<16, true>(n, H4, W4, dd) WG_STAMP_ARG);
-            else if (tw == 8 && fuse_dx)
-                hipLaunchKernelGGL((dil_wgrad16_kernel<TX, 8, true>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, g16[cur], partials, n, H4, W4, dd, (const u32x4 *)wt, g16[cur ^ 1], prev, w16_geometry<8, false>(n, H4, W4, dd) WG_STAMP_ARG);
-            else if (tw == 8)
-                hipLaunchKernelGGL((dil_wgrad16_kernel<TX, 8, false>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, g16[cur], partials, n, H4, W4, dd, (const u32x4 *)nullptr, (unsigned short *)nullptr, prev, w16_geometry<8, false>(n, H4, W4, dd) WG_STAMP_ARG);
-            else if (fuse_dx)
-                hipLaunchKernelGGL((dil_wgrad16_kernel<TX, 16, true>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, g16[cur], partials, n, H4, W4, dd, (const u32x4 *)wt, g16[cur ^ 1], prev, w16_geometry<16, false>(n, H4, W4, dd) WG_STAMP_ARG);
-            else
-                hipLaunchKernelGGL((dil_wgrad16_kernel<TX, 16, false>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, g16[cur], partials, n, H4, W4, dd, (const u32x4 *)nullptr, (unsigned short *)nullptr, prev, w16_geometry<16, false>(n, H4, W4, dd) WG_STAMP_ARG);
-            if (!fuse_dx) ubd_launch_dilconv16(h, 1, wt, nullptr, X, dd, g16[cur], g16[cur ^ 1], n, H4, W4, st);
-            cur ^= 1;
-        }
-        // chained reduction: the first dilated layer's rows are totalled at the end of L3's kernel below, so the dilated + head segment
-        // is final (and its all-reduce may start) one kernel later than with the stand-alone reduction
-        if (!h->chain_reduce) {
-            rp_flush(&rq, st);
-            if (ubd_comm_fused(h)) { const int rc = ubd_comm_begin_tail(h, grads, st); if (rc) return rc; }   // dilated + head gradients are final
-        }
-        // separable layers: G1 / G2 are built tile-wise in LDS from the bf16 dDW tensor of the layer above (sepbwd16.h)
-        const int pad2 = h->cfg.fml_compatible ? 1 : 0;
-        const float *dw0 = params + h->off_sep_dw[0], *dw1 = params + h->off_sep_dw[1], *dw2 = params + h->off_sep_dw[2];
-        const float *pw0 = params + h->off_sep_pw[0], *pw1 = params + h->off_sep_pw[1], *pw2 = params + h->off_sep_pw[2];
-        unsigned short *ddw3 = (unsigned short *)(ws + T.off_ddw3), *ddw2 = (unsigned short *)(ws + T.off_gb[0]);
-        // ReLU bits of a2 and a1 (one word per pixel, sepbwd16.h): written by the kernel that reads the activation as its input, read by the next one
-        unsigned *bits2 = (unsigned *)(ws + T.off_gb[1]), *bits1 = bits2 + ubd_align_up((size_t)n * H2 * W2, 64);
-        if (launch_sepb16<UBD_C, 2, 0, TX>(h, a2, 0, g16[cur], nullptr, bits2, ddw3, dw2, pw2, dw2, grads + h->off_sep_dw[2], grads + h->off_sep_pw[2],
-                                       grads + h->off_sep_b[2], &rq, n, H2, W2, H4, W4, pad2, H4, W4, 0, 0.f, 1.f, st)) return -1;
-        if (h->chain_reduce && ubd_comm_fused(h)) { const int rc = ubd_comm_begin_tail(h, grads, st); if (rc) return rc; }   // dilated + head gradients are final
-        if (launch_sepb16<UBD_C, 1, 2, TX>(h, a1, 0, ddw3, bits2, bits1, ddw2, dw1, pw1, dw2, grads + h->off_sep_dw[1], grads + h->off_sep_pw[1],
-                                       grads + h->off_sep_b[1], &rq, n, H2, W2, H2, W2, 1, H4, W4, pad2, 0.f, 1.f, st)) return -1;
-        float sub = 0.f, div = 1.f;
-        if (preprocessing == UBD_PRE_MOBILENET) { sub = 127.5f; div = 127.5f; }
-        const int u8 = in_dtype == UBD_IN_U8;
-        int rc1;
-        if (h->cfg.c_in == 1)
-            rc1 = launch_sepb16<1, 2, 1, TX>(h, images, u8, ddw2, bits1, nullptr, nullptr, dw0, pw0, dw1, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0],
-                                             grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad2, H2, W2, 1, sub, div, st);
-        else
-            rc1 = launch_sepb16<3, 2, 1, TX>(h, images, u8, ddw2, bits1, nullptr, nullptr, dw0, pw0, dw1, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0],
-                                             grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad2, H2, W2, 1, sub, div, st);
-        if (rc1) return -1;
-        rp_flush(&rq, st);
-        UBD_CHECK_HIP(hipGetLastError());
-        if (ubd_comm_fused(h)) return ubd_comm_finish(h, grads, st);
-        return 0;
-    } else {
     // head
     hipLaunchKernelGGL((head_dx_kernel<TX>), dim3(grid), dim3(256), 0, st, dlogits, acts[6], params + h->off_head_k, gq[0], npix, h->k_out);
     if (launch_head_wgrad<TX>(h, acts[6], dlogits, grads, &rq, npix, st)) return -1;
     // dilated layers, top to bottom
     for (int k = UBD_NUM_DIL - 1; k >= 0; --k) {
         const void *X = acts[k];                                // input of dilated layer k (= output of the layer below)
-        {
-            const int dd = UBD_DILATIONS[k];
-            const long items = (long)n * dd * dd * (((H4 + dd - 1) / dd + WG_TH - 1) / WG_TH) * (((W4 + dd - 1) / dd + WG_TW - 1) / WG_TW);
-            int gw = h->num_cus * 2;
-            if (gw > items) gw = (int)items;
-            gw = (gw + 7) / 8 * 8;                                  // the item ranges are cut per XCD: all eight need a block
-            float *partials = rp_add(&rq, gw, 217 * UBD_C, grads + h->off_dil_k[k], 216 * UBD_C, grads + h->off_dil_b[k], UBD_C, nullptr, st);
-            if (!partials) return -1;
-            if constexpr (sizeof(TX) == 4) {
-                if (h->split_sepbwd32) hipLaunchKernelGGL((dil_wgrad_kernel<TX>), dim3(gw), dim3(256), 0, st, X, gq[cur], partials, n, H4, W4, dd);     // diagnostics: the four-wave form
-                else hipLaunchKernelGGL((dil_wgrad_kernel<TX, 2>), dim3(gw), dim3(512), 0, st, X, gq[cur], partials, n, H4, W4, dd);
-            } else
-                hipLaunchKernelGGL((dil_wgrad_kernel<TX>), dim3(gw), dim3(256), 0, st, X, gq[cur], partials, n, H4, W4, dd);
-        }
+        const int dd = UBD_DILATIONS[k];
+        const long items = (long)n * dd * dd * (((H4 + dd - 1) / dd + WG_TH - 1) / WG_TH) * (((W4 + dd - 1) / dd + WG_TW - 1) / WG_TW);
+        int gw = (int)std::min<long>(items, h->num_cus * 2);
+        gw = (gw + 7) / 8 * 8;                                  // the item ranges are cut per XCD: all eight need a block
+        float *partials = rp_add(&rq, gw, 217 * UBD_C, grads + h->off_dil_k[k], 216 * UBD_C, grads + h->off_dil_b[k], UBD_C, nullptr, st);
+        if (!partials) return -1;
+        if constexpr (sizeof(TX) == 4) {
+            if (h->split_sepbwd32) hipLaunchKernelGGL((dil_wgrad_kernel<TX>), dim3(gw), dim3(256), 0, st, X, gq[cur], partials, n, H4, W4, dd);     // diagnostics: the four-wave form
+            else hipLaunchKernelGGL((dil_wgrad_kernel<TX, 2>), dim3(gw), dim3(512), 0, st, X, gq[cur], partials, n, H4, W4, dd);
+        } else
+            hipLaunchKernelGGL((dil_wgrad_kernel<TX>), dim3(gw), dim3(256), 0, st, X, gq[cur], partials, n, H4, W4, dd);
         if (h->use_wino)
-            ubd_launch_dilconv_wino(h, 1, bfrag + UBD_BWD_DIRECT_FLOATS + (size_t)k * UBD_WINO_FRAG_FLOATS, X, act_dtype, UBD_DILATIONS[k], gq[cur], gq[cur ^ 1], n, H4, W4, st);
+            ubd_launch_dilconv_wino(h, 1, bfrag + UBD_BWD_DIRECT_FLOATS + (size_t)k * UBD_WINO_FRAG_FLOATS, X, h->cfg.dtype, dd, gq[cur], gq[cur ^ 1], n, H4, W4, st);
         else
-            ubd_launch_dilconv(h, 1, bfrag + (size_t)k * UBD_DIL_FRAG_FLOATS, (const float *)X, UBD_DILATIONS[k], gq[cur], gq[cur ^ 1], n, H4, W4, st);
+            ubd_launch_dilconv(h, 1, bfrag + (size_t)k * UBD_DIL_FRAG_FLOATS, (const float *)X, dd, gq[cur], gq[cur ^ 1], n, H4, W4, st);
         cur ^= 1;
-    }
     }
     rp_flush(&rq, st);
     if (ubd_comm_fused(h)) { const int rc = ubd_comm_begin_tail(h, grads, st); if (rc) return rc; }       // dilated + head gradients are final
-    // separable layers
+    return sep_backward_f32<TX>(gq[cur], &rq);
+}
+
+// separable layers L3, L2, L1 of that pass; G3: the gradient at L3's output
+template <typename TX>
+int bwd_pass::sep_backward_f32(const float *G3, rp_queue *rq)
+{
+    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+    float *ddw3 = (float *)(ws + T.off_ddw3), *gb[2] = {(float *)(ws + T.off_gb[0]), (float *)(ws + T.off_gb[1])};
     const int pad_s2 = h->cfg.fml_compatible ? 1 : 0;
+    const int per_sep = UBD_SEP_FRAG_FLOATS + UBD_SEP_DW_FLOATS;
     const float *sf0 = wfrag, *sf1 = wfrag + per_sep, *sf2 = wfrag + 2 * per_sep;
-    const float *bs0 = bfrag + UBD_BWD_DGRAD_FLOATS, *bs1 = bs0 + UBD_BWD_SEP_FLOATS, *bs2 = bs1 + UBD_BWD_SEP_FLOATS;
-    // L3: input a2 (H2 x W2), output H4 x W4, G = gq[cur]
-    if (launch_sep_bwd<UBD_C, 2, TX>(h, a2, 0, gq[cur], ddw3, sf2, bs2, grads + h->off_sep_dw[2], grads + h->off_sep_pw[2], grads + h->off_sep_b[2], &rq, n, H2, W2, H4, W4, pad_s2, 0.f, 1.f, st)) return -1;
-    float sub = 0.f, div = 1.f;
-    if (preprocessing == UBD_PRE_MOBILENET) { sub = 127.5f; div = 127.5f; }
-    const int u8 = in_dtype == UBD_IN_U8;
-    int rc1;
+    const float *bs0 = (const float *)(ws + T.off_bfrag) + UBD_BWD_DGRAD_FLOATS, *bs1 = bs0 + UBD_BWD_SEP_FLOATS, *bs2 = bs1 + UBD_BWD_SEP_FLOATS;
+    const input_affine_t in = input_affine(preprocessing, in_dtype);
+    // L3: input a2 (H2 x W2), output H4 x W4
+    if (launch_sep_bwd<UBD_C, 2, TX>(h, a2, 0, G3, ddw3, sf2, bs2, grads, 2, rq, n, H2, W2, H4, W4, pad_s2, 0.f, 1.f, st)) return -1;
     if constexpr (sizeof(TX) == 4) {
-        // fp32 activations (round 5): L2's and L1's kernels build their G tiles themselves from the dDW tensor of the layer above and
-        // their own output activation (the ReLU mask) -- no sep_dx launches, no G tensors (UBD_SEPBWD=split keeps the two-kernel form)
+        // fp32 activations: L2's and L1's kernels build their G tiles themselves from the dDW tensor of the layer above and their own
+        // output activation (the ReLU mask) -- no sep_dx launches, no G tensors (UBD_SEPBWD=split keeps the two-kernel form)
         if (!h->split_sepbwd32) {
             const float *dwk2 = params + h->off_sep_dw[2], *dwk1 = params + h->off_sep_dw[1];
-            if (launch_sep_bwd<UBD_C, 1, TX, TX, 2>(h, a1, 0, (const float *)a2, gb[1], sf1, bs1, grads + h->off_sep_dw[1], grads + h->off_sep_pw[1], grads + h->off_sep_b[1], &rq, n, H2, W2, H2, W2, 1, 0.f, 1.f, st,
+            if (launch_sep_bwd<UBD_C, 1, TX, TX, 2>(h, a1, 0, (const float *)a2, gb[1], sf1, bs1, grads, 1, rq, n, H2, W2, H2, W2, 1, 0.f, 1.f, st,
                                                     ddw3, dwk2, H4, W4, pad_s2)) return -1;
-            if (h->cfg.c_in == 1)
-                rc1 = launch_sep_bwd<1, 2, float, TX, 1>(h, images, u8, (const float *)a1, nullptr, sf0, bs0, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0], grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad_s2, sub, div, st,
-                                                         gb[1], dwk1, H2, W2, 1);
-            else
-                rc1 = launch_sep_bwd<3, 2, float, TX, 1>(h, images, u8, (const float *)a1, nullptr, sf0, bs0, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0], grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad_s2, sub, div, st,
-                                                         gb[1], dwk1, H2, W2, 1);
-            if (rc1) return -1;
-            rp_flush(&rq, st);
-            UBD_CHECK_HIP(hipGetLastError());
-            if (ubd_comm_fused(h)) return ubd_comm_finish(h, grads, st);
-            return 0;
+            if (with_c_in(h, [&](auto c) {
+                    return launch_sep_bwd<decltype(c)::value, 2, float, TX, 1>(h, images, in.u8, (const float *)a1, nullptr, sf0, bs0, grads, 0, rq, n, H, W, H2, W2,
+                                                                                pad_s2, in.sub, in.div, st, gb[1], dwk1, H2, W2, 1);
+                })) return -1;
+            return finish_step(h, rq, grads, st);
         }
     }
-    {
-        const long tiles = (long)n * H2 * ((W2 + 15) / 16);
-        const int g3 = ubd_grid_for(tiles, h->num_cus, 4, 8);
-        hipLaunchKernelGGL((sep_dx_kernel<2, TX>), dim3(g3), dim3(256), 0, st, ddw3, a2, gb[0], sf2, n, H2, W2, H4, W4, pad_s2);
-        // L2: input a1, output H2 x W2, G = gb[0]
-        if (launch_sep_bwd<UBD_C, 1, TX>(h, a1, 0, gb[0], gb[1], sf1, bs1, grads + h->off_sep_dw[1], grads + h->off_sep_pw[1], grads + h->off_sep_b[1], &rq, n, H2, W2, H2, W2, 1, 0.f, 1.f, st)) return -1;
-        hipLaunchKernelGGL((sep_dx_kernel<1, TX>), dim3(g3), dim3(256), 0, st, gb[1], a1, gb[0], sf1, n, H2, W2, H2, W2, 1);
-    }
+    const int g3 = ubd_grid_for((long)n * H2 * ((W2 + 15) / 16), h->num_cus, 4, 8);
+    hipLaunchKernelGGL((sep_dx_kernel<2, TX>), dim3(g3), dim3(256), 0, st, ddw3, a2, gb[0], sf2, n, H2, W2, H4, W4, pad_s2);
+    // L2: input a1, output H2 x W2, G = gb[0]
+    if (launch_sep_bwd<UBD_C, 1, TX>(h, a1, 0, gb[0], gb[1], sf1, bs1, grads, 1, rq, n, H2, W2, H2, W2, 1, 0.f, 1.f, st)) return -1;
+    hipLaunchKernelGGL((sep_dx_kernel<1, TX>), dim3(g3), dim3(256), 0, st, gb[1], a1, gb[0], sf1, n, H2, W2, H2, W2, 1);
     // L1: input = images (fp32 / uint8), no data gradient
-    if (h->cfg.c_in == 1)
-        rc1 = launch_sep_bwd<1, 2, float, TX>(h, images, u8, gb[0], nullptr, sf0, bs0, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0], grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad_s2, sub, div, st);
-    else
-        rc1 = launch_sep_bwd<3, 2, float, TX>(h, images, u8, gb[0], nullptr, sf0, bs0, grads + h->off_sep_dw[0], grads + h->off_sep_pw[0], grads + h->off_sep_b[0], &rq, n, H, W, H2, W2, pad_s2, sub, div, st);
-    if (rc1) return -1;
-    rp_flush(&rq, st);
-    UBD_CHECK_HIP(hipGetLastError());
-    if (ubd_comm_fused(h)) return ubd_comm_finish(h, grads, st);
-    return 0;
+    if (with_c_in(h, [&](auto c) {
+            return launch_sep_bwd<decltype(c)::value, 2, float, TX>(h, images, in.u8, gb[0], nullptr, sf0, bs0, grads, 0, rq, n, H, W, H2, W2, pad_s2, in.sub, in.div, st);
+        })) return -1;
+    return finish_step(h, rq, grads, st);
 }
+// Never called (the bf16 step is backward_bf16): the library has always carried the ten bf16 instantiations of sep_bwd_kernel and
+// sep_dx_kernel, and this keeps its set of kernels what it was.
+template int bwd_pass::sep_backward_f32<__bf16>(const float *, rp_queue *);
+
+// The bf16 step, with bf16 gradient tensors (bwd16.h, sepbwd16.h): G9..G3 live in the two halves of gq[0].  The step's prologue kernel
+// has zeroed the gradient vector and packed every fragment; the transposed 16-bit fragments take the Winograd part of bfrag.
+int bwd_pass::backward_bf16()
+{
+    using TX = __bf16;
+    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+    const long npix = (long)n * H4 * W4;
+    const unsigned *frag16t = (const unsigned *)((const float *)(ws + T.off_bfrag) + UBD_BWD_DIRECT_FLOATS);
+    unsigned short *g16[2] = {(unsigned short *)(ws + T.off_gq[0]), (unsigned short *)(ws + T.off_gq[0]) + (size_t)npix * UBD_C};
+    const unsigned short *a9 = (const unsigned short *)acts[6];
+    rp_queue rq;
+    rp_init(&rq, (float *)(ws + T.off_partials), T.partials_floats);
+    int cur = 0;
+    if (h->k_out == 1) {                                       // one pass over A9 for both head gradients
+        int g1 = (int)std::min<long>((npix * 3 + 255) / 256, h->num_cus * 6);
+        g1 = (g1 + 2) / 3 * 3;                                 // 256 g1 = 0 (mod 3): a thread keeps its channel group
+        float *partials = rp_add(&rq, g1, UBD_C + 1, grads + h->off_head_k, UBD_C, grads + h->off_head_b, 1, nullptr, st);
+        if (!partials) return -1;
+        hipLaunchKernelGGL((head_bwd1_16_kernel<TX>), dim3(g1), dim3(256), 0, st, dlogits, a9, params + h->off_head_k, g16[0], partials, npix);
+    } else if (h->split_headbwd) {                            // UBD_HEADBWD=split: the two kernels
+        const int grid = (int)std::min<long>((npix + 255) / 256, h->num_cus * 8);
+        hipLaunchKernelGGL((head_dx16_kernel<TX>), dim3(grid), dim3(256), 0, st, dlogits, a9, params + h->off_head_k, g16[0], npix, h->k_out);
+        if (launch_head_wgrad<TX>(h, a9, dlogits, grads, &rq, npix, st)) return -1;
+    } else if (launch_head_wgrad<TX, true>(h, a9, dlogits, grads, &rq, npix, st, params + h->off_head_k, g16[0])) return -1;
+    for (int k = UBD_NUM_DIL - 1; k >= 0; --k) {
+        const void *X = acts[k];
+        const int dd = UBD_DILATIONS[k];
+        const int sw = (W4 + dd - 1) / dd, tw = sw <= 8 ? 8 : 16;              // narrow sub-grids: 8-wide tiles
+        // sub-grids exactly 8 columns wide and at most 8 rows high (dilation 16 on 128 x 128 maps): two of them side by side in one 16-wide tile
+        // (UBD_DILBWD=pair8 keeps the 8-wide form)
+        const bool pair = !h->split_dilbwd && !h->no_pair_dilbwd && tw == 8 && sw == 8 && (dd & 1) == 0 && W4 % dd == 0 && (H4 + dd - 1) / dd <= 8;
+        const long items = pair ? (long)n * dd * (dd / 2)
+                                : (long)n * dd * dd * (((H4 + dd - 1) / dd + W16_TH(tw) - 1) / W16_TH(tw)) * ((sw + tw - 1) / tw);
+        int gw = (int)std::min<long>(items, h->num_cus * ((tw == 8 && !pair) ? 3 : 2));     // 16 x 16 tiles: two blocks per CU (LDS, registers); 8-wide tiles: three; the same grid in the split mode (same order of the partial sums)
+        gw = (gw + 7) / 8 * 8;                                  // the item ranges are cut per XCD: all eight need a block
+        const rp_job prev = h->chain_reduce ? rp_take_prev(&rq) : rp_job{};   // the head's / the layer above's partial rows: totalled at the end of this kernel
+        float *partials = rp_add(&rq, gw, 217 * UBD_C, grads + h->off_dil_k[k], 216 * UBD_C, grads + h->off_dil_b[k], UBD_C, nullptr, st);
+        if (!partials) return -1;
+        const unsigned *wt = frag16t + (size_t)k * UBD_DIL16_FRAG_U32;
+        const bool fuse_dx = !h->split_dilbwd;                  // UBD_DILBWD=split keeps the separate data-gradient kernel
+        launch_dil_wgrad16<TX>(gw, X, g16[cur], partials, n, H4, W4, dd, wt, g16[cur ^ 1], prev, tw, pair, fuse_dx, st);
+        if (!fuse_dx) ubd_launch_dilconv16(h, 1, wt, nullptr, X, dd, g16[cur], g16[cur ^ 1], n, H4, W4, st);
+        cur ^= 1;
+    }
+    // chained reduction: the first dilated layer's rows are totalled at the end of L3's kernel below, so the dilated + head segment
+    // is final (and its all-reduce may start) one kernel later than with the stand-alone reduction
+    if (!h->chain_reduce) {
+        rp_flush(&rq, st);
+        if (ubd_comm_fused(h)) { const int rc = ubd_comm_begin_tail(h, grads, st); if (rc) return rc; }   // dilated + head gradients are final
+    }
+    // separable layers: G1 / G2 are built tile-wise in LDS from the bf16 dDW tensor of the layer above (sepbwd16.h)
+    const int pad2 = h->cfg.fml_compatible ? 1 : 0;
+    const float *dw0 = params + h->off_sep_dw[0], *dw1 = params + h->off_sep_dw[1], *dw2 = params + h->off_sep_dw[2];
+    const float *pw0 = params + h->off_sep_pw[0], *pw1 = params + h->off_sep_pw[1], *pw2 = params + h->off_sep_pw[2];
+    unsigned short *ddw3 = (unsigned short *)(ws + T.off_ddw3), *ddw2 = (unsigned short *)(ws + T.off_gb[0]);
+    // ReLU bits of a2 and a1 (one word per pixel, sepbwd16.h): written by the kernel that reads the activation as its input, read by the next one
+    unsigned *bits2 = (unsigned *)(ws + T.off_gb[1]), *bits1 = bits2 + ubd_align_up((size_t)n * H2 * W2, 64);
+    if (launch_sepb16<UBD_C, 2, 0, TX>(h, a2, 0, g16[cur], nullptr, bits2, ddw3, dw2, pw2, dw2, grads, 2, &rq, n, H2, W2, H4, W4, pad2, H4, W4, 0, 0.f, 1.f, st)) return -1;
+    if (h->chain_reduce && ubd_comm_fused(h)) { const int rc = ubd_comm_begin_tail(h, grads, st); if (rc) return rc; }   // dilated + head gradients are final
+    if (launch_sepb16<UBD_C, 1, 2, TX>(h, a1, 0, ddw3, bits2, bits1, ddw2, dw1, pw1, dw2, grads, 1, &rq, n, H2, W2, H2, W2, 1, H4, W4, pad2, 0.f, 1.f, st)) return -1;
+    const input_affine_t in = input_affine(preprocessing, in_dtype);
+    if (with_c_in(h, [&](auto c) {
+            return launch_sepb16<decltype(c)::value, 2, 1, TX>(h, images, in.u8, ddw2, bits1, nullptr, nullptr, dw0, pw0, dw1, grads, 0, &rq, n, H, W, H2, W2, pad2, H2, W2, 1, in.sub, in.div, st);
+        })) return -1;
+    return finish_step(h, &rq, grads, st);
+}
+}      // namespace
 
 extern "C" int ubd_train_step(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
                               const int32_t *y_true, int n, int height, int width, float *grads, float *loss,
@@ -1606,41 +1611,29 @@ extern "C" int ubd_train_step(ubd_handle *h, const float *params, const void *im
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     float *logits = (float *)(ws + T.off_logits), *dlogits = (float *)(ws + T.off_dlogits);
-    const long npix = (long)n * (height / 4) * (width / 4);
-    const void *acts[7];
+    const bool f32 = h->cfg.dtype == UBD_F32, bf16 = h->cfg.dtype == UBD_BF16;
+    bwd_pass p = {h, params, images, in_dtype, preprocessing, n, height, width, dlogits, grads, ws, T, st};
     int rc;
-    if (h->cfg.dtype == UBD_F32) {
+    if (f32) {
         rc = ubd_forward_impl(h, params, images, in_dtype, preprocessing, n, height, width, logits, ws, T.fwd, st);
-        if (rc) return rc;
-        rc = ubd_loss_impl(logits, h->k_out, y_true, npix, loss, dlogits, ws + T.off_loss, st, h);
-        if (rc) return rc;
-        for (int k = 0; k < 7; ++k) acts[k] = ws + T.fwd.off_acts[k];
-        return backward_impl<float>(h, params, images, in_dtype, preprocessing, n, height, width, ws + T.fwd.off_a1, ws + T.fwd.off_a2,
-                                    acts, (const float *)(ws + T.fwd.off_wfrag), dlogits, grads, ws, T, st);
+        p.a1 = ws + T.fwd.off_a1; p.a2 = ws + T.fwd.off_a2; p.wfrag = (const float *)(ws + T.fwd.off_wfrag);
+        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd.off_acts[k];
+    } else {
+        UBD_REQUIRE(in_dtype == UBD_IN_F32 || in_dtype == UBD_IN_U8, "ubd_train_step: bad in_dtype %d", in_dtype);
+        if (bf16) {                                                // the one-launch prologue: everything packed, gradients and loss scratch zeroed
+            train_prologue_args a = fill_pack_args(h);
+            a.loss_zero_words = ubd_loss_zero_bytes() / 4;
+            a.wfrag32 = (float *)(ws + T.fwd16.off_wfrag32); a.wfrag16 = (unsigned *)(ws + T.fwd16.off_wfrag16);
+            a.bfrag = (float *)(ws + T.off_bfrag); a.frag16t = (unsigned *)(a.bfrag + UBD_BWD_DIRECT_FLOATS);
+            a.grads = grads; a.loss_zero = (unsigned *)(ws + T.off_loss);
+            hipLaunchKernelGGL((train_prologue16_kernel<__bf16>), dim3(4 * 48), dim3(256), 0, st, params, a);
+        }
+        rc = ubd_forward16_layout(h, params, images, bf16 ? (in_dtype | UBD_IN_PREPACKED) : in_dtype, preprocessing, n, height, width, logits, ws, T.fwd16, st);
+        p.a1 = ws + T.fwd16.off_a1; p.a2 = ws + T.fwd16.off_a2; p.wfrag = (const float *)(ws + T.fwd16.off_wfrag32);
+        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd16.off_acts[k];
     }
-    UBD_REQUIRE(in_dtype == UBD_IN_F32 || in_dtype == UBD_IN_U8, "ubd_train_step: bad in_dtype %d", in_dtype);
-    const bool one_prologue = h->cfg.dtype == UBD_BF16;                          // configs[2] / configs[3]
-    if (one_prologue) {
-        train_prologue_args a;
-        for (int s = 0; s < 3; ++s) { a.pa.off_sep_dw[s] = h->off_sep_dw[s]; a.pa.off_sep_pw[s] = h->off_sep_pw[s]; a.pb.off_sep_pw[s] = h->off_sep_pw[s]; }
-        for (int k = 0; k < UBD_NUM_DIL; ++k) { a.pa.off_dil_k[k] = h->off_dil_k[k]; a.pb.off_dil_k[k] = h->off_dil_k[k]; }
-        a.pa.c_in = a.pb.c_in = h->cfg.c_in;
-        a.ps = ubd_pack_sep16_args(h);
-        a.off0 = h->off_dil_k[0]; a.layer_stride = h->off_dil_k[1] - h->off_dil_k[0];
-        a.n_params = h->n_params; a.loss_zero_words = ubd_loss_zero_bytes() / 4;
-        a.wfrag32 = (float *)(ws + T.fwd16.off_wfrag32); a.wfrag16 = (unsigned *)(ws + T.fwd16.off_wfrag16);
-        a.bfrag = (float *)(ws + T.off_bfrag); a.frag16t = (unsigned *)(a.bfrag + UBD_BWD_DIRECT_FLOATS);
-        a.grads = grads; a.loss_zero = (unsigned *)(ws + T.off_loss);
-        hipLaunchKernelGGL((train_prologue16_kernel<__bf16>), dim3(4 * 48), dim3(256), 0, st, params, a);
-    }
-    rc = ubd_forward16_layout(h, params, images, one_prologue ? (in_dtype | UBD_IN_PREPACKED) : in_dtype, preprocessing, n, height, width, logits, ws, T.fwd16, st);
     if (rc) return rc;
-    rc = ubd_loss_impl(logits, h->k_out, y_true, npix, loss, dlogits, ws + T.off_loss, st, h, one_prologue);
+    rc = ubd_loss_impl(logits, h->k_out, y_true, (long)n * (height / 4) * (width / 4), loss, dlogits, ws + T.off_loss, st, h, bf16);
     if (rc) return rc;
-    for (int k = 0; k < 7; ++k) acts[k] = ws + T.fwd16.off_acts[k];
-    if (h->cfg.dtype == UBD_BF16)
-        return backward_impl<__bf16>(h, params, images, in_dtype, preprocessing, n, height, width, ws + T.fwd16.off_a1, ws + T.fwd16.off_a2,
-                                     acts, (const float *)(ws + T.fwd16.off_wfrag32), dlogits, grads, ws, T, st, true);
-    return backward_impl<_Float16>(h, params, images, in_dtype, preprocessing, n, height, width, ws + T.fwd16.off_a1, ws + T.fwd16.off_a2,
-                                   acts, (const float *)(ws + T.fwd16.off_wfrag32), dlogits, grads, ws, T, st);
+    return bf16 ? p.backward_bf16() : f32 ? p.backward_f32<float>() : p.backward_f32<_Float16>();
 }

@@ -38,7 +38,10 @@ for f in api forward fwd16 wino wino6 postprocess loss backward train comm raste
     [ "$(cat _obj/api.build_id 2>/dev/null)" != "$BUILD_ID" ] && stale=1
   fi
   if [ ! -f _obj/$f.o ] || [ $stale = 1 ]; then
-    ( /opt/rocm/bin/hipcc $FLAGS $extra -c $f.hip -o _obj/$f.o ${UBD_SAVE_TEMPS:+-save-temps=obj} ) &
+    # UBD_SAVE_TEMPS=1: the unit's gfx950 assembly beside its object, for tools/cmp_device_code.py.  A compile of its own:
+    # -save-temps compiles the preprocessed text, where `#pragma unroll MACRO` (fwd16.hip) no longer finds its macro
+    ( /opt/rocm/bin/hipcc $FLAGS $extra -c $f.hip -o _obj/$f.o
+      [ -z "$UBD_SAVE_TEMPS" ] || /opt/rocm/bin/hipcc $FLAGS $extra -Wno-unused-command-line-argument --cuda-device-only -S $f.hip -o _obj/$f-hip-amdgcn-amd-amdhsa-gfx950.s ) &
     pids+=($!)
   fi
 done

@@ -19,23 +19,33 @@ struct ubd_handle {
     size_t off_dil_k[UBD_NUM_DIL], off_dil_b[UBD_NUM_DIL];
     size_t off_head_k, off_head_b;
     size_t n_params;
-    int num_cus;
+    int num_cus;              // CUs of the device; UBD_TEST_NUM_CUS=n (test hook): pretend it has n, so that every persistent kernel walks many tiles per block even on
+                              // the small shapes the CPU oracle can check (tests/test_gpu_persistent.py; ubd_num_cus reports what was taken)
+    // The UBD_* environment switches below are the definition of each switch (api.hip holds only the table that parses them).  They are read
+    // ONCE, in ubd_create, never in a launch path; a value that is not named here is ignored.
     int pp_lds_attr_set;      // pp_front_lds_kernel's dynamic-LDS limit has been raised on this handle's device
     int fuse_force;           // UBD_STEM named a fused variant explicitly: use it at any launch size
     int split_headbwd;        // UBD_HEADBWD=split: bf16 train step with classes: head data gradient and head weight gradient as two kernels (diagnostics / tests)
     int no_pair_dilbwd;       // UBD_DILBWD=pair8: narrow sub-grids (dilation 16 on 128-wide maps) keep the 8-wide tiles instead of pairs in 16-wide ones (diagnostics / tests)
     int split_dilbwd;         // UBD_DILBWD=split: bf16 dilated backward as two kernels per layer (diagnostics / tests)
-    int split_stem16;         // UBD_STEM16=split: 16-bit pass with separate L1 and L2 kernels (diagnostics / tests)
-    int pp_global, pp_split, pp_poison, pp_serial_tail, pp_threads_512;   // UBD_PP_* test hooks, read ONCE in ubd_create (never in the launch path)
+    int split_stem16;         // 16-bit pass: 0 = L1 -> L2 -> L3 in one kernel (default), 2 = L1 -> L2 fused + L3 (UBD_STEM16=fused12), 1 = three kernels (UBD_STEM16=split) (diagnostics / tests)
+    // UBD_PP_GLOBAL / _SPLIT / _POISON / _SERIAL_TAIL / _THREADS_512 set to anything (postprocess test hooks): multi-launch front end at any map size /
+    // separate tail launches / LDS poisoning + forest integrity check / one-lane box fit / the 512-thread block shape the job has inside the stem kernel
+    int pp_global, pp_split, pp_poison, pp_serial_tail, pp_threads_512;
     int sepb_x_regs;          // UBD_SEPB16_X=regs: bf16 backward of L1 stages its fp32 input patch through registers even where LDS-DMA applies (diagnostics / tests)
     int split_sepbwd32;       // UBD_SEPBWD=split: fp32 train step with the stand-alone data-gradient kernels of the separable layers (sep_dx_kernel) instead of G tiles built inside the weight-gradient kernels (diagnostics / tests)
-    int chain_reduce;         // bf16 train step: weight-gradient kernels total the previous producer's partial rows at their end (default; UBD_REDUCE=batched: the two stand-alone launches)
+    int chain_reduce;         // 1 (default): bf16 train step: weight-gradient kernels total the previous producer's partial rows at their end (0, UBD_REDUCE=batched: the two stand-alone launches)
     int direct_dil16;         // UBD_DILCONV16=direct: 16-bit forward dilated layers with the direct (unstaged) kernel (diagnostics / tests)
-    int fuse_stem;            // inference stem: 2 = L1 -> L2 -> L3 in one kernel (default with fml padding), 1 = L2 -> L3 fused, 0 = three kernels (UBD_STEM=fused123|fused|unfused)
+    // Inference stem: 2 = L1 -> L2 -> L3 in one kernel (stem123.h; UBD_STEM=fused123), 3 = that kernel with one cold-started tile per work unit
+    // (UBD_STEM=cold123, fml padding only; what 2 takes by itself for small launches), 1 = L1, then L2 -> L3 fused with L2's output in LDS (stem23.h;
+    // UBD_STEM=fused), 0 = three kernels (UBD_STEM=unfused).  Default: 2 with the fml padding (the variant that inherits the 33rd L2 column from the tile
+    // to its left: 0.405 vs 0.417 ms per forward pass at 32 x 512 x 512), else 0 -- with TF 'same' padding the fused kernel only ties the separate
+    // kernels.  Training always runs the separate kernels.
+    int fuse_stem;
     int use_wino;             // 1: Winograd F(2x2,3x3) dilated layers (default), 0: direct implicit GEMM (UBD_DILCONV=direct)
     int loss_chain;           // UBD_LOSS=chain: the loss as its five dependent launches (the batch-global mode's form) instead of the one-launch kernel (diagnostics / tests)
     int wino_x6;              // forward Winograd products as three-way bf16 split products on the bf16 MFMA (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
-    int wino6_natural;        // UBD_WINO6_LAYOUT=natural: the fp32 inference pass keeps every activation in the natural column order (wino6.hip)
+    int wino6_natural;        // UBD_WINO6_LAYOUT=natural: the fp32 inference pass keeps every activation in the natural column order (wino6.hip), no phase-major layouts between the layers (the reference side of the bit-identity tests)
 };
 
 static const int UBD_DILATIONS[UBD_NUM_DIL] = {1, 2, 4, 8, 16, 1};
