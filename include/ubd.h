@@ -259,6 +259,37 @@ int ubd_evaluate_objects(const int32_t *quads, const int32_t *classes, const int
 int ubd_evaluate_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int64_t *offset_bytes,
                                int64_t *stride_doubles);
 
+/* --- pixel classification accuracy (semantic_segmentation/evaluation.py:546-575, _calc_pixel_classification_correctness_mask) ---
+ * For n maps of map_h x map_w: pred = argmax over the n_classes class logits of a pixel (np.argmax: first maximum, first NaN),
+ * mask = label > 0, true = label - 1 where mask else 0, correct = (true == pred) at every pixel.  Objects are the external
+ * 8-connected components of mask (every one, single pixels included); an object's region is its filled contour (enclosed
+ * background and nested components included) and its accuracy is the share of correct pixels of the region.
+ *   class_logits : device, the first CLASS logit of pixel 0; pixel p's classes are class_logits[p * pixel_stride + 0..n_classes-1]
+ *                  (the net's (n, h, w, 1 + n_classes) output: &logits[1] with pixel_stride = n_classes + 1)
+ *   labels       : device (n, h, w) int32, the y_true layout of ubd_loss: 0 background, k > 0 class k - 1, negative = background
+ *   mask         : device (n, h, w) int8 or NULL: +1 mask & correct, -1 mask & !correct, 0 elsewhere
+ *   per_image    : device (n) records or NULL
+ *   accumulator  : device, ubd_evaluate_pixels_accumulator_bytes() bytes, zeroed by the caller before the first call, as 8-byte
+ *                  slots: [0] int64 n_correct, [1] int64 n_total, [2] int64 n_objects, [3] double sum of the object accuracies,
+ *                  [4] int64 images, [5..7] unused.
+ * The object accuracies are formed in fp64 and summed in a fixed order (objects by raster position of their first pixel, images
+ * in order, one block): the same calls give the same bits.  Limits (non-zero return, ubd_last_error, nothing launched, the
+ * accumulator untouched): n >= 1, n_classes 1..31, 1 <= map_h, map_w < 32768 (no multiple-of-4 requirement),
+ * pixel_stride >= n_classes.  Any n: the call works through the batch in chunks of less than 2^31 pixels.  Maps of at most
+ * 16384 pixels take three launches per chunk (one block per map labels it in LDS), larger maps seven; no host
+ * synchronisation, no allocation, capturable in a HIP graph. */
+typedef struct ubd_pixel_record {
+    int64_t n_correct, n_total;              /* pixels with mask & correct, pixels with mask */
+    int64_t n_objects;
+    double object_acc_sum;                   /* sum over the image's objects of correct / size */
+} ubd_pixel_record;
+size_t ubd_evaluate_pixels_accumulator_bytes(void);
+size_t ubd_evaluate_pixels_workspace_bytes(int n, int map_h, int map_w);   /* 0 outside the limits */
+int ubd_evaluate_pixels(const float *class_logits, int pixel_stride, int n_classes,
+                        const int32_t *labels, int n, int map_h, int map_w,
+                        int8_t *mask, ubd_pixel_record *per_image,
+                        void *accumulator, void *workspace, size_t workspace_bytes, void *stream);
+
 /* --- data parallelism (no reference counterpart: the reference is single-device) -------------------
  * One process per GPU, per-replica loss (losses.py:86-126 applied to the rank's own images), ONE sum all-reduce of the flat
  * fp32 gradient vector per step over RCCL / xGMI, 1/world applied by ubd_adam_step's grad_scale, parameters broadcast once.

@@ -10,9 +10,16 @@ Prints one JSON line per measurement (HIP-event time, median of --iters calls af
       part is host work);
   (c) for orientation only, the host alternative: copy the object lists back and score them with a plain fp64 Python / NumPy
       version of the same rule (score_image_fp64 below; wall clock, one core).
-Usage: python tools/bench_evaluate.py [--iters 20]
+  (d) ubd_evaluate_pixels: 32 maps of 128 x 128 and 8 maps of 256 x 256 with three classes (the LDS form and the global-memory
+      form), the bare C-ABI call on buffers made beforehand and the public evaluate_pixels wrapper (which allocates the
+      workspace and the outputs per call); beside it, in the same run, stand-alone ubd_postprocess on logits whose detection
+      channel draws the SAME maps (the same labelling plus a box fit), and the host alternative: copy logits and labels back
+      and run the numpy / oracle.cv_post restatement on one core (wall clock).
+Usage: python tools/bench_evaluate.py [--iters 20] [--only-pixels]
        rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bench_evaluate.py --trace-loop 50
          (only the 32-image, 1-8-object call, 50 times: the per-kernel split of profiles/r09_evaluate_kernel_stats.csv)
+       rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bench_evaluate.py --trace-loop-pixels 50
+         (both pixel cases, 50 times each: profiles/r10_evaluate_pixels_kernel_stats.csv)
 """
 import argparse
 import json
@@ -296,9 +303,80 @@ def leg_pipeline(iters, n=32, side=512):
             "wall_us_median_with_sync": {"forward_postprocess": wall[0], "plus_c_abi_call": wall[1], "plus_public_evaluate_batch": wall[2]}}
 
 
+class _RawPixelCall:
+    """ubd_evaluate_pixels with every buffer made once"""
+
+    def __init__(self, logits_d, labels_d, n_classes):
+        self.lib = _lib.load()
+        self.z, self.labels, self.C = logits_d, labels_d, n_classes
+        self.n, self.h, self.w = (int(v) for v in labels_d.shape)
+        self.need = int(self.lib.ubd_evaluate_pixels_workspace_bytes(self.n, self.h, self.w))
+        self.ws = torch.empty(self.need, dtype=torch.uint8, device=logits_d.device)
+        self.acc = torch.zeros(ev.pixel_accumulator_bytes(), dtype=torch.uint8, device=logits_d.device)
+        self.mask = torch.empty((self.n, self.h, self.w), dtype=torch.int8, device=logits_d.device)
+
+    def __call__(self):
+        _lib.check(self.lib.ubd_evaluate_pixels(self.z.data_ptr() + 4, self.C + 1, self.C, self.labels.data_ptr(), self.n, self.h, self.w,
+                                                self.mask.data_ptr(), None, self.acc.data_ptr(), self.ws.data_ptr(), self.need,
+                                                torch.cuda.current_stream().cuda_stream), "ubd_evaluate_pixels")
+
+
+def _pixel_inputs(n, side, n_classes=3):
+    """label maps of textured-rectangle scenes and net-shaped logits: the detection channel draws the same maps (for the
+    postprocess beside it), the class channels favour the true class"""
+    labels = synthetic.rectangle_maps(17 + side, n, side, side, n_classes=n_classes).astype(np.int32).reshape(n, side, side)
+    rng = np.random.default_rng(side)
+    z = rng.normal(size=(n, side, side, 1 + n_classes)).astype(np.float32)
+    z[..., 0] = np.where(labels > 0, 5.0, -5.0)
+    np.put_along_axis(z, np.where(labels > 0, labels, 1)[..., None], 1.0, axis=-1)
+    return labels, z
+
+
+def _host_pixels(z, labels):
+    """the host alternative: evaluation.py:546-575 with numpy and the sequential contour routines of oracle/cv_post.c"""
+    from oracle import cv_post as ocv
+    mask = labels > 0
+    correct = np.where(mask, labels - 1, 0) == np.argmax(z[..., 1:], axis=-1)
+    accs = []
+    for i in range(len(labels)):
+        h, w = mask[i].shape
+        for cnt in ocv.find_contours(mask[i].astype(np.uint8), approx_simple=False):
+            accs.append(correct[i][ocv.fill_contour(cnt, h, w).astype(bool)].mean())
+    return int((correct & mask).sum()), int(mask.sum()), len(accs), float(np.sum(accs))
+
+
+def leg_pixels(n, side, iters, model):
+    labels, z = _pixel_inputs(n, side)
+    zd, ld = torch.from_numpy(z).cuda(), torch.from_numpy(labels).cuda()
+    call = _RawPixelCall(zd, ld, 3)
+    med, mn = _time(call, iters)
+    acc = torch.zeros(ev.pixel_accumulator_bytes(), dtype=torch.uint8, device="cuda")
+    pub_med, pub_min = _time(lambda: ev.evaluate_pixels(zd, ld, acc, want_mask=True, n_classes=3, per_image=False), iters)
+    pub_wall = _wall(lambda: ev.evaluate_pixels(zd, ld, acc, want_mask=True, n_classes=3, per_image=False), iters)
+    outs = model.alloc_postprocess_outputs(n, side, side, 256)
+    pp_med, pp_min = _time(lambda: model.postprocess_on_device(zd, 0.0, 4, 5, cap=256, outputs=outs), iters)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    host = _host_pixels(zd.cpu().numpy(), ld.cpu().numpy())
+    host_ms = 1e3 * (time.perf_counter() - t0)
+    call.acc.zero_(); call(); torch.cuda.synchronize()
+    a = ev.unpack_pixel_accumulator(call.acc.cpu().numpy())
+    assert (a["n_correct"], a["n_total"], a["n_objects"]) == host[:3], (a, host)
+    return {"leg": f"evaluate_pixels_{n}_maps_{side}x{side}_3_classes", "form": "lds" if side * side <= 16384 else "global",
+            "objects": a["n_objects"], "logit_bytes": int(z.nbytes), "us_median": med, "us_min": mn,
+            "public_evaluate_pixels": {"us_median": pub_med, "us_min": pub_min, "wall_us_median_with_sync": pub_wall},
+            "standalone_postprocess_same_maps": {"us_median": pp_med, "us_min": pp_min, "found": int(outs[3].clamp(max=256).sum().item())},
+            "host_copy_and_numpy_oracle_ms": round(host_ms, 1)}
+
+
+PIXEL_CASES = ((32, 128), (8, 256))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--only-pixels", action="store_true", help="only the ubd_evaluate_pixels legs")
+    ap.add_argument("--trace-loop-pixels", type=int, default=0, help="only N calls of each pixel case (for a kernel trace)")
     ap.add_argument("--trace-loop", type=int, default=0, help="only N calls of the 32-image 1-8-object case (for a kernel trace)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -309,11 +387,23 @@ def main():
             call()
         torch.cuda.synchronize()
         return
+    if args.trace_loop_pixels:
+        for n, side in PIXEL_CASES:
+            labels, z = _pixel_inputs(n, side)
+            call = _RawPixelCall(torch.from_numpy(z).cuda(), torch.from_numpy(labels).cuda(), 3)
+            for _ in range(args.trace_loop_pixels):
+                call()
+            torch.cuda.synchronize()
+        return
     print(json.dumps({"device": torch.cuda.get_device_name(0)}), flush=True)
-    for n in (32, 64):
-        for lo, hi in ((1, 8), (64, 64)):
-            print(json.dumps(leg_alone(n, lo, hi, args.iters)), flush=True)
-    print(json.dumps(leg_pipeline(args.iters)), flush=True)
+    if not args.only_pixels:
+        for n in (32, 64):
+            for lo, hi in ((1, 8), (64, 64)):
+                print(json.dumps(leg_alone(n, lo, hi, args.iters)), flush=True)
+        print(json.dumps(leg_pipeline(args.iters)), flush=True)
+    pp_model = Model(NetConfig(class_names=["a", "b", "c"], grey=False), seed=0)
+    for n, side in PIXEL_CASES:
+        print(json.dumps(leg_pixels(n, side, args.iters, pp_model)), flush=True)
 
 
 if __name__ == "__main__":

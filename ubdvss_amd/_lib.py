@@ -17,6 +17,7 @@ ABI_VERSION = 3
 UBD_WARP_COPY, UBD_WARP_AFFINE, UBD_WARP_PERSPECTIVE = 0, 1, 2
 UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS = 8, 256, 256, 16
 UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
+UBD_MAX_CLASSES = 31
 
 
 class UbdConfig(ctypes.Structure):
@@ -28,6 +29,11 @@ class UbdEvalRecord(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("tp", "fp", "fn", "one_to_one", "one_to_many", "many_to_one", "matched_boxes_count",
                                               "detection_rate", "n_gt", "n_found", "flags", "reserved")] + \
                [(k, ctypes.c_double) for k in ("iou_sum", "precision_by_area", "recall_by_area", "iou_by_area")]
+
+
+class UbdPixelRecord(ctypes.Structure):
+    _fields_ = [("n_correct", ctypes.c_int64), ("n_total", ctypes.c_int64), ("n_objects", ctypes.c_int64),
+                ("object_acc_sum", ctypes.c_double)]
 
 
 # every symbol include/ubd.h declares: name -> (restype, argtypes)
@@ -62,6 +68,9 @@ SIGNATURES = {
     "ubd_evaluate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ubd_evaluate_objects": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_evaluate_tables_layout": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_evaluate_pixels_accumulator_bytes": (_sz, []),
+    "ubd_evaluate_pixels_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ubd_evaluate_pixels": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ubd_comm_unique_id": (_i, [_vp]),
     "ubd_comm_init": (_i, [_vp, _vp, _i, _i, _i]),
     "ubd_comm_destroy": (_i, [_vp]),

@@ -15,7 +15,7 @@ print(h.hexdigest()[:16])
 PY
 )
 pids=()
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate; do
+for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate evaluate_pixels; do
   [ -f $f.hip ] || continue
   extra=""
   # OpenCV-exact float geometry: no FMA contraction in postprocess
@@ -47,7 +47,7 @@ for f in api forward fwd16 wino wino6 postprocess loss backward train comm raste
 done
 for p in "${pids[@]}"; do wait $p; done
 objs=""
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
+for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate evaluate_pixels; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
 echo "$BUILD_ID" > _obj/api.build_id
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs -ldl
 echo "built $OUT"

@@ -5,10 +5,12 @@ The reference builds shapely polygons image by image on the host.  Here the area
 matching, the group and by-area unions and the counters at every IoU threshold are computed on the MI355X by
 ``ubd_evaluate_objects`` (include/ubd.h) from the object lists ``ubd_postprocess`` left in device memory, and summed into a
 device accumulator: a validation epoch is any number of ``evaluate_batch`` calls and ONE small read in ``get_metrics``.
+The pixel classification accuracies of ``_calc_pixel_classification_correctness_mask`` (:546-575) come from
+``ubd_evaluate_pixels`` in the same way: the class logits of the forward pass and the label maps stay on the device, the
+sums go to a second small accumulator and the correctness mask comes back as a device tensor.
 There is no CPU path: without a GPU the entry points raise ``RuntimeError``.
 
-Not here: the pixel classification accuracies of ``_calc_pixel_classification_correctness_mask``,
-``ImageResultCategories``, visualisations, non-convex ground truth.
+Not here: ``ImageResultCategories``, visualisations, non-convex ground truth.
 """
 import ctypes
 import math
@@ -238,6 +240,111 @@ def evaluate_objects(quads, classes, counts, gt_polygons, gt_classes, thresholds
     return rec
 
 
+# ---- pixel classification accuracy (ubd_evaluate_pixels) ----------------------------------------------------------------------------
+_PIX_REC_BYTES = ctypes.sizeof(_lib.UbdPixelRecord)
+_PIX_REC_DTYPE = np.dtype([("n_correct", np.int64), ("n_total", np.int64), ("n_objects", np.int64), ("object_acc_sum", np.float64)])
+assert _PIX_REC_DTYPE.itemsize == _PIX_REC_BYTES == 32
+
+
+def pixel_accumulator_bytes():
+    return int(_lib.load().ubd_evaluate_pixels_accumulator_bytes())
+
+
+def unpack_pixel_accumulator(acc_host):
+    """host bytes of a pixel accumulator -> dict(n_correct, n_total, n_objects, object_acc_sum, images)"""
+    raw = np.ascontiguousarray(acc_host).view(np.uint8).reshape(-1)
+    i64, f64 = raw.view(np.int64), raw.view(np.float64)
+    return dict(n_correct=int(i64[0]), n_total=int(i64[1]), n_objects=int(i64[2]), object_acc_sum=float(f64[3]), images=int(i64[4]))
+
+
+def pixel_logs_from_sums(n_correct, n_total, n_objects, object_acc_sum):
+    """The two pixel entries of the reference's ``scalar_logs`` (evaluation.py:526-530) from the sums of an epoch.  A zero
+    denominator gives nan, as the reference's numpy division (0 / 0) and its mean of an empty list do."""
+    nan = float("nan")
+    return {"classification_pixel_acc_total": n_correct / n_total if n_total > 0 else nan,
+            "classification_pixel_acc_object": object_acc_sum / n_objects if n_objects > 0 else nan}
+
+
+def _pixel_stride(t):
+    """(N, h, w, C) float32 tensor -> floats between consecutive pixels when the view is one regular pixel grid (the class
+    slice of the net's contiguous output is), else None"""
+    n, h, w, c = (int(v) for v in t.shape)
+    if c > 1 and t.stride(3) != 1:
+        return None
+    units = ((w, t.stride(2), 1), (h, t.stride(1), w), (n, t.stride(0), h * w))
+    ps = None
+    for size, stride, pixels in units:
+        if size > 1:
+            if stride % pixels:
+                return None
+            if ps is None:
+                ps = stride // pixels
+            if stride != ps * pixels:
+                return None
+    if ps is None:
+        ps = c
+    return ps if ps >= c else None
+
+
+def evaluate_pixels(class_logits, labels, accumulator, want_mask=False, n_classes=None, per_image=True):
+    """One ubd_evaluate_pixels call on the current stream.  class_logits: float32 device tensor, either the net's full output
+    (N, h, w, n_classes + 1) or a class slice (N, h, w, n_classes); with n_classes given the two are told apart by the last
+    dimension, without it the tensor is a class slice.  A full tensor (and any view that is a regular pixel grid) is passed as
+    it lies, without a copy.  labels: (N, h, w) or (N, h, w, 1), int32 device tensor or numpy array (the y_true of the loss).
+    accumulator: device uint8 tensor of pixel_accumulator_bytes(), zeroed before the first call.  Returns (records, mask):
+    the per-image records as a device uint8 tensor (N, 32) (None with per_image=False) and the correctness mask, an int8
+    device tensor (N, h, w) of -1 / 0 / 1 (None unless want_mask)."""
+    torch = _require_gpu()
+    lib = _lib.load()
+    if not torch.is_tensor(class_logits):
+        class_logits = torch.from_numpy(np.ascontiguousarray(np.asarray(class_logits, dtype=np.float32))).to(accumulator.device)
+    if class_logits.dim() != 4 or class_logits.dtype != torch.float32:
+        raise ValueError(f"class logits must be a float32 (N, h, w, C) tensor, got {tuple(class_logits.shape)} {class_logits.dtype}")
+    dev = class_logits.device
+    last = int(class_logits.shape[3])
+    if n_classes is None:
+        C = last
+    else:
+        C = int(n_classes)
+        if last == C + 1:
+            class_logits = class_logits[..., 1:]
+        elif last != C:
+            raise ValueError(f"class logits have {last} channels: expected {C} (a class slice) or {C + 1} (the net's output)")
+    n, h, w = (int(v) for v in class_logits.shape[:3])
+    stride = _pixel_stride(class_logits)
+    if stride is None:
+        class_logits = class_logits.contiguous()
+        stride = C
+    if not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels).astype(np.int32, copy=False)))
+    if labels.dim() == 4 and labels.shape[3] == 1:
+        labels = labels[..., 0]
+    if tuple(labels.shape) != (n, h, w):
+        raise ValueError(f"labels {tuple(labels.shape)} do not match the logits' maps {(n, h, w)}")
+    if labels.dtype != torch.int32:
+        raise ValueError(f"labels must be int32, got {labels.dtype}")
+    labels = labels.to(dev).contiguous()
+    need = int(lib.ubd_evaluate_pixels_workspace_bytes(n, h, w)) if 1 <= C <= _lib.UBD_MAX_CLASSES else 0
+    if need == 0:
+        raise ValueError(f"pixel evaluation sizes outside the limits: n={n} h={h} w={w} classes={C} "
+                         f"(n >= 1, sides 1..32767, classes 1..{_lib.UBD_MAX_CLASSES})")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    rec = torch.empty((n, _PIX_REC_BYTES), dtype=torch.uint8, device=dev) if per_image else None
+    mask = torch.empty((n, h, w), dtype=torch.int8, device=dev) if want_mask else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.ubd_evaluate_pixels(class_logits.data_ptr(), int(stride), C, labels.data_ptr(), n, h, w,
+                                       mask.data_ptr() if mask is not None else None, rec.data_ptr() if rec is not None else None,
+                                       accumulator.data_ptr(), ws.data_ptr(), need, stream), "ubd_evaluate_pixels")
+    # the inputs and the workspace were allocated on this stream: the caching allocator reuses them in stream order
+    return rec, mask
+
+
+def pixel_records_to_numpy(records):
+    """device (n, 32) uint8 pixel records -> host structured array (n) (synchronises)"""
+    h = records.cpu().numpy()
+    return h.reshape(-1).view(_PIX_REC_DTYPE)
+
+
 def records_to_numpy(records):
     """device (n, T, 80) uint8 records -> host structured array (n, T) (synchronises)"""
     h = records.cpu().numpy()
@@ -366,6 +473,7 @@ class DatasetMetricCalculator:
         self._with_cls = bool(net_config.is_classification_supported())
         self._n_classes = net_config.get_n_classes() if self._with_cls else 0
         self._acc = None
+        self._pix_acc = None
         self._images = 0
 
     def _accumulator(self, device):
@@ -383,8 +491,11 @@ class DatasetMetricCalculator:
         """gt_objects: per image a list of markup records (``bbox``, ``object_type`` id).  found_objects: the same kind of
         lists (integer quads), or the device triple (quads, classes, counts) of ``ModelRunner.predict_on_device``.  scales:
         (n, 2) xscale, yscale applied to the found quads on the device (model_runner.py:140-148), or None.  Adds the batch
-        to the device sums and returns (records, None): the per-image records of every threshold as a device tensor -- no
-        host copy is made here -- and None for the pixel classification mask, which is not computed."""
+        to the device sums and returns (records, mask): the per-image records of every threshold as a device tensor -- no
+        host copy is made here -- and the pixel classification correctness mask.  With a classification config and both
+        gt_segmap (the label maps, (N, h, w) or (N, h, w, 1) int32) and classification_logits (the net's output or its class
+        slice, see ``evaluate_pixels``) the pixel accuracies of evaluation.py:546-575 are added to their device sums too and
+        mask is an int8 device tensor (N, h, w) of -1 / 0 / 1; in every other case mask is None."""
         torch = _require_gpu()
         for i, objs in enumerate(gt_objects):
             if len(objs) == 0:
@@ -401,8 +512,14 @@ class DatasetMetricCalculator:
             raise ValueError(f"{len(gt_objects)} ground-truth lists for {int(quads.shape[0])} images")
         rec = evaluate_objects(quads, classes, counts, polys, cls, self.IOU_THRESHOLDS, self._n_classes,
                                self._accumulator(quads.device), scales=scales, image_offset=self._images)
+        mask = None
+        if self._with_cls and gt_segmap is not None and classification_logits is not None:
+            if self._pix_acc is None:
+                self._pix_acc = torch.zeros(pixel_accumulator_bytes(), dtype=torch.uint8, device=quads.device)
+            _, mask = evaluate_pixels(classification_logits, gt_segmap, self._pix_acc, want_mask=True, n_classes=self._n_classes,
+                                      per_image=False)
         self._images += len(gt_objects)
-        return rec, None
+        return rec, mask
 
     def get_per_threshold_metrics(self):
         """The one read of the epoch: {threshold: FtMetrics} from the device sums.  Raises RuntimeError when an image was
@@ -431,12 +548,19 @@ class DatasetMetricCalculator:
         return out
 
     def get_metrics(self):
-        return self.scalar_logs(self.get_per_threshold_metrics(), self._net_config)
+        """``scalar_logs`` of the epoch; with pixel sums (a classification config whose batches came with label maps and
+        logits) also classification_pixel_acc_total and classification_pixel_acc_object (evaluation.py:526-530)."""
+        logs = self.scalar_logs(self.get_per_threshold_metrics(), self._net_config)
+        if self._pix_acc is not None:
+            p = unpack_pixel_accumulator(self._pix_acc.cpu().numpy())
+            if p["images"] > 0:
+                logs.update(pixel_logs_from_sums(p["n_correct"], p["n_total"], p["n_objects"], p["object_acc_sum"]))
+        return logs
 
     @classmethod
     def scalar_logs(cls, per_iou_metrics, net_config):
         """{threshold: FtMetrics} -> the flat dict of the reference's ``scalar_logs`` (evaluation.py:509-544; the key strings
-        are the interface), without the two pixel accuracies.  Per-type accuracies are logged at the threshold 0.5 only."""
+        are the interface), without the two pixel accuracies (``get_metrics`` adds them from the pixel sums).  Per-type accuracies are logged at the threshold 0.5 only."""
         with_types = bool(net_config.is_classification_supported())
         logs = {}
         for thr in cls.IOU_THRESHOLDS:

@@ -88,10 +88,15 @@ class ModelRunner:
         (ubd_evaluate_objects) are enqueued on the current stream -- the found objects never leave the device; the quads are
         rescaled to the original images there with meta.xscale / meta.yscale (meta_infos may be None: no rescale) -- and
         the ``scalar_logs`` of DatasetMetricCalculator.get_metrics are returned after ONE read of the device sums.
-        images: (N,H,W,C) numpy array or device tensor; gt_objects: per image a list of markup records."""
+        images: (N,H,W,C) numpy array or device tensor; gt_objects: per image a list of markup records.
+        A batch may also be (images, gt_objects, meta_infos, gt_segmap), gt_segmap the label maps (N,h,w) or (N,h,w,1) int32
+        (device tensor or numpy, e.g. of ``prepare_batch_on_device``): on a classification config the logits the forward pass
+        just wrote are then scored in place (ubd_evaluate_pixels) and the two pixel accuracies join the result."""
         from .evaluation import DatasetMetricCalculator
         evaluator = DatasetMetricCalculator(self._net_config)
-        for images, gt_objects, meta_infos in batches:
+        for batch in batches:
+            images, gt_objects, meta_infos = batch[:3]
+            gt_segmap = batch[3] if len(batch) > 3 else None
             if not torch.is_tensor(images):
                 x = np.asarray(images)
                 if x.dtype != np.uint8:
@@ -100,10 +105,12 @@ class ModelRunner:
             images = images.to(model.device)
             if meta_infos is not None and len(meta_infos) != len(images):
                 raise AssertionError("one meta_info per image is required")
-            _, _, quads, classes, counts = self.predict_on_device(model, images)
+            logits, _, quads, classes, counts = self.predict_on_device(model, images)
             self.flush()                                # pipelined runner: this batch's postprocess before its evaluation
             scales = None if meta_infos is None else np.array([[m.xscale, m.yscale] for m in meta_infos], dtype=np.float64)
-            evaluator.evaluate_batch(gt_objects, (quads, classes, counts), meta_infos=meta_infos, scales=scales)
+            evaluator.evaluate_batch(gt_objects, (quads, classes, counts), gt_segmap=gt_segmap,
+                                     classification_logits=logits if gt_segmap is not None else None,
+                                     meta_infos=meta_infos, scales=scales)
         return evaluator.get_metrics()
 
     def predict(self, model, images, rescale=False, meta_infos=None):
