@@ -1,7 +1,8 @@
 /* ubd.h -- C ABI of libubd_hip.so: the MI355X (gfx950) implementation of the
  * ubdvss hot path (dilated-FCN forward -> threshold map -> external components ->
  * rotated quads; train step = forward + loss + backward + Adam; training input:
- * geometric augmentation warps, bicubic resize, label rasteriser).
+ * geometric augmentation warps, photometric augmentation stages, bicubic resize,
+ * label rasteriser).
  *
  * The reference (asmekal/ubdvss) has no FFI: the path sits behind three Python
  * seams.  Each entry point below names the seam it replaces (paths relative to
@@ -202,6 +203,51 @@ typedef struct ubd_warp_desc {
 } ubd_warp_desc;
 int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes, const ubd_warp_desc *descs,
                     int channels, int n, void *stream);
+
+/* --- photometric augmentation ---------------------------------------------------
+ * The built part of the reference's imgaug stage (augmentation.py:276-332), one operation ("stage") per image per call, for n
+ * uint8 images of `channels` (1 or 3) channels with packed rows (pitch w * channels), every image with its own size, at
+ * src + src_offset, written at dst + dst_offset.  imgaug and OpenCV are not available to pin against: every mode is DEFINED in
+ * integer arithmetic here (each follows imgaug's published formula) and the device matches the numpy oracle of the tests bit for
+ * bit; PARITY WITH imgaug / cv2 IS UNPINNED.  `>>` is an arithmetic shift, clamp is to 0..255, borders are reflect-101 (fold
+ * with period 2(n-1); always 0 for n = 1).  Layout of p[] per mode:
+ *   UBD_PHOTO_AFFINE  (Invert, Add, Multiply, ContrastNormalization): p[c] = m_c, p[3 + c] = a_c (Q16), c = channel;
+ *                     out = clamp((m_c v + a_c + 32768) >> 16)
+ *   UBD_PHOTO_GREY    (Grayscale): p[0] = aq = rint(alpha 16384); g = (4899 R + 9617 G + 1868 B + 8192) >> 14,
+ *                     out = ((16384 - aq) v + aq g + 8192) >> 14; one channel: the identity
+ *   UBD_PHOTO_FILTER3 (Sharpen, Emboss): p[0..8] = the 3x3 correlation taps in Q14, row-major, |tap| <= 13 * 16384;
+ *                     out = clamp((sum tap v + 8192) >> 14)
+ *   UBD_PHOTO_SEP     (GaussianBlur): p[0] = radius r (1..4), p[1 + d] = Q14 weight at distance d = 0..r, each 0..16384, the
+ *                     2r + 1 taps summing to 16384; rows: t = (sum w v + 64) >> 7, then columns: out = clamp((sum w t + 2^20) >> 21)
+ *   UBD_PHOTO_BOX     (AverageBlur): p[0] = k (2..7); window offsets -(k/2) .. k-1-(k/2) on both axes, S its sum,
+ *                     out = (2 S + k k) / (2 k k)
+ *   UBD_PHOTO_NOISE   (AdditiveGaussianNoise): p[0] = the bits of the fp32 scale (finite, >= 0); flags bit 0 = per channel
+ *   UBD_PHOTO_DROPOUT (Dropout): p[0] = the bits of the uint32 threshold floor(p 2^32); flags bit 0 = per channel
+ * Random words of NOISE / DROPOUT: Philox4x32-10, key = seed (lo, hi), counter = (y w + x, 0, j, 0); block j = 0 gives r0..r3,
+ * j = 1 gives r4..r7.  DROPOUT: 0 where the word < threshold; channel c tests r_c per channel, else every channel tests r0.
+ * NOISE: u1 = ((a >> 9) + 0.5) 2^-23, u2 likewise from b, z = sqrt(-2 ln u1) cos(2 pi u2) in fp32, out = clamp(rint(v + scale z));
+ * (a, b) = (r_2c, r_2c+1) per channel, else (r0, r1).
+ * The pointwise modes (AFFINE, GREY, NOISE, DROPOUT) may run in place (same address for source and destination of an image);
+ * any other overlap of an image's source and destination is refused, for the neighbourhood modes (FILTER3, SEP, BOX) every one.
+ * descs: HOST array of n descriptors.  Dword loads / stores are used where the addresses allow; any byte alignment works.
+ * Limits: sides 1..16384 (so an image stays below 2^31 bytes), n >= 1, channels 1 or 3, ranges inside the two buffers, a known
+ * mode, BOX k 2..7, SEP radius 1..4; and the parameter ranges that keep every sum inside int32: AFFINE |m_c| <= 2^17 and
+ * |a_c| <= 2^24 (all three channels' entries are checked), GREY aq 0..16384, FILTER3 |tap| <= 13 * 16384, SEP weights 0..16384
+ * whose 2r + 1 taps sum to 16384, NOISE scale finite and >= 0 (non-zero return otherwise, nothing launched).
+ * Enqueues at most two launches per 32 images; no host synchronisation, capturable in a HIP graph.
+ * Not built (they need OpenCV's 8-bit HSV or imgaug's noise-mask generators): MedianBlur, SimplexNoiseAlpha(EdgeDetect /
+ * DirectedEdgeDetect), AddToHueAndSaturation, FrequencyNoiseAlpha, ElasticTransformation. */
+enum { UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE, UBD_PHOTO_DROPOUT };
+typedef struct ubd_photo_desc {
+    int64_t src_offset, dst_offset;  /* bytes from src / dst to the image */
+    int32_t w, h;
+    int32_t mode;                    /* UBD_PHOTO_* */
+    int32_t flags;                   /* bit 0: per channel (NOISE, DROPOUT) */
+    uint64_t seed;                   /* Philox key (NOISE, DROPOUT) */
+    int32_t p[24];                   /* per mode, see above; unused entries 0 */
+} ubd_photo_desc;
+int ubd_photometric_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes,
+                           const ubd_photo_desc *descs, int channels, int n, void *stream);
 
 /* --- object-level evaluation ----------------------------------------------------
  * Replaces FtMetricsCalculator (evaluation.py:168-429: areas, the G x F intersection / IoU tables :210-227, analyze :229-328, the

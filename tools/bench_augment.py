@@ -9,8 +9,11 @@ Prints one JSON line per measurement:
     next to (a) the host chain the reference runs -- Pillow rotate + crop + transform + BICUBIC resize + convert('L') +
     ImageDraw label map, on a thread pool, labelled with its core count -- and (b) the plain prepare_batch_on_device on the same
     frames (no augmentation).
-The photometric (imgaug) stage is not part of either side.
-Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5]
+The photometric stage is not part of either side of the end-to-end legs (the plans are sampled without a photo_rng).
+  --photometric: instead of the legs above, HIP-event time of one ubd_photometric_images call per mode over 16 x 1080 x 1920 RGB
+    frames (median of --iters), source and destination in separate buffers, next to the bytes-moved bound of a stage,
+    2 x image bytes (read once, written once), and the GB/s those bytes are in that time.
+Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5] [--photometric]
 """
 import argparse
 import concurrent.futures as cf
@@ -61,6 +64,50 @@ def kernel_leg(name, n, h, w, c, mode, coeffs, dst_size, iters):
     gb = (n * h * w * c + n * dw * dh * c) / 1e9
     return {"leg": name, "images": n, "src": [h, w, c], "dst": [dh, dw, c], "us_median": round(us, 1), "us_min": round(float(np.min(times)), 1),
             "MB_moved": round(gb * 1e3, 1), "TBps": round(gb / us * 1e3, 3), "fraction_of_8TBps": round(gb / us * 1e3 / HBM_TBS, 3)}
+
+
+def photometric_legs(iters, n=16, h=1080, w=1920, c=3):
+    lib = _lib.load()
+    St = aug.Stage
+    stages = [("affine_contrast", St("contrast", {"alphas": (1.7, 0.6, 1.2), "per_channel": True}, None)),
+              ("grey", St("grayscale", {"alpha": 0.6}, None)),
+              ("filter3_sharpen", St("sharpen", {"alpha": 0.5, "lightness": 1.2}, None)),
+              ("sep_gaussian_sigma1_r2", St("gaussian_blur", {"sigma": 1.0}, None)),
+              ("sep_gaussian_sigma3_r4", St("gaussian_blur", {"sigma": 3.0}, None)),
+              ("box_k2", St("average_blur", {"k": 2}, None)),
+              ("box_k7", St("average_blur", {"k": 7}, None)),
+              ("noise_shared", St("noise", {"scale": 6.0, "per_channel": False, "seed": 1}, None)),
+              ("noise_per_channel", St("noise", {"scale": 6.0, "per_channel": True, "seed": 1}, None)),
+              ("dropout_per_channel", St("dropout", {"p": 0.05, "per_channel": True, "seed": 2}, None))]
+    per = h * w * c
+    src = torch.randint(0, 256, (n * per,), dtype=torch.uint8, device="cuda")
+    dst = torch.empty(n * per, dtype=torch.uint8, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out = []
+    for name, st in stages:
+        f = aug.photometric_descs(st, w, h, c)
+        descs = np.zeros(n, aug.PHOTO_DESC)
+        descs["src_offset"] = descs["dst_offset"] = np.arange(n, dtype=np.int64) * per
+        descs["w"], descs["h"], descs["mode"], descs["flags"], descs["seed"] = w, h, f["mode"], f["flags"], f["seed"]
+        descs["p"][:, :len(f["p"])] = f["p"]
+
+        def call():
+            _lib.check(lib.ubd_photometric_images(src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(), descs.ctypes.data, c, n, stream),
+                       "ubd_photometric_images")
+        for _ in range(3):
+            call()
+        times = []
+        for _ in range(iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); call(); b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e3)
+        us = float(np.median(times))
+        gb = 2 * n * per / 1e9
+        out.append({"leg": f"photometric_{name}_{n}x{h}p_c{c}", "mode": int(f["mode"]), "us_median": round(us, 1), "us_min": round(float(np.min(times)), 1),
+                    "MB_bound_2x_image_bytes": round(gb * 1e3, 1), "GBps": round(gb / us * 1e6, 1),
+                    "fraction_of_8TBps": round(gb / us * 1e3 / HBM_TBS, 3)})
+    return out
 
 
 def _pillow_chain(im, plan):
@@ -124,8 +171,13 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--e2e-iters", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
+    ap.add_argument("--photometric", action="store_true", help="time ubd_photometric_images per mode instead of the warp / end-to-end legs")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.photometric:
+        for leg in photometric_legs(args.iters):
+            print(json.dumps(leg), flush=True)
+        return
     _, matrix, size = aug.rotate_matrix_and_size(31.7, (1920, 1080))
     persp = (aug.PERSPECTIVE_MEAN + 0.5 * aug.PERSPECTIVE_HALF).tolist()
     for c in (3, 1):

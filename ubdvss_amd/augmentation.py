@@ -1,4 +1,4 @@
-"""Geometric augmentation on the MI355X -- host mirror of semantic_segmentation/augmentation.py.
+"""Geometric and photometric augmentation on the MI355X -- host mirror of semantic_segmentation/augmentation.py.
 
 The reference augments every training image on the host with Pillow at full source resolution (augmentation.py:50-85): a
 random rotation in +-45 degrees, a random crop that keeps all markup, a quarter turn (+-90 / 180 degrees), a random
@@ -8,8 +8,18 @@ on the host in float64 (``apply_plan_to_markup``), and the pixels are warped on 
 (csrc/warp.hip), bit-identical to Pillow: at most two passes per image (rotation; perspective or a final copy) -- crops and
 quarter turns are signed strided views that the next pass reads through.
 
-THE PHOTOMETRIC (imgaug) STAGE IS NOT BUILT.  Its draw is consumed so that the parameter stream stays the reference's, and
-the plan records that it was requested (``photometric_requested``); the pixels are left as the geometric chain made them.
+The photometric (imgaug) stage (augmentation.py:83-84, :276-332: ``iaa.SomeOf((0, 5), [13 entries], random_order=True)``) runs
+after the warps, on the device, when the caller hands ``sample_plan`` a generator for it (``photo_rng``; imgaug keeps its own
+generator too): ``sample_photometric`` draws up to five stages, ``photometric_descs`` turns a stage into the integer descriptor
+of ``ubd_photometric_images`` (csrc/photometric.hip), ``augment_arrays_on_device`` runs them slot by slot.  Built: GaussianBlur,
+AverageBlur, Sharpen, Emboss, AdditiveGaussianNoise, Dropout, Invert, Add, Multiply, ContrastNormalization, Grayscale.
+NOT BUILT (drawn as often as in the reference, recorded as ``Stage("unbuilt", {"name": ...})``, no pixel changes): MedianBlur,
+SimplexNoiseAlpha(EdgeDetect / DirectedEdgeDetect), AddToHueAndSaturation, FrequencyNoiseAlpha, ElasticTransformation -- they
+need OpenCV's 8-bit HSV or imgaug's noise-mask generators.  imgaug and OpenCV are not available to compare with: each built
+operation follows imgaug's published formula in integer arithmetic DEFINED by include/ubd.h and tests/photometric_oracle.py,
+which the device matches bit for bit; PARITY WITH imgaug / cv2 IS UNPINNED, and the random stream is numpy's, not imgaug's.
+Without ``photo_rng`` the stage's decision draw is consumed, the plan records it (``photometric_requested``) and the pixels
+are left as the geometric chain made them.
 Flips have probability 0 in the reference: their draws are consumed, they are never applied.
 """
 import collections
@@ -26,10 +36,16 @@ from . import _lib
 
 # kind: 'rotate' {angle}, 'crop' {box: unrounded (left, top, right, bottom), window: Pillow's rounded (x0, y0, x1, y1)},
 # 'quarter' {angle: 90 | -90 | 180}, 'perspective' {coeffs: 8 floats}; size: (w, h) after the stage
+# photometric stages (size None; every params has 'entry', the index into PHOTO_ENTRIES; per-channel parameters are 3-tuples):
+# 'gaussian_blur' {sigma}, 'average_blur' {k}, 'sharpen' {alpha, lightness}, 'emboss' {alpha, strength},
+# 'noise' {scale, per_channel, seed}, 'dropout' {p, per_channel, seed}, 'invert' {channels}, 'add' {values, per_channel},
+# 'multiply' {factors, per_channel}, 'contrast' {alphas, per_channel}, 'grayscale' {alpha}, 'unbuilt' {name}
 Stage = collections.namedtuple("Stage", ["kind", "params", "size"])
 # size: (w, h) of the source image; original: the 10 % "feed the original" branch was taken (no further draws);
-# photometric_requested: the reference would have run its imgaug stage here (not built, see the module docstring)
-AugmentationPlan = collections.namedtuple("AugmentationPlan", ["size", "stages", "original", "photometric_requested"])
+# photometric_requested: the reference would have run its imgaug stage here; photometric: that stage's operations, drawn only
+# when sample_plan is given a generator for them (module docstring)
+AugmentationPlan = collections.namedtuple("AugmentationPlan", ["size", "stages", "original", "photometric_requested", "photometric"],
+                                          defaults=[()])
 
 FEED_ORIGINAL_P, ROTATE_P, CROP_P, HFLIP_P, VFLIP_P, ROTATE_90_P, PERSPECTIVE_P, PHOTOMETRIC_P = 0.1, 0.5, 0.5, 0, 0, 0.5, 0.5, 0.7
 ROTATION_90_ANGLES = [90, -90, 180]
@@ -208,7 +224,7 @@ def _sample_crop(boxes, size, rng):
     return Stage("crop", {"box": box, "window": (x0, y0, x1, y1)}, (x1 - x0, y1 - y0))
 
 
-def sample_plan(image_size, markup, rng=None, np_rng=None):
+def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None):
     """Draws the parameters of the reference's ``__augment_image`` (augmentation.py:50-85) for one image of ``image_size`` =
     (w, h) and its ``markup`` and returns an ``AugmentationPlan``: the stages with their numbers and the image size after each.
 
@@ -217,8 +233,11 @@ def sample_plan(image_size, markup, rng=None, np_rng=None):
     ``random()`` (< 0.5) -> ``uniform(-45, 45)``; ``random()`` (< 0.5) -> four ``uniform`` (left, top, right, bottom);
     two ``random()`` for the flips (probability 0); ``random()`` (< 0.5) -> ``choice([90, -90, 180])`` and the
     ``uniform(angle, angle)`` of the reference's ``__rotate``; ``random()`` (< 0.5) -> one ``np_rng.uniform`` of 8 numbers;
-    ``random()`` (< 0.7) for the photometric stage, WHICH IS NOT BUILT: the plan only records that it was requested.
+    ``random()`` (< 0.7) for the photometric stage: the plan records that it was requested.
     ``rng`` / ``np_rng``: objects with the interface of the ``random`` / ``numpy.random`` modules (the defaults).
+    ``photo_rng``: a ``numpy.random.Generator`` for the photometric stage's own draws (imgaug keeps its own generator too);
+    when it is given and the stage was requested, ``plan.photometric = sample_photometric(3, photo_rng)`` (per-channel
+    parameters for three channels; a grey image uses the first).  Nothing more is drawn from ``rng`` / ``np_rng`` either way.
     A stage whose input is degenerate (markup bounds without width or height, a crop that rounds to an empty window) is
     skipped with a warning and the chain goes on."""
     rng = _random if rng is None else rng
@@ -255,13 +274,157 @@ def sample_plan(image_size, markup, rng=None, np_rng=None):
         coeffs = np_rng.uniform(PERSPECTIVE_MEAN - PERSPECTIVE_HALF, PERSPECTIVE_MEAN + PERSPECTIVE_HALF).tolist()
         push(Stage("perspective", {"coeffs": coeffs}, cur))
     photometric = rng.random() < PHOTOMETRIC_P
+    if photometric and photo_rng is not None:
+        return AugmentationPlan(size, tuple(stages), False, True, sample_photometric(3, photo_rng))
     return AugmentationPlan(size, tuple(stages), False, bool(photometric))
+
+
+# ---------------------------------------------------------------------------------------------------------- photometric
+# the 13 top-level entries of the reference's iaa.SomeOf (augmentation.py:290-327), in its list order
+PHOTO_ENTRIES = ("blur", "sharpen", "emboss", "edge_detect", "noise", "dropout", "invert", "add", "hue_saturation", "multiply",
+                 "contrast", "grayscale", "elastic")
+PHOTO_UNBUILT = ("MedianBlur", "SimplexNoiseAlpha", "AddToHueAndSaturation", "FrequencyNoiseAlpha", "ElasticTransformation")
+PHOTO_POINTWISE = (_lib.UBD_PHOTO_AFFINE, _lib.UBD_PHOTO_GREY, _lib.UBD_PHOTO_NOISE, _lib.UBD_PHOTO_DROPOUT)
+
+
+def sample_photometric(channels, gen):
+    """The draws of the reference's imgaug stage (augmentation.py:280-330) from ``gen``, a ``numpy.random.Generator``: a tuple of
+    ``Stage``s (``size`` None) in the order they are applied.  Order of the draws: ``n = gen.integers(0, 6)``;
+    ``gen.permutation(13)[:n]`` over ``PHOTO_ENTRIES`` (SomeOf((0, 5)), random_order=True); per chosen entry its parameters in
+    the order the reference lists them (a parameter that may be per channel: ``channels`` values), then the ``per_channel``
+    coin (``gen.random() < 0.5``) where the reference has ``per_channel=0.5``, then a 64-bit seed for noise / dropout.  The blur
+    entry first draws ``gen.integers(0, 3)`` (gaussian / average / median), the multiply entry ``gen.integers(0, 2)`` (Multiply /
+    FrequencyNoiseAlpha), the elastic entry its ``sometimes`` coin.  A draw that lands on an operation that is not built
+    (``PHOTO_UNBUILT``) gives ``Stage("unbuilt", {"name": ...}, None)``: recorded, no pixels change, so the built operations
+    occur as often as in the reference.  The stream is numpy's, not imgaug's."""
+    c = int(channels)
+
+    def per_channel(values):
+        values = tuple(values)
+        shared = not gen.random() < 0.5
+        return (values[:1] * c if shared else values), not shared
+
+    def seed():
+        return int(gen.integers(0, 2 ** 64, dtype=np.uint64))
+
+    n = int(gen.integers(0, 6))
+    stages = []
+    for e in gen.permutation(len(PHOTO_ENTRIES))[:n].tolist():
+        name = PHOTO_ENTRIES[e]
+        if name == "blur":
+            which = int(gen.integers(0, 3))
+            if which == 0:
+                st = ("gaussian_blur", {"sigma": float(gen.uniform(0.0, 3.0))})
+            elif which == 1:
+                st = ("average_blur", {"k": int(gen.integers(2, 8))})
+            else:
+                st = ("unbuilt", {"name": "MedianBlur"})
+        elif name == "sharpen":
+            st = ("sharpen", {"alpha": float(gen.uniform(0.0, 1.0)), "lightness": float(gen.uniform(0.75, 1.5))})
+        elif name == "emboss":
+            st = ("emboss", {"alpha": float(gen.uniform(0.0, 1.0)), "strength": float(gen.uniform(0.0, 2.0))})
+        elif name == "edge_detect":
+            st = ("unbuilt", {"name": "SimplexNoiseAlpha"})
+        elif name == "noise":
+            scale = float(gen.uniform(0.0, 0.05 * 255))
+            st = ("noise", {"scale": scale, "per_channel": bool(gen.random() < 0.5), "seed": seed()})
+        elif name == "dropout":
+            p = float(gen.uniform(0.01, 0.1))
+            st = ("dropout", {"p": p, "per_channel": bool(gen.random() < 0.5), "seed": seed()})
+        elif name == "invert":                                            # Invert(0.05, per_channel=True): one coin per channel
+            st = ("invert", {"channels": tuple(bool(v) for v in gen.random(c) < 0.05)})
+        elif name == "add":
+            values, pc = per_channel(int(v) for v in gen.integers(-10, 11, size=c))
+            st = ("add", {"values": values, "per_channel": pc})
+        elif name == "hue_saturation":
+            st = ("unbuilt", {"name": "AddToHueAndSaturation"})
+        elif name == "multiply":
+            if int(gen.integers(0, 2)) == 0:
+                factors, pc = per_channel(float(v) for v in gen.uniform(0.5, 1.5, size=c))
+                st = ("multiply", {"factors": factors, "per_channel": pc})
+            else:
+                st = ("unbuilt", {"name": "FrequencyNoiseAlpha"})
+        elif name == "contrast":
+            alphas, pc = per_channel(float(v) for v in gen.uniform(0.5, 2.0, size=c))
+            st = ("contrast", {"alphas": alphas, "per_channel": pc})
+        elif name == "grayscale":
+            st = ("grayscale", {"alpha": float(gen.uniform(0.0, 1.0))})
+        else:                                                             # sometimes(ElasticTransformation): Sometimes(0.5, ...)
+            st = ("unbuilt", {"name": "ElasticTransformation", "applied": bool(gen.random() < 0.5)})
+        st[1]["entry"] = e
+        stages.append(Stage(st[0], st[1], None))
+    return tuple(stages)
+
+
+def gaussian_taps(sigma):
+    """(radius, Q14 weights at distance 0..radius) of GaussianBlur(sigma): kernel width max(5, int(3.3 sigma)), odd; the float64
+    weights exp(-x^2 / 2 sigma^2) normalised, quantised to Q14, the centre adjusted so that all taps sum to 16384"""
+    k = max(5, int(3.3 * sigma))
+    k += 1 - k % 2
+    r = k // 2
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    wts = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    q = np.rint(wts / wts.sum() * 16384.0).astype(np.int64)
+    q[r] += 16384 - int(q.sum())
+    return r, [int(v) for v in q[r:]]
+
+
+def photometric_descs(stage, w, h, c):
+    """The integer descriptor fields of one photometric stage for a w x h image of c channels (layout: ubd_photo_desc in
+    include/ubd.h): {"mode", "flags", "seed", "p"} -- or None when the stage launches nothing: an unbuilt operation, Grayscale
+    of a grey image, a blur with sigma < 1e-3.  Pure host code."""
+    kind, q = stage.kind, stage.params
+    c = int(c)
+
+    def desc(mode, p, flags=0, seed=0):
+        return {"mode": mode, "flags": int(flags), "seed": int(seed), "p": [int(v) for v in p]}
+
+    def affine(ms, as_):
+        ms, as_ = list(ms)[:c], list(as_)[:c]
+        return desc(_lib.UBD_PHOTO_AFFINE, ms + [65536] * (3 - c) + as_ + [0] * (3 - c))
+
+    def filter3(alpha, e):
+        k = (1.0 - alpha) * np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], np.float64) + alpha * np.array(e, np.float64)
+        return desc(_lib.UBD_PHOTO_FILTER3, np.rint(k * 16384.0).astype(np.int64).reshape(-1))
+
+    if kind == "unbuilt":
+        return None
+    if kind == "invert":
+        return affine([-65536 if v else 65536 for v in q["channels"]], [255 * 65536 if v else 0 for v in q["channels"]])
+    if kind == "add":
+        return affine([65536] * 3, [int(v) * 65536 for v in q["values"]])
+    if kind == "multiply":
+        return affine([int(np.rint(f * 65536.0)) for f in q["factors"]], [0] * 3)
+    if kind == "contrast":
+        return affine([int(np.rint(a * 65536.0)) for a in q["alphas"]], [int(np.rint(128.0 * (1.0 - a) * 65536.0)) for a in q["alphas"]])
+    if kind == "grayscale":
+        return None if c == 1 else desc(_lib.UBD_PHOTO_GREY, [int(np.rint(q["alpha"] * 16384.0))])
+    if kind == "sharpen":
+        return filter3(q["alpha"], [[-1, -1, -1], [-1, 8 + q["lightness"], -1], [-1, -1, -1]])
+    if kind == "emboss":
+        s = q["strength"]
+        return filter3(q["alpha"], [[-1 - s, -s, 0], [-s, 1, s], [0, s, 1 + s]])
+    if kind == "gaussian_blur":
+        if q["sigma"] < 1e-3:
+            return None
+        r, wts = gaussian_taps(q["sigma"])
+        return desc(_lib.UBD_PHOTO_SEP, [r] + wts)
+    if kind == "average_blur":
+        return desc(_lib.UBD_PHOTO_BOX, [q["k"]])
+    if kind == "noise":
+        return desc(_lib.UBD_PHOTO_NOISE, [int(np.array([q["scale"]], np.float32).view(np.int32)[0])], q["per_channel"], q["seed"])
+    if kind == "dropout":
+        thr = int(math.floor(q["p"] * 4294967296.0))
+        return desc(_lib.UBD_PHOTO_DROPOUT, [thr - (1 << 32) if thr >= (1 << 31) else thr], q["per_channel"], q["seed"])
+    raise ValueError(f"unknown photometric stage kind {kind!r}")
 
 
 # --------------------------------------------------------------------------------------------------------------- device
 WARP_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("src_xpitch", np.int32), ("src_ypitch", np.int32),
                       ("src_w", np.int32), ("src_h", np.int32), ("dst_w", np.int32), ("dst_h", np.int32), ("mode", np.int32),
                       ("reserved", np.int32), ("coeffs", np.float64, (8,))], align=True)      # ubd_warp_desc of include/ubd.h
+PHOTO_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("w", np.int32), ("h", np.int32), ("mode", np.int32),
+                       ("flags", np.int32), ("seed", np.uint64), ("p", np.int32, (24,))], align=True)   # ubd_photo_desc
 
 
 class _View:
@@ -270,6 +433,10 @@ class _View:
 
     def __init__(self, ptr, w, h, c, keep):
         self.ptr, self.xp, self.yp, self.w, self.h, self.c, self.keep = int(ptr), c, w * c, int(w), int(h), c, keep
+
+    def rebind(self, ptr, w, h, keep):
+        """the view becomes the packed w x h image at ptr, kept alive by ``keep``"""
+        self.__init__(ptr, w, h, self.c, keep)
 
     def packed(self):
         return self.xp == self.c and self.yp == self.w * self.c
@@ -325,7 +492,7 @@ def _warp_pass(jobs, c, device):
         _lib.check(lib.ubd_warp_images(ctypes.c_void_p(base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data, c, len(jobs),
                                        stream), "ubd_warp_images")
     for k, (v, _, _, (dw, dh)) in enumerate(jobs):
-        v.__init__(out.data_ptr() + starts[k], dw, dh, c, out)
+        v.rebind(out.data_ptr() + starts[k], dw, dh, out)
 
 
 def warp_views_on_device(views, plans, device):
@@ -374,6 +541,57 @@ def warp_views_on_device(views, plans, device):
     return views
 
 
+def _photometric_pass(jobs, c, device):
+    """One ubd_photometric_images call: jobs = [(view, descriptor fields, in_place)].  In-place images (pointwise modes on pixels
+    this module owns) keep their views; the others are written to one new device buffer and their views replaced."""
+    lib = _lib.load()
+    starts, pos = [], 0
+    for v, _, in_place in jobs:
+        starts.append(None if in_place else pos)
+        if not in_place:
+            pos += (v.w * v.h * c + 255) & ~255                   # every image on a 256-byte boundary: dword stores
+    out = torch.empty(max(pos, 1), dtype=torch.uint8, device=device)
+    size = [v.w * v.h * c for v, _, _ in jobs]
+    dsts = [v.ptr if st is None else out.data_ptr() + st for (v, _, _), st in zip(jobs, starts)]
+    src_base = min(v.ptr for v, _, _ in jobs)
+    src_bytes = max(v.ptr + n for (v, _, _), n in zip(jobs, size)) - src_base
+    dst_base = min(dsts)
+    dst_bytes = max(d + n for d, n in zip(dsts, size)) - dst_base
+    descs = np.zeros(len(jobs), PHOTO_DESC)
+    for k, (v, f, _) in enumerate(jobs):
+        d = descs[k]
+        d["src_offset"], d["dst_offset"], d["w"], d["h"] = v.ptr - src_base, dsts[k] - dst_base, v.w, v.h
+        d["mode"], d["flags"], d["seed"] = f["mode"], f["flags"], f["seed"]
+        d["p"][:len(f["p"])] = f["p"]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(lib.ubd_photometric_images(ctypes.c_void_p(src_base), src_bytes, ctypes.c_void_p(dst_base), dst_bytes,
+                                              descs.ctypes.data, c, len(jobs), stream), "ubd_photometric_images")
+    for (v, _, _), st in zip(jobs, starts):
+        if st is not None:
+            v.rebind(out.data_ptr() + st, v.w, v.h, out)
+
+
+def photometric_views_on_device(views, plans, owned, device):
+    """Runs ``plan.photometric`` of every image on its packed view, slot by slot: one ubd_photometric_images call per slot over
+    the images that have a built stage there.  Pointwise stages run in place, neighbourhood stages go to a new buffer that is
+    swapped in; a view whose pixels are not this module's (``owned[k]`` false: a caller's tensor that no warp pass copied) is
+    never written: its first stage goes to a new buffer.  Stream-ordered, no host synchronisation."""
+    c = views[0].c
+    owned = list(owned)
+    chains = [() if plan.original else tuple(plan.photometric) for plan in plans]
+    for slot in range(max((len(ch) for ch in chains), default=0)):
+        jobs = []
+        for k, (v, ch) in enumerate(zip(views, chains)):
+            f = photometric_descs(ch[slot], v.w, v.h, c) if slot < len(ch) else None
+            if f is not None:
+                jobs.append((v, f, owned[k] and f["mode"] in PHOTO_POINTWISE))
+                owned[k] = True
+        if jobs:
+            _photometric_pass(jobs, c, device)
+    return views
+
+
 def _view_tensor(v):
     """the (h, w, c) uint8 tensor of a packed view"""
     off = v.ptr - v.keep.data_ptr()
@@ -382,8 +600,10 @@ def _view_tensor(v):
 
 def augment_arrays_on_device(arrays, plans, device=None):
     """(H, W, C) uint8 images (numpy arrays on the host, staged through one pinned buffer and one transfer, or tensors on the
-    device, read in place; all with the same C of 1 or 3) through their plans -> list of (h, w, C) uint8 device tensors.
-    The photometric stage is not built (module docstring)."""
+    device, read in place and never written; all with the same C of 1 or 3) through their plans -> list of (h, w, C) uint8
+    device tensors: the warp passes, then the photometric stages of ``plan.photometric`` (empty unless the plan was sampled with
+    a ``photo_rng``; skipped for ``plan.original``), slot by slot.  An image without any pass is returned as a view of its
+    source."""
     if not torch.cuda.is_available():
         raise RuntimeError("augmentation on the device needs an MI355X; there is no CPU fallback")
     from .segmap_manager import _stage_host
@@ -405,6 +625,8 @@ def augment_arrays_on_device(arrays, plans, device=None):
         if views[k] is None:
             views[k] = _View(a.data_ptr(), a.shape[1], a.shape[0], c, a)
     warp_views_on_device(views, plans, device)
+    owned = [not isinstance(a, torch.Tensor) or v.keep is not a for a, v in zip(arrays, views)]
+    photometric_views_on_device(views, plans, owned, device)
     return [_view_tensor(v) for v in views]
 
 
@@ -412,18 +634,19 @@ class SegLinksImageAugmentation:
     """The reference's class (augmentation.py:34-91) for one PIL image ('L' or 'RGB') and its markup: draws a plan from the
     ``random`` / ``numpy.random`` modules (or the given generators), runs its geometric chain on the MI355X and returns a PIL
     image of the same mode.  Nothing is drawn and nothing changes for empty markup.  The caller's markup objects are not
-    mutated.  THE PHOTOMETRIC (imgaug) STAGE IS NOT BUILT: ``plan.photometric_requested`` says whether the reference would
-    have run it.  Needs an MI355X (RuntimeError otherwise: no CPU fallback)."""
+    mutated.  The photometric (imgaug) stage runs only with ``photo_rng`` (a ``numpy.random.Generator``; module docstring: the
+    built operations, the unbuilt ones, parity with imgaug / OpenCV unpinned); without it ``plan.photometric_requested`` says
+    whether the reference would have run it.  Needs an MI355X (RuntimeError otherwise: no CPU fallback)."""
 
-    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None):
+    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None):
         if not torch.cuda.is_available():
             raise RuntimeError("SegLinksImageAugmentation needs an MI355X; there is no CPU fallback")
         if image.mode not in ("L", "RGB"):
             raise ValueError(f"image mode must be 'L' or 'RGB', got {image.mode!r}")
         self.__net_config = net_config
-        self.plan = sample_plan(image.size, markup, rng, np_rng) if plan is None else plan
+        self.plan = sample_plan(image.size, markup, rng, np_rng, photo_rng) if plan is None else plan
         self.__aug_image, self.__aug_markup = image, markup
-        if not self.plan.stages:
+        if not self.plan.stages and (self.plan.original or not self.plan.photometric):
             return
         a = np.asarray(image)
         out = augment_arrays_on_device([np.ascontiguousarray(a[:, :, None] if a.ndim == 2 else a)], [self.plan])[0].cpu().numpy()

@@ -15,7 +15,7 @@ print(h.hexdigest()[:16])
 PY
 )
 pids=()
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate evaluate_pixels; do
+for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp photometric evaluate evaluate_pixels; do
   [ -f $f.hip ] || continue
   extra=""
   # OpenCV-exact float geometry: no FMA contraction in postprocess
@@ -26,6 +26,8 @@ for f in api forward fwd16 wino wino6 postprocess loss backward train comm raste
   [ "$f" = "resize" ] && extra="-ffp-contract=off"
   # Pillow-exact double arithmetic of the generic transform and its bilinear filter: no FMA contraction
   [ "$f" = "warp" ] && extra="-ffp-contract=off"
+  # fp32 Box-Muller of the noise mode, product and sum rounded separately as the numpy oracle does: no FMA contraction
+  [ "$f" = "photometric" ] && extra="-ffp-contract=off"
   # exact fp64 cross products of the evaluation geometry (collinearity tests compare them with 0): no FMA contraction
   [ "$f" = "evaluate" ] && extra="-ffp-contract=off"
   # no SLP packing of adjacent fp32 adds into v_pk_add_f32: beside MFMAs the packed form issues slower than two scalar adds
@@ -47,7 +49,7 @@ for f in api forward fwd16 wino wino6 postprocess loss backward train comm raste
 done
 for p in "${pids[@]}"; do wait $p; done
 objs=""
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp evaluate evaluate_pixels; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
+for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp photometric evaluate evaluate_pixels; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
 echo "$BUILD_ID" > _obj/api.build_id
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs -ldl
 echo "built $OUT"
