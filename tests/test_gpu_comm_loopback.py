@@ -331,7 +331,7 @@ def test_eight_ranks_broadcast_from_a_non_zero_root(loopback):
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_fused_step_ordering_matches_the_explicit_all_reduce_step_by_step(loopback, monkeypatch, world):
-    """Cross-stream ordering of the fused data-parallel step (comm.hip / backward.hip): the dilated + head segment is all-reduced on
+    """Cross-stream ordering of the fused data-parallel step (comm.hip / bwd32.hip, bwd16.hip): the dilated + head segment is all-reduced on
     the handle's communication stream under the stem backward (event `ready`: compute -> communication stream; event `done`:
     communication stream -> the caller's stream before Adam).  Reference without any cross-stream edge: the same step with an
     unfused communicator and ONE explicit ubd_allreduce_grads on the caller's stream.  bf16 gradients are bit-reproducible, the

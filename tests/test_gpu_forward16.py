@@ -281,7 +281,7 @@ def test_bf16_dilated_backward_fused_equals_split(monkeypatch, n, hh, ww):
 @pytest.mark.parametrize("n,hh,ww,ncls", [(2, 256, 256, 8), (3, 72, 104, 3), (1, 40, 36, 1), (2, 64, 96, 31)])
 def test_bf16_head_backward_with_classes_in_one_pass_equals_the_two_kernels(monkeypatch, n, hh, ww, ncls):
     """bf16 train step with classes: the head's data gradient G9 is written by the head's weight-gradient kernel from the tile it stages anyway
-    (backward.hip head_wgrad_kernel<TX, true>) instead of by a second pass over A9 (UBD_HEADBWD=split).  Same expression, same order: loss and
+    (bwd_common.h head_wgrad_kernel<TX, true>) instead of by a second pass over A9 (UBD_HEADBWD=split).  Same expression, same order: loss and
     every gradient bit-identical, up to the 31 classes the ABI allows, on ragged maps too."""
     from ubdvss_amd import Trainer, Adam
     cfg = NetConfig(class_names=[f"c{i}" for i in range(ncls)], grey=False)
@@ -421,7 +421,7 @@ def test_bf16_train_fused_stem_equals_split(monkeypatch, n, hh, ww):
 @pytest.mark.parametrize("n,hh,ww,ncls", [(2, 256, 256, 0), (3, 72, 104, 0), (2, 64, 96, 3), (1, 40, 36, 0)])
 def test_bf16_chained_partial_sum_reduction_equals_the_batched_launches(monkeypatch, n, hh, ww, ncls):
     """bf16 train step: every weight-gradient kernel totals, at its end, the per-block partial rows of the producer in front of it
-    (backward.hip rp_reduce_tail; the last producer's rows go to one small stand-alone launch) instead of two batched reduction
+    (bwd_common.h rp_reduce_tail; the last producer's rows go to one small stand-alone launch) instead of two batched reduction
     launches per pass (UBD_REDUCE=batched).  Same rows, same order of additions: loss and gradients are bit-identical."""
     from ubdvss_amd import Trainer, Adam
     cfg = NetConfig(class_names=[f"c{i}" for i in range(ncls)] if ncls else None, grey=False)

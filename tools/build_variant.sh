@@ -10,7 +10,7 @@ extra=""
 [ "$FILE" = "wino6" ] && extra="-fno-slp-vectorize"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-function $extra "$@" -c $FILE.hip -o ../../tools/_ab/_obj_var/$NAME.o
 objs=""
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster; do
+for f in api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster; do
   if [ "$f" = "$FILE" ]; then objs="$objs ../../tools/_ab/_obj_var/$NAME.o"; else objs="$objs _obj/$f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/_ab/$NAME.so $objs -ldl

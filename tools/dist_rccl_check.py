@@ -6,7 +6,7 @@
 
 Per world size, configs[3]'s per-GPU shape (bf16 activations, 64 x 512 x 512 x 3 per rank; DIST_CHECK_BATCH / DIST_CHECK_SIDE shrink it):
   1. CORRECTNESS of the cross-stream ordering over REAL RCCL.  The dilated + head segment of the gradient vector is all-reduced on the
-     handle's communication stream under the stem backward (comm.hip, backward.hip: ubd_comm_begin_tail behind the kernel that makes the
+     handle's communication stream under the stem backward (comm.hip, bwd32.hip / bwd16.hip: ubd_comm_begin_tail behind the kernel that makes the
      segment final, ubd_comm_finish before Adam).  With the bf16 step's fixed-order reductions the summed gradients must be BIT-EQUAL between
        (a) fused communication + chained partial-sum reduction (the default),
        (b) fused communication + UBD_REDUCE=batched,

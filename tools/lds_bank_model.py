@@ -1,4 +1,4 @@
-"""LDS bank model behind the padded tile layouts of sep_bwd_kernel (backward.hip, sepb_cfg): 64 banks of 4 bytes; a ds_read_b64 is served in two
+"""LDS bank model behind the padded tile layouts of sep_bwd_kernel (bwd32.hip, sepb_cfg): 64 banks of 4 bytes; a ds_read_b64 is served in two
 passes of 32 lanes, a ds_read_b32 in one of 64, a ds_read_b128 in four of 16; a pass takes as many cycles as the most-wanted bank has distinct
 dwords.  Lane (i, q) = (lane & 15, lane >> 4) reads three 8-byte pairs at position(pixel i * S + kx) + 6 q + 2 j.  Prints the cycles of the
 nine pair-reads of a 3x3 tap window for pixel strides / pads and the best layouts (ideal: 18).  python tools/lds_bank_model.py"""

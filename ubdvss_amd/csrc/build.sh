@@ -14,8 +14,9 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric evaluate evaluate_pixels"
 pids=()
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp photometric evaluate evaluate_pixels; do
+for f in $UNITS; do
   [ -f $f.hip ] || continue
   extra=""
   # OpenCV-exact float geometry: no FMA contraction in postprocess
@@ -49,7 +50,7 @@ for f in api forward fwd16 wino wino6 postprocess loss backward train comm raste
 done
 for p in "${pids[@]}"; do wait $p; done
 objs=""
-for f in api forward fwd16 wino wino6 postprocess loss backward train comm raster resize warp photometric evaluate evaluate_pixels; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
+for f in $UNITS; do [ -f _obj/$f.o ] && objs="$objs _obj/$f.o"; done
 echo "$BUILD_ID" > _obj/api.build_id
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT $objs -ldl
 echo "built $OUT"

@@ -1,4 +1,4 @@
-// bf16-gradient kernels of the UBD_BF16 train step (included by backward.hip).
+// bf16-gradient kernels of the UBD_BF16 train step (bwd16.hip).
 //
 // BASELINE.json configs[2]/[3] ("bf16 train step"): activations AND the gradient tensors that flow between layers
 // (G = dL/dZ) are stored in bf16, every product is accumulated in fp32, weight gradients / master weights / Adam
@@ -13,6 +13,7 @@
 //   (data gradient)       dilconv16_kernel<T, 1> in fwd16.hip
 //   (separable layers)    sepb16_kernel in sepbwd16.h
 #pragma once
+#include "bwd_common.h"
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -440,5 +441,5 @@ __global__ __launch_bounds__(256, W16_OCC(TW, DX)) void dil_wgrad16_kernel(const
         wgrad_block_reduce(acc, (float *)smem, partials + (size_t)blockIdx.x * (217 * UBD_C), lane, wid);
     }
     __syncthreads();                                   // every wave has left the LDS
-    rp_reduce_tail(prev, (float *)smem);               // the partial rows of the producer in front of this kernel (backward.hip)
+    rp_reduce_tail(prev, (float *)smem);               // the partial rows of the producer in front of this kernel (bwd_common.h)
 }

@@ -153,7 +153,7 @@ int ubd_comm_allgather_u32(ubd_handle *h, const unsigned *send_one, unsigned *re
     return 0;
 }
 
-// ---- hooks of ubd_train_step (backward.hip) with UBD_COMM_FUSED ----------------------------------------------------------
+// ---- hooks of the train step (backward.hip, bwd32.hip, bwd16.hip) with UBD_COMM_FUSED ------------------------------------
 bool ubd_comm_fused(const ubd_handle *h) { return h->comm && (h->comm->flags & UBD_COMM_FUSED); }
 
 // the dilated + head gradients [off_dil_k[0], n_params) are final: reduce them on the communication stream

@@ -1,6 +1,6 @@
-// Weight repacking shared by forward.hip, fwd16.hip and backward.hip: flat Keras-ordered parameters -> per-lane MFMA fragments.
+// Weight repacking shared by forward.hip, fwd16.hip, bwd32.hip and bwd16.hip: flat Keras-ordered parameters -> per-lane MFMA fragments.
 // Every packer is a device function over a VIRTUAL thread grid (vtid of vthreads), so that the stand-alone kernels and the
-// one-launch prologue of the bf16 train step (backward.hip train_prologue16_kernel: four packers + the zeroing of the gradient
+// one-launch prologue of the bf16 train step (bwd16.hip train_prologue16_kernel: four packers + the zeroing of the gradient
 // vector and of the loss scratch in ONE launch instead of six ~5-us launches) run the same code.
 #pragma once
 #include "common.h"

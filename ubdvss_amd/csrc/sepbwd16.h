@@ -1,6 +1,6 @@
-// Separable-layer backward of the UBD_BF16 train step (included by backward.hip after sep_bwd_kernel).
+// Separable-layer backward of the UBD_BF16 train step (bwd16.hip).
 //
-// Same math as sep_bwd_kernel + sep_dx_kernel, but the gradient tensor G = dL/dZ of layers L1 and L2 is never written
+// Same math as sep_bwd_kernel + sep_dx_kernel (bwd32.hip), but the gradient tensor G = dL/dZ of layers L1 and L2 is never written
 // to memory: the kernel of layer L builds its G tile in LDS from the depthwise-output gradient dDW of the layer ABOVE
 // (a 3x3 depthwise transposed convolution, masked with L's saved output), then runs the usual per-tile work.
 // dDW tensors are stored in bf16.  Per 64-image batch this removes the G1/G2 round trips (2 x 403 MB written and
@@ -30,6 +30,7 @@
 // ds_read_b64_tr_b16 (as dil_wgrad16_kernel), an all-ones column gives the bias gradient; the depthwise-kernel gradient
 // (24 channels) as the diagonals of X_t^T dDW, 14 MFMAs per k-block whose accumulators are owned by waves (see M2 below).
 #pragma once
+#include "bwd16.h"
 
 // NW = waves per block: the 1/3-channel layer needs few registers, so 6 waves share one tile's LDS (3 waves per SIMD at two
 // blocks per CU); the 24-channel layers hold 54 + 16 accumulators per lane and run 4 waves per block.
@@ -856,5 +857,5 @@ __global__ __launch_bounds__(256, (sepb16_cfg<CIN, STRIDE, GSRC, IN_MODE == 2>::
     float *prow = partials + (size_t)blockIdx.x * C::PART;
     for (int t = threadIdx.x; t < C::PART; t += blockDim.x) prow[t] = red[t];
     __syncthreads();                                   // the LDS image is free
-    rp_reduce_tail(prev, (float *)lds);                // the partial rows of the producer in front of this kernel (backward.hip)
+    rp_reduce_tail(prev, (float *)lds);                // the partial rows of the producer in front of this kernel (bwd_common.h)
 }

@@ -1,5 +1,5 @@
 // Training path of the ubdvss hot path on gfx950: fused loss, backward, Adam.
-// Adam update (loss: loss.hip; backward + train step: backward.hip).
+// Adam update (loss: loss.hip; train step: backward.hip; its backward passes: bwd32.hip, bwd16.hip).
 #include "common.h"
 
 __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
