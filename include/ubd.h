@@ -205,7 +205,8 @@ int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t d
                     int channels, int n, void *stream);
 
 /* --- photometric augmentation ---------------------------------------------------
- * The built part of the reference's imgaug stage (augmentation.py:276-332), one operation ("stage") per image per call, for n
+ * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one
+ * operation ("stage") per image per call, for n
  * uint8 images of `channels` (1 or 3) channels with packed rows (pitch w * channels), every image with its own size, at
  * src + src_offset, written at dst + dst_offset.  imgaug and OpenCV are not available to pin against: every mode is DEFINED in
  * integer arithmetic here (each follows imgaug's published formula) and the device matches the numpy oracle of the tests bit for
@@ -223,27 +224,64 @@ int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t d
  *                     out = (2 S + k k) / (2 k k)
  *   UBD_PHOTO_NOISE   (AdditiveGaussianNoise): p[0] = the bits of the fp32 scale (finite, >= 0); flags bit 0 = per channel
  *   UBD_PHOTO_DROPOUT (Dropout): p[0] = the bits of the uint32 threshold floor(p 2^32); flags bit 0 = per channel
- * Random words of NOISE / DROPOUT: Philox4x32-10, key = seed (lo, hi), counter = (y w + x, 0, j, 0); block j = 0 gives r0..r3,
+ *   UBD_PHOTO_MEDIAN = 16 (MedianBlur): p[0] = k, odd, 3..11; per channel, out = the median of the k x k window centred on the
+ *                     pixel = element (k k - 1) / 2 of its sorted k k values.  Coordinates outside the image are CLAMPED TO THE
+ *                     EDGE (OpenCV's medianBlur documents BORDER_REPLICATE) -- not the reflect-101 of the other neighbourhood modes
+ *   UBD_PHOTO_HSV = 17 (AddToHueAndSaturation): 3 channels only; p[0] = dh, p[1] = ds, each -255..255.  All int32, `/` truncates
+ *                     (its operands are never negative).  Forward, OpenCV's 8-bit RGB -> HSV (H 0..179) with its Q12 reciprocal
+ *                     tables: V = max(R,G,B), m = min(R,G,B), D = V - m; sdiv(i) = (2088960 + i) / (2 i), hdiv(i) =
+ *                     (245760 + i) / (2 i) for i >= 1, both 0 for i = 0 (= rint((255 << 12) / i), rint((180 << 12) / (6 i)));
+ *                     S = (D sdiv(V) + 2048) >> 12; hn = G - B if V = R, else B - R + 2 D if V = G, else R - G + 4 D (the first
+ *                     case that matches); H = (hn hdiv(D) + 2048) >> 12, H += 180 if H < 0.  Shift: H' = (H + dh) mod 180
+ *                     (0..179), S' = clamp(S + ds, 0, 255), V unchanged.  Backward: i = H' / 30, f = H' - 30 i,
+ *                     P = (30 V (255 - S') + 3825) / 7650, Q = (V (7650 - S' f) + 3825) / 7650,
+ *                     T = (V (7650 - S' (30 - f)) + 3825) / 7650; (R,G,B) by sector i = 0..5: (V,T,P), (Q,V,P), (P,V,T), (P,Q,V),
+ *                     (T,P,V), (V,P,Q).  Over all 2^24 colours H stays in 0..179 and S in 0..255, the largest product is
+ *                     1 044 582; dh = ds = 0 is NOT the identity (8-bit HSV loses up to 5 levels).  Design decision: imgaug of the
+ *                     reference's era adds one value to the H and S channels and CLIPS H at 0..255; later imgaug wraps the hue.
+ *                     This mode wraps.
+ *   UBD_PHOTO_ELASTIC = 18 (ElasticTransformation): p[0] = aq = rint(256 alpha), 0..4096; p[1] = w0, p[2] = w1: the Q14 taps of
+ *                     the 3-tap Gaussian that smooths the displacement field, each >= 0, w0 + 2 w1 = 16384; seed = the Philox key.
+ *                     Raw field of a pixel inside the image, from the words of counter (y w + x, 0, 0, 0):
+ *                     ex = (r0 >> 16) - 32768, ey = (r1 >> 16) - 32768 (Q15 in (-1, 1)); outside the image both are 0 (imgaug's
+ *                     gaussian_filter(mode="constant", cval=0)).  Smoothing, for ex and ey alike: rows
+ *                     t = (w1 e(x-1) + w0 e(x) + w1 e(x+1) + 8192) >> 14, then columns s = (w1 t(y-1) + w0 t(y) + w1 t(y+1) + 8192)
+ *                     >> 14 with t = 0 for a row outside the image; every sum stays below 2^30.  Displacement in 1/32 pixel:
+ *                     d = (aq s + 2^17) >> 18 (|aq s| <= 2^27, so at most 16 pixels).  Source position X = 32 x + dx,
+ *                     Y = 32 y + dy; ix = X >> 5, kx = X & 31, likewise for y: output (x, y) samples the input at (x + dx, y + dy).
+ *                     Interpolation: Keys' bicubic with a = -3/4 at 1/32-pixel phases (cv2.remap's INTER_CUBIC), exact integer
+ *                     weights in Q17: W0 = -3 k (32 - k)^2, W1 = 5 k^3 - 288 k^2 + 131072, W2 = W1 at 32 - k, W3 = -3 (32 - k) k^2
+ *                     (they sum to 131072) on the taps ix - 1 .. ix + 2; a tap outside the image contributes 0 (constant border).
+ *                     out = clamp((sum_j sum_i Wy_j Wx_i v(ix-1+i, iy-1+j) + 2^33) >> 34), exact: a row's inner sum stays below
+ *                     2^26 (int32), the four outer products are int64.  All channels share one displacement.  aq = 0 is the
+ *                     identity; a constant image stays constant wherever all 16 taps are inside.  Design decision: imgaug of the
+ *                     reference's era interpolates with a scipy cubic spline; this mode follows the later cv2 path, which is
+ *                     defined without a whole-row prefilter.
+ * Random words of NOISE / DROPOUT / ELASTIC: Philox4x32-10, key = seed (lo, hi), counter = (y w + x, 0, j, 0); block j = 0 gives r0..r3,
  * j = 1 gives r4..r7.  DROPOUT: 0 where the word < threshold; channel c tests r_c per channel, else every channel tests r0.
  * NOISE: u1 = ((a >> 9) + 0.5) 2^-23, u2 likewise from b, z = sqrt(-2 ln u1) cos(2 pi u2) in fp32, out = clamp(rint(v + scale z));
  * (a, b) = (r_2c, r_2c+1) per channel, else (r0, r1).
- * The pointwise modes (AFFINE, GREY, NOISE, DROPOUT) may run in place (same address for source and destination of an image);
- * any other overlap of an image's source and destination is refused, for the neighbourhood modes (FILTER3, SEP, BOX) every one.
+ * The pointwise modes (AFFINE, GREY, NOISE, DROPOUT, HSV) may run in place (same address for source and destination of an image);
+ * any other overlap of an image's source and destination is refused, for the neighbourhood modes (FILTER3, SEP, BOX, MEDIAN,
+ * ELASTIC) every one.
  * descs: HOST array of n descriptors.  Dword loads / stores are used where the addresses allow; any byte alignment works.
  * Limits: sides 1..16384 (so an image stays below 2^31 bytes), n >= 1, channels 1 or 3, ranges inside the two buffers, a known
- * mode, BOX k 2..7, SEP radius 1..4; and the parameter ranges that keep every sum inside int32: AFFINE |m_c| <= 2^17 and
+ * mode (0..6 and 16..18: 7..15 and everything above 18 are refused), BOX k 2..7, SEP radius 1..4, MEDIAN k odd and 3..11, HSV
+ * with 3 channels and |dh|, |ds| <= 255, ELASTIC aq 0..4096 with taps >= 0 and w0 + 2 w1 = 16384; and the parameter ranges that keep every sum inside int32: AFFINE |m_c| <= 2^17 and
  * |a_c| <= 2^24 (all three channels' entries are checked), GREY aq 0..16384, FILTER3 |tap| <= 13 * 16384, SEP weights 0..16384
  * whose 2r + 1 taps sum to 16384, NOISE scale finite and >= 0 (non-zero return otherwise, nothing launched).
- * Enqueues at most two launches per 32 images; no host synchronisation, capturable in a HIP graph.
- * Not built (they need OpenCV's 8-bit HSV or imgaug's noise-mask generators): MedianBlur, SimplexNoiseAlpha(EdgeDetect /
- * DirectedEdgeDetect), AddToHueAndSaturation, FrequencyNoiseAlpha, ElasticTransformation. */
-enum { UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE, UBD_PHOTO_DROPOUT };
+ * Enqueues at most four launches per 32 images (one kernel each for the pointwise modes, for FILTER3 / SEP / BOX, for MEDIAN and
+ * for ELASTIC; a kernel whose modes do not occur is not launched); no host synchronisation, capturable in a HIP graph.
+ * Not built (they need imgaug's simplex / frequency noise-mask generators and its cv2 mask upscaling): SimplexNoiseAlpha(EdgeDetect
+ * / DirectedEdgeDetect) and FrequencyNoiseAlpha. */
+enum { UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE, UBD_PHOTO_DROPOUT,
+       UBD_PHOTO_MEDIAN = 16, UBD_PHOTO_HSV = 17, UBD_PHOTO_ELASTIC = 18 };
 typedef struct ubd_photo_desc {
     int64_t src_offset, dst_offset;  /* bytes from src / dst to the image */
     int32_t w, h;
     int32_t mode;                    /* UBD_PHOTO_* */
     int32_t flags;                   /* bit 0: per channel (NOISE, DROPOUT) */
-    uint64_t seed;                   /* Philox key (NOISE, DROPOUT) */
+    uint64_t seed;                   /* Philox key (NOISE, DROPOUT, ELASTIC) */
     int32_t p[24];                   /* per mode, see above; unused entries 0 */
 } ubd_photo_desc;
 int ubd_photometric_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes,

@@ -13,7 +13,8 @@ The photometric stage is not part of either side of the end-to-end legs (the pla
   --photometric: instead of the legs above, HIP-event time of one ubd_photometric_images call per mode over 16 x 1080 x 1920 RGB
     frames (median of --iters), source and destination in separate buffers, next to the bytes-moved bound of a stage,
     2 x image bytes (read once, written once), and the GB/s those bytes are in that time.
-Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5] [--photometric]
+    The legs: every mode, MEDIAN at k = 3 and 11, HSV, ELASTIC at alpha = 3.5 (--only NAME[,NAME]: just those legs).
+Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5] [--photometric [--only median_k11]]
 """
 import argparse
 import concurrent.futures as cf
@@ -66,7 +67,7 @@ def kernel_leg(name, n, h, w, c, mode, coeffs, dst_size, iters):
             "MB_moved": round(gb * 1e3, 1), "TBps": round(gb / us * 1e3, 3), "fraction_of_8TBps": round(gb / us * 1e3 / HBM_TBS, 3)}
 
 
-def photometric_legs(iters, n=16, h=1080, w=1920, c=3):
+def photometric_legs(iters, n=16, h=1080, w=1920, c=3, only=None):
     lib = _lib.load()
     St = aug.Stage
     stages = [("affine_contrast", St("contrast", {"alphas": (1.7, 0.6, 1.2), "per_channel": True}, None)),
@@ -78,7 +79,13 @@ def photometric_legs(iters, n=16, h=1080, w=1920, c=3):
               ("box_k7", St("average_blur", {"k": 7}, None)),
               ("noise_shared", St("noise", {"scale": 6.0, "per_channel": False, "seed": 1}, None)),
               ("noise_per_channel", St("noise", {"scale": 6.0, "per_channel": True, "seed": 1}, None)),
-              ("dropout_per_channel", St("dropout", {"p": 0.05, "per_channel": True, "seed": 2}, None))]
+              ("dropout_per_channel", St("dropout", {"p": 0.05, "per_channel": True, "seed": 2}, None)),
+              ("median_k3", St("median_blur", {"k": 3}, None)),
+              ("median_k11", St("median_blur", {"k": 11}, None)),
+              ("hsv", St("hue_saturation", {"value": 12}, None)),
+              ("elastic_alpha3.5", St("elastic", {"applied": True, "alpha": 3.5, "sigma": 0.25, "seed": 3}, None))]
+    if only:
+        stages = [(name, st) for name, st in stages if name in only]
     per = h * w * c
     src = torch.randint(0, 256, (n * per,), dtype=torch.uint8, device="cuda")
     dst = torch.empty(n * per, dtype=torch.uint8, device="cuda")
@@ -172,10 +179,11 @@ def main():
     ap.add_argument("--e2e-iters", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--photometric", action="store_true", help="time ubd_photometric_images per mode instead of the warp / end-to-end legs")
+    ap.add_argument("--only", default="", help="with --photometric: comma-separated leg names (e.g. median_k11), for a profiler run of one leg")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.photometric:
-        for leg in photometric_legs(args.iters):
+        for leg in photometric_legs(args.iters, only=[v for v in args.only.split(",") if v]):
             print(json.dumps(leg), flush=True)
         return
     _, matrix, size = aug.rotate_matrix_and_size(31.7, (1920, 1080))

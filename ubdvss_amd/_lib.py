@@ -17,6 +17,7 @@ ABI_VERSION = 3
 UBD_WARP_COPY, UBD_WARP_AFFINE, UBD_WARP_PERSPECTIVE = 0, 1, 2
 (UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE,
  UBD_PHOTO_DROPOUT) = range(7)
+UBD_PHOTO_MEDIAN, UBD_PHOTO_HSV, UBD_PHOTO_ELASTIC = 16, 17, 18
 UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS = 8, 256, 256, 16
 UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
 UBD_MAX_CLASSES = 31

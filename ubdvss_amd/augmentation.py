@@ -12,12 +12,16 @@ The photometric (imgaug) stage (augmentation.py:83-84, :276-332: ``iaa.SomeOf((0
 after the warps, on the device, when the caller hands ``sample_plan`` a generator for it (``photo_rng``; imgaug keeps its own
 generator too): ``sample_photometric`` draws up to five stages, ``photometric_descs`` turns a stage into the integer descriptor
 of ``ubd_photometric_images`` (csrc/photometric.hip), ``augment_arrays_on_device`` runs them slot by slot.  Built: GaussianBlur,
-AverageBlur, Sharpen, Emboss, AdditiveGaussianNoise, Dropout, Invert, Add, Multiply, ContrastNormalization, Grayscale.
-NOT BUILT (drawn as often as in the reference, recorded as ``Stage("unbuilt", {"name": ...})``, no pixel changes): MedianBlur,
-SimplexNoiseAlpha(EdgeDetect / DirectedEdgeDetect), AddToHueAndSaturation, FrequencyNoiseAlpha, ElasticTransformation -- they
-need OpenCV's 8-bit HSV or imgaug's noise-mask generators.  imgaug and OpenCV are not available to compare with: each built
-operation follows imgaug's published formula in integer arithmetic DEFINED by include/ubd.h and tests/photometric_oracle.py,
-which the device matches bit for bit; PARITY WITH imgaug / cv2 IS UNPINNED, and the random stream is numpy's, not imgaug's.
+AverageBlur, Sharpen, Emboss, AdditiveGaussianNoise, Dropout, Invert, Add, Multiply, ContrastNormalization, Grayscale; and,
+drawn only with ``extended=True`` / ``photo_extended=True`` (``PHOTO_EXTENDED``; off by default, so every earlier plan and
+stream stays as it was): MedianBlur, AddToHueAndSaturation (the hue wraps; imgaug of the reference's era clips it) and
+ElasticTransformation (cv2.remap's bicubic; imgaug of the reference's era uses a scipy spline).  Without the flag these three
+are recorded as ``Stage("unbuilt", {"name": ...})`` and change no pixel.
+NOT BUILT (drawn as often as in the reference, always recorded as ``unbuilt``, no pixel changes): SimplexNoiseAlpha(EdgeDetect /
+DirectedEdgeDetect) and FrequencyNoiseAlpha -- they need imgaug's noise-mask generators.  imgaug and OpenCV are not available to
+compare with: each built operation follows the libraries' published behaviour in integer arithmetic DEFINED by include/ubd.h,
+tests/photometric_oracle.py and tests/photometric_ext_oracle.py, which the device matches bit for bit; PARITY WITH imgaug / cv2
+IS UNPINNED, and the random stream is numpy's, not imgaug's.
 Without ``photo_rng`` the stage's decision draw is consumed, the plan records it (``photometric_requested``) and the pixels
 are left as the geometric chain made them.
 Flips have probability 0 in the reference: their draws are consumed, they are never applied.
@@ -39,7 +43,8 @@ from . import _lib
 # photometric stages (size None; every params has 'entry', the index into PHOTO_ENTRIES; per-channel parameters are 3-tuples):
 # 'gaussian_blur' {sigma}, 'average_blur' {k}, 'sharpen' {alpha, lightness}, 'emboss' {alpha, strength},
 # 'noise' {scale, per_channel, seed}, 'dropout' {p, per_channel, seed}, 'invert' {channels}, 'add' {values, per_channel},
-# 'multiply' {factors, per_channel}, 'contrast' {alphas, per_channel}, 'grayscale' {alpha}, 'unbuilt' {name}
+# 'multiply' {factors, per_channel}, 'contrast' {alphas, per_channel}, 'grayscale' {alpha}, 'unbuilt' {name};
+# drawn only with extended=True: 'median_blur' {k}, 'hue_saturation' {value}, 'elastic' {applied, sigma; alpha, seed when applied}
 Stage = collections.namedtuple("Stage", ["kind", "params", "size"])
 # size: (w, h) of the source image; original: the 10 % "feed the original" branch was taken (no further draws);
 # photometric_requested: the reference would have run its imgaug stage here; photometric: that stage's operations, drawn only
@@ -224,7 +229,7 @@ def _sample_crop(boxes, size, rng):
     return Stage("crop", {"box": box, "window": (x0, y0, x1, y1)}, (x1 - x0, y1 - y0))
 
 
-def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None):
+def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None, photo_extended=False):
     """Draws the parameters of the reference's ``__augment_image`` (augmentation.py:50-85) for one image of ``image_size`` =
     (w, h) and its ``markup`` and returns an ``AugmentationPlan``: the stages with their numbers and the image size after each.
 
@@ -236,8 +241,8 @@ def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None):
     ``random()`` (< 0.7) for the photometric stage: the plan records that it was requested.
     ``rng`` / ``np_rng``: objects with the interface of the ``random`` / ``numpy.random`` modules (the defaults).
     ``photo_rng``: a ``numpy.random.Generator`` for the photometric stage's own draws (imgaug keeps its own generator too);
-    when it is given and the stage was requested, ``plan.photometric = sample_photometric(3, photo_rng)`` (per-channel
-    parameters for three channels; a grey image uses the first).  Nothing more is drawn from ``rng`` / ``np_rng`` either way.
+    when it is given and the stage was requested, ``plan.photometric = sample_photometric(3, photo_rng, photo_extended)``
+    (per-channel parameters for three channels; a grey image uses the first).  Nothing more is drawn from ``rng`` / ``np_rng`` either way.
     A stage whose input is degenerate (markup bounds without width or height, a crop that rounds to an empty window) is
     skipped with a warning and the chain goes on."""
     rng = _random if rng is None else rng
@@ -275,7 +280,7 @@ def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None):
         push(Stage("perspective", {"coeffs": coeffs}, cur))
     photometric = rng.random() < PHOTOMETRIC_P
     if photometric and photo_rng is not None:
-        return AugmentationPlan(size, tuple(stages), False, True, sample_photometric(3, photo_rng))
+        return AugmentationPlan(size, tuple(stages), False, True, sample_photometric(3, photo_rng, photo_extended))
     return AugmentationPlan(size, tuple(stages), False, bool(photometric))
 
 
@@ -284,10 +289,13 @@ def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None):
 PHOTO_ENTRIES = ("blur", "sharpen", "emboss", "edge_detect", "noise", "dropout", "invert", "add", "hue_saturation", "multiply",
                  "contrast", "grayscale", "elastic")
 PHOTO_UNBUILT = ("MedianBlur", "SimplexNoiseAlpha", "AddToHueAndSaturation", "FrequencyNoiseAlpha", "ElasticTransformation")
-PHOTO_POINTWISE = (_lib.UBD_PHOTO_AFFINE, _lib.UBD_PHOTO_GREY, _lib.UBD_PHOTO_NOISE, _lib.UBD_PHOTO_DROPOUT)
+# the three of them that sample_photometric(..., extended=True) draws as stages of their own
+PHOTO_EXTENDED = ("MedianBlur", "AddToHueAndSaturation", "ElasticTransformation")
+PHOTO_POINTWISE = (_lib.UBD_PHOTO_AFFINE, _lib.UBD_PHOTO_GREY, _lib.UBD_PHOTO_NOISE, _lib.UBD_PHOTO_DROPOUT, _lib.UBD_PHOTO_HSV)
+ELASTIC_SIGMA = 0.25
 
 
-def sample_photometric(channels, gen):
+def sample_photometric(channels, gen, extended=False):
     """The draws of the reference's imgaug stage (augmentation.py:280-330) from ``gen``, a ``numpy.random.Generator``: a tuple of
     ``Stage``s (``size`` None) in the order they are applied.  Order of the draws: ``n = gen.integers(0, 6)``;
     ``gen.permutation(13)[:n]`` over ``PHOTO_ENTRIES`` (SomeOf((0, 5)), random_order=True); per chosen entry its parameters in
@@ -296,7 +304,11 @@ def sample_photometric(channels, gen):
     entry first draws ``gen.integers(0, 3)`` (gaussian / average / median), the multiply entry ``gen.integers(0, 2)`` (Multiply /
     FrequencyNoiseAlpha), the elastic entry its ``sometimes`` coin.  A draw that lands on an operation that is not built
     (``PHOTO_UNBUILT``) gives ``Stage("unbuilt", {"name": ...}, None)``: recorded, no pixels change, so the built operations
-    occur as often as in the reference.  The stream is numpy's, not imgaug's."""
+    occur as often as in the reference.  The stream is numpy's, not imgaug's.
+    ``extended``: the three operations of ``PHOTO_EXTENDED`` draw their parameters in place of the ``unbuilt`` stage -- MedianBlur
+    ``k = gen.integers(3, 12)``, an even k becoming k + 1 (imgaug's rule); AddToHueAndSaturation one ``gen.integers(-20, 21)`` for
+    both channels; ElasticTransformation, after its coin and only when applied, ``gen.uniform(0.5, 3.5)`` (alpha) and a 64-bit
+    seed, sigma 0.25.  Every other entry, the count and the permutation draw as without it."""
     c = int(channels)
 
     def per_channel(values):
@@ -317,6 +329,9 @@ def sample_photometric(channels, gen):
                 st = ("gaussian_blur", {"sigma": float(gen.uniform(0.0, 3.0))})
             elif which == 1:
                 st = ("average_blur", {"k": int(gen.integers(2, 8))})
+            elif extended:
+                k = int(gen.integers(3, 12))
+                st = ("median_blur", {"k": k + 1 - k % 2})
             else:
                 st = ("unbuilt", {"name": "MedianBlur"})
         elif name == "sharpen":
@@ -337,7 +352,7 @@ def sample_photometric(channels, gen):
             values, pc = per_channel(int(v) for v in gen.integers(-10, 11, size=c))
             st = ("add", {"values": values, "per_channel": pc})
         elif name == "hue_saturation":
-            st = ("unbuilt", {"name": "AddToHueAndSaturation"})
+            st = ("hue_saturation", {"value": int(gen.integers(-20, 21))}) if extended else ("unbuilt", {"name": "AddToHueAndSaturation"})
         elif name == "multiply":
             if int(gen.integers(0, 2)) == 0:
                 factors, pc = per_channel(float(v) for v in gen.uniform(0.5, 1.5, size=c))
@@ -350,7 +365,13 @@ def sample_photometric(channels, gen):
         elif name == "grayscale":
             st = ("grayscale", {"alpha": float(gen.uniform(0.0, 1.0))})
         else:                                                             # sometimes(ElasticTransformation): Sometimes(0.5, ...)
-            st = ("unbuilt", {"name": "ElasticTransformation", "applied": bool(gen.random() < 0.5)})
+            applied = bool(gen.random() < 0.5)
+            if not extended:
+                st = ("unbuilt", {"name": "ElasticTransformation", "applied": applied})
+            elif applied:
+                st = ("elastic", {"applied": True, "alpha": float(gen.uniform(0.5, 3.5)), "sigma": ELASTIC_SIGMA, "seed": seed()})
+            else:
+                st = ("elastic", {"applied": False, "sigma": ELASTIC_SIGMA})
         st[1]["entry"] = e
         stages.append(Stage(st[0], st[1], None))
     return tuple(stages)
@@ -369,10 +390,21 @@ def gaussian_taps(sigma):
     return r, [int(v) for v in q[r:]]
 
 
+def elastic_taps(sigma):
+    """(w0, w1): the Q14 taps of the 3-tap Gaussian that smooths ElasticTransformation's displacement field, w0 + 2 w1 = 16384.
+    Radius 1 is scipy's ``int(4 sigma + 0.5)``; a sigma that needs a larger radius raises ValueError."""
+    if not sigma > 0 or int(4.0 * sigma + 0.5) != 1:
+        raise ValueError(f"elastic sigma {sigma} needs a filter radius other than 1; only the 3-tap field filter is built")
+    g = math.exp(-1.0 / (2.0 * sigma * sigma))
+    w1 = int(np.rint(16384.0 * g / (1.0 + 2.0 * g)))
+    return 16384 - 2 * w1, w1
+
+
 def photometric_descs(stage, w, h, c):
     """The integer descriptor fields of one photometric stage for a w x h image of c channels (layout: ubd_photo_desc in
     include/ubd.h): {"mode", "flags", "seed", "p"} -- or None when the stage launches nothing: an unbuilt operation, Grayscale
-    of a grey image, a blur with sigma < 1e-3.  Pure host code."""
+    or AddToHueAndSaturation of a grey image, a blur with sigma < 1e-3, an ElasticTransformation whose coin said no.  Pure host
+    code."""
     kind, q = stage.kind, stage.params
     c = int(c)
 
@@ -416,6 +448,14 @@ def photometric_descs(stage, w, h, c):
     if kind == "dropout":
         thr = int(math.floor(q["p"] * 4294967296.0))
         return desc(_lib.UBD_PHOTO_DROPOUT, [thr - (1 << 32) if thr >= (1 << 31) else thr], q["per_channel"], q["seed"])
+    if kind == "median_blur":
+        return desc(_lib.UBD_PHOTO_MEDIAN, [q["k"]])
+    if kind == "hue_saturation":
+        return None if c == 1 else desc(_lib.UBD_PHOTO_HSV, [q["value"], q["value"]])
+    if kind == "elastic":
+        if not q["applied"]:
+            return None
+        return desc(_lib.UBD_PHOTO_ELASTIC, [int(np.rint(256.0 * q["alpha"]))] + list(elastic_taps(q["sigma"])), seed=q["seed"])
     raise ValueError(f"unknown photometric stage kind {kind!r}")
 
 
@@ -574,7 +614,8 @@ def _photometric_pass(jobs, c, device):
 
 def photometric_views_on_device(views, plans, owned, device):
     """Runs ``plan.photometric`` of every image on its packed view, slot by slot: one ubd_photometric_images call per slot over
-    the images that have a built stage there.  Pointwise stages run in place, neighbourhood stages go to a new buffer that is
+    the images that have a built stage there.  Pointwise stages run in place, neighbourhood stages (MEDIAN and ELASTIC among
+    them) go to a new buffer that is
     swapped in; a view whose pixels are not this module's (``owned[k]`` false: a caller's tensor that no warp pass copied) is
     never written: its first stage goes to a new buffer.  Stream-ordered, no host synchronisation."""
     c = views[0].c
@@ -635,16 +676,16 @@ class SegLinksImageAugmentation:
     ``random`` / ``numpy.random`` modules (or the given generators), runs its geometric chain on the MI355X and returns a PIL
     image of the same mode.  Nothing is drawn and nothing changes for empty markup.  The caller's markup objects are not
     mutated.  The photometric (imgaug) stage runs only with ``photo_rng`` (a ``numpy.random.Generator``; module docstring: the
-    built operations, the unbuilt ones, parity with imgaug / OpenCV unpinned); without it ``plan.photometric_requested`` says
+    built operations, those that ``photo_extended`` adds, the unbuilt ones, parity with imgaug / OpenCV unpinned); without it ``plan.photometric_requested`` says
     whether the reference would have run it.  Needs an MI355X (RuntimeError otherwise: no CPU fallback)."""
 
-    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None):
+    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None, photo_extended=False):
         if not torch.cuda.is_available():
             raise RuntimeError("SegLinksImageAugmentation needs an MI355X; there is no CPU fallback")
         if image.mode not in ("L", "RGB"):
             raise ValueError(f"image mode must be 'L' or 'RGB', got {image.mode!r}")
         self.__net_config = net_config
-        self.plan = sample_plan(image.size, markup, rng, np_rng, photo_rng) if plan is None else plan
+        self.plan = sample_plan(image.size, markup, rng, np_rng, photo_rng, photo_extended) if plan is None else plan
         self.__aug_image, self.__aug_markup = image, markup
         if not self.plan.stages and (self.plan.original or not self.plan.photometric):
             return
