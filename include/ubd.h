@@ -272,8 +272,8 @@ int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t d
  * whose 2r + 1 taps sum to 16384, NOISE scale finite and >= 0 (non-zero return otherwise, nothing launched).
  * Enqueues at most four launches per 32 images (one kernel each for the pointwise modes, for FILTER3 / SEP / BOX, for MEDIAN and
  * for ELASTIC; a kernel whose modes do not occur is not launched); no host synchronisation, capturable in a HIP graph.
- * Not built (they need imgaug's simplex / frequency noise-mask generators and its cv2 mask upscaling): SimplexNoiseAlpha(EdgeDetect
- * / DirectedEdgeDetect) and FrequencyNoiseAlpha. */
+ * The two noise-alpha operations of that stage, SimplexNoiseAlpha(EdgeDetect / DirectedEdgeDetect) and FrequencyNoiseAlpha, are
+ * ubd_noise_alpha_images below. */
 enum { UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE, UBD_PHOTO_DROPOUT,
        UBD_PHOTO_MEDIAN = 16, UBD_PHOTO_HSV = 17, UBD_PHOTO_ELASTIC = 18 };
 typedef struct ubd_photo_desc {
@@ -286,6 +286,71 @@ typedef struct ubd_photo_desc {
 } ubd_photo_desc;
 int ubd_photometric_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes,
                            const ubd_photo_desc *descs, int channels, int n, void *stream);
+
+/* --- mask-blended augmentation stages ---------------------------------------------
+ * The last two operations of the reference's imgaug stage: SimplexNoiseAlpha(OneOf([EdgeDetect, DirectedEdgeDetect]))
+ * (augmentation.py:301-304) and FrequencyNoiseAlpha(first = Multiply, second = ContrastNormalization) (:319-323).  Both blend two
+ * differently processed copies of the image, per pixel, by a smooth random mask: a few tiny noise grids (made by the caller on
+ * the host), upscaled to the image, aggregated and pushed through a curve.  Images as for ubd_photometric_images: n uint8 images
+ * of `channels` (1 or 3) channels with packed rows, every image with its own size at src + src_offset, written at
+ * dst + dst_offset; sides 1..16384; any byte alignment works, dword accesses are used where the addresses allow.  Every
+ * overlap of an image's source and destination ranges is refused (the FILTER3 branch reads neighbours).
+ * DEFINITION, all in integer arithmetic (`>>` is an arithmetic shift, `/` has non-negative operands only); the device matches
+ * tests/noise_alpha_oracle.py bit for bit; PARITY WITH imgaug / cv2 IS UNPINNED (cv2.resize's coefficients are restated at
+ * 1/32-pixel phases, the noise generators are the caller's).
+ *   Branches `first` and `second` give a uint8 value per channel, F_c and S_c:
+ *     UBD_NA_IDENTITY  the pixel
+ *     UBD_NA_FILTER3   p[0..8] = 3x3 correlation taps in Q14, row-major, |tap| <= 13 * 16384, reflect-101 border:
+ *                      clamp((sum tap v + 8192) >> 14), exactly UBD_PHOTO_FILTER3
+ *     UBD_NA_AFFINE    p[c] = m_c, p[3 + c] = a_c (Q16), |m_c| <= 2^17, |a_c| <= 2^24 (all three entries are checked):
+ *                      clamp((m_c v + a_c + 32768) >> 16), exactly UBD_PHOTO_AFFINE
+ *   Mask: `iterations` (1..3) grids; grid i has gw x gh cells (each 1..16), row-major uint16 values g in 0..32768 (Q15) at
+ *   tables + grid_offset, and an upscale method.  Upscaled value u_i(x, y), Q15; each axis independently (x shown; y the same
+ *   with h, gh, y):
+ *     UBD_NA_NEAREST   ix = min(gw - 1, (x gw) / w), one tap of weight 1
+ *     UBD_NA_LINEAR, UBD_NA_CUBIC (cv2.resize's pixel-centre rule): X = (2 x + 1) gw - w, ix = floor(X / 2 w) (a true floor: X may
+ *                      be negative, then ix = -1), r = X - ix 2 w, phase k = (32 r) / (2 w) in 0..31
+ *       LINEAR         taps ix, ix + 1 with weights 32 - k, k
+ *       CUBIC          taps ix - 1 .. ix + 2 with the Q17 Keys weights W0..W3 at phase k of UBD_PHOTO_ELASTIC (they sum to 131072)
+ *     tap indices are clamped to 0..gw-1 (replicate border).  The 2-D value is the full double sum over both axes' taps, rounded
+ *     once: NEAREST g itself; LINEAR (sum wy wx g + 512) >> 10; CUBIC clamp((sum Wy Wx g + 2^33) >> 34, 0, 32768) (per axis the
+ *     sum of |W| is at most 180224 = 1.375 * 2^17, so the sum needs 64 bits and stays below 2^51).
+ *   Aggregation: UBD_NA_MAX u = max_i u_i; UBD_NA_AVG u = (sum_i u_i + iterations / 2) / iterations.
+ *   Curve: 257 uint16 values T[0..256], each 0..16384 (Q14), at tables + curve_offset (a sigmoid, or T[i] = 64 i for none):
+ *     i = u >> 7, f = u & 127, a = T[i] when f = 0, else (T[i] (128 - f) + T[i + 1] f + 64) >> 7 (i = 256 occurs only with f = 0).
+ *   Blend, one mask for all channels: out_c = (a F_c + (16384 - a) S_c + 8192) >> 14.
+ * descs: HOST array of n descriptors; tables: DEVICE array of table_count uint16 values; offsets into it are in uint16 units.
+ * Checked on the host (non-zero return, nothing launched, ubd_last_error() starts with the function's name): null pointers,
+ * n >= 1, channels 1 or 3, sides, ranges inside the two buffers, overlaps, branch kinds and parameters, iterations 1..3, grid
+ * sides 1..16, the upscale and aggregation codes, every grid and the curve inside table_count.  The table VALUES are on the
+ * device and are trusted: a g above 32768 or a T above 16384 is the caller's error (the result is then undefined, though no
+ * access leaves the buffers).
+ * Enqueues one launch per 24 images; no host synchronisation, capturable in a HIP graph. */
+enum { UBD_NA_IDENTITY, UBD_NA_FILTER3, UBD_NA_AFFINE };      /* branch kinds */
+enum { UBD_NA_NEAREST, UBD_NA_LINEAR, UBD_NA_CUBIC };         /* upscale methods */
+enum { UBD_NA_MAX, UBD_NA_AVG };                              /* aggregation */
+typedef struct ubd_noise_alpha_branch {
+    int32_t kind;                    /* UBD_NA_IDENTITY / FILTER3 / AFFINE */
+    int32_t p[9];                    /* per kind, see above; unused entries 0 */
+} ubd_noise_alpha_branch;
+typedef struct ubd_noise_alpha_grid {
+    int32_t gw, gh;                  /* 1..16 */
+    int32_t upscale;                 /* UBD_NA_NEAREST / LINEAR / CUBIC */
+    int32_t reserved;                /* 0 */
+    int64_t grid_offset;             /* uint16 units from tables to the gh * gw values */
+} ubd_noise_alpha_grid;
+typedef struct ubd_noise_alpha_desc {
+    int64_t src_offset, dst_offset;  /* bytes from src / dst to the image */
+    int32_t w, h;
+    int32_t iterations;              /* 1..3: how many of grid[] are used */
+    int32_t aggregation;             /* UBD_NA_MAX / AVG */
+    ubd_noise_alpha_branch first, second;
+    ubd_noise_alpha_grid grid[3];
+    int64_t curve_offset;            /* uint16 units from tables to T[0..256] */
+} ubd_noise_alpha_desc;
+int ubd_noise_alpha_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes,
+                           const ubd_noise_alpha_desc *descs, const uint16_t *tables, size_t table_count,
+                           int channels, int n, void *stream);
 
 /* --- object-level evaluation ----------------------------------------------------
  * Replaces FtMetricsCalculator (evaluation.py:168-429: areas, the G x F intersection / IoU tables :210-227, analyze :229-328, the

@@ -14,7 +14,11 @@ The photometric stage is not part of either side of the end-to-end legs (the pla
     frames (median of --iters), source and destination in separate buffers, next to the bytes-moved bound of a stage,
     2 x image bytes (read once, written once), and the GB/s those bytes are in that time.
     The legs: every mode, MEDIAN at k = 3 and 11, HSV, ELASTIC at alpha = 3.5 (--only NAME[,NAME]: just those legs).
-Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5] [--photometric [--only median_k11]]
+  --noise-alpha: instead of the legs above, HIP-event time of one ubd_noise_alpha_images call over 32 x 512 x 512 RGB images with
+    three 16 x 16 cubic grids, max aggregation and a sigmoid curve, branches FILTER3 / IDENTITY (SimplexNoiseAlpha's shape) and
+    AFFINE / AFFINE (FrequencyNoiseAlpha's), next to one ubd_photometric_images call in mode FILTER3 on the same images: the
+    three calls alternate inside every round (200 rounds by default), median and minimum per call, and the ratios to FILTER3.
+Usage: python tools/bench_augment.py [--iters 30] [--e2e-iters 5] [--photometric [--only median_k11]] [--noise-alpha [--rounds 200]]
 """
 import argparse
 import concurrent.futures as cf
@@ -117,6 +121,56 @@ def photometric_legs(iters, n=16, h=1080, w=1920, c=3, only=None):
     return out
 
 
+def noise_alpha_legs(rounds, n=32, h=512, w=512, c=3):
+    lib = _lib.load()
+    St = aug.Stage
+    per = h * w * c
+    src = torch.randint(0, 256, (n * per,), dtype=torch.uint8, device="cuda")
+    dst = torch.empty(n * per, dtype=torch.uint8, device="cuda")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    its = tuple({"size": 16, "upscale": "cubic", "seed": 10 + k} for k in range(3))
+    stages = {"simplex_filter3_identity": St("simplex_alpha", {"directed": True, "alpha": 0.8, "direction": 0.3, "iterations": its, "aggregation": "max",
+                                                              "sigmoid": True, "threshold": 1.0}, None),
+              "frequency_affine_affine": St("frequency_alpha", {"exponent": -2.0, "factors": (0.7, 1.1, 1.4), "contrast_alpha": 1.6, "iterations": its,
+                                                                "aggregation": "max", "sigmoid": True, "threshold": 1.0}, None)}
+    calls, keep = {}, []
+    for name, st in stages.items():
+        f, tab = aug.noise_alpha_descs(st, w, h, c)
+        descs = np.zeros(n, aug.NOISE_ALPHA_DESC)
+        for k in range(n):
+            aug.fill_noise_alpha_desc(descs[k], f)
+        descs["src_offset"] = descs["dst_offset"] = np.arange(n, dtype=np.int64) * per
+        descs["w"], descs["h"] = w, h
+        tables = torch.from_numpy(tab.view(np.int16)).cuda()
+        keep.append((descs, tables))
+        calls["noise_alpha_" + name] = lambda d=descs, t=tables: _lib.check(
+            lib.ubd_noise_alpha_images(src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(), d.ctypes.data, t.data_ptr(), t.numel(), c, n, stream),
+            "ubd_noise_alpha_images")
+    f = aug.photometric_descs(St("sharpen", {"alpha": 0.5, "lightness": 1.2}, None), w, h, c)
+    pd = np.zeros(n, aug.PHOTO_DESC)
+    pd["src_offset"] = pd["dst_offset"] = np.arange(n, dtype=np.int64) * per
+    pd["w"], pd["h"], pd["mode"] = w, h, f["mode"]
+    pd["p"][:, :len(f["p"])] = f["p"]
+    calls["photometric_filter3"] = lambda: _lib.check(
+        lib.ubd_photometric_images(src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(), pd.ctypes.data, c, n, stream), "ubd_photometric_images")
+    for fn in calls.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in calls}
+    for _ in range(rounds):                                   # the calls alternate inside every round
+        for name, fn in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b) * 1e3)
+    base = float(np.median(times["photometric_filter3"]))
+    gb = 2 * n * per / 1e9
+    return [{"leg": f"{name}_{n}x{h}x{w}_c{c}", "rounds": rounds, "us_median": round(float(np.median(t)), 1), "us_min": round(float(np.min(t)), 1),
+             "MB_bound_2x_image_bytes": round(gb * 1e3, 1), "GBps": round(gb / float(np.median(t)) * 1e6, 1),
+             "ratio_to_photometric_filter3": round(float(np.median(t)) / base, 2)} for name, t in times.items()]
+
+
 def _pillow_chain(im, plan):
     for st in plan.stages:
         if st.kind in ("rotate", "quarter"):
@@ -180,8 +234,14 @@ def main():
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--photometric", action="store_true", help="time ubd_photometric_images per mode instead of the warp / end-to-end legs")
     ap.add_argument("--only", default="", help="with --photometric: comma-separated leg names (e.g. median_k11), for a profiler run of one leg")
+    ap.add_argument("--noise-alpha", action="store_true", help="time ubd_noise_alpha_images next to ubd_photometric_images in mode FILTER3")
+    ap.add_argument("--rounds", type=int, default=200, help="with --noise-alpha: rounds in which the calls alternate")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.noise_alpha:
+        for leg in noise_alpha_legs(args.rounds):
+            print(json.dumps(leg), flush=True)
+        return
     if args.photometric:
         for leg in photometric_legs(args.iters, only=[v for v in args.only.split(",") if v]):
             print(json.dumps(leg), flush=True)

@@ -18,6 +18,9 @@ UBD_WARP_COPY, UBD_WARP_AFFINE, UBD_WARP_PERSPECTIVE = 0, 1, 2
 (UBD_PHOTO_AFFINE, UBD_PHOTO_GREY, UBD_PHOTO_FILTER3, UBD_PHOTO_SEP, UBD_PHOTO_BOX, UBD_PHOTO_NOISE,
  UBD_PHOTO_DROPOUT) = range(7)
 UBD_PHOTO_MEDIAN, UBD_PHOTO_HSV, UBD_PHOTO_ELASTIC = 16, 17, 18
+UBD_NA_IDENTITY, UBD_NA_FILTER3, UBD_NA_AFFINE = 0, 1, 2
+UBD_NA_NEAREST, UBD_NA_LINEAR, UBD_NA_CUBIC = 0, 1, 2
+UBD_NA_MAX, UBD_NA_AVG = 0, 1
 UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS = 8, 256, 256, 16
 UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
 UBD_MAX_CLASSES = 31
@@ -68,6 +71,7 @@ SIGNATURES = {
     "ubd_resize_images": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
     "ubd_warp_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_photometric_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
+    "ubd_noise_alpha_images": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _vp]),
     "ubd_evaluate_accumulator_bytes": (_sz, [_i, _i]),
     "ubd_evaluate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ubd_evaluate_objects": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

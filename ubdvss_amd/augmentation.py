@@ -17,11 +17,18 @@ drawn only with ``extended=True`` / ``photo_extended=True`` (``PHOTO_EXTENDED``;
 stream stays as it was): MedianBlur, AddToHueAndSaturation (the hue wraps; imgaug of the reference's era clips it) and
 ElasticTransformation (cv2.remap's bicubic; imgaug of the reference's era uses a scipy spline).  Without the flag these three
 are recorded as ``Stage("unbuilt", {"name": ...})`` and change no pixel.
-NOT BUILT (drawn as often as in the reference, always recorded as ``unbuilt``, no pixel changes): SimplexNoiseAlpha(EdgeDetect /
-DirectedEdgeDetect) and FrequencyNoiseAlpha -- they need imgaug's noise-mask generators.  imgaug and OpenCV are not available to
-compare with: each built operation follows the libraries' published behaviour in integer arithmetic DEFINED by include/ubd.h,
-tests/photometric_oracle.py and tests/photometric_ext_oracle.py, which the device matches bit for bit; PARITY WITH imgaug / cv2
-IS UNPINNED, and the random stream is numpy's, not imgaug's.
+The last two, drawn only with ``noise_alpha=True`` / ``photo_noise_alpha=True`` (``PHOTO_NOISE_ALPHA``; off by default too, and
+independent of the other flag): SimplexNoiseAlpha(EdgeDetect / DirectedEdgeDetect) and FrequencyNoiseAlpha(Multiply,
+ContrastNormalization).  Both blend two processed copies of the image by a smooth random mask: ``simplex_grid`` /
+``frequency_grid`` make the mask's tiny noise grids on the host (at most 16 x 16 cells: ``noise_alpha_grid_size``),
+``alpha_curve`` its sigmoid table, ``noise_alpha_descs`` lowers a stage to the descriptor of ``ubd_noise_alpha_images``
+(csrc/noise_alpha.hip), which upscales, aggregates, applies the curve, makes both branches and blends in one kernel.  Without
+the flag they too are recorded as ``unbuilt``.  With both flags no operation of the reference's stage is left out.
+imgaug and OpenCV are not available to compare with: each built operation follows the libraries' published behaviour in integer
+arithmetic DEFINED by include/ubd.h, tests/photometric_oracle.py, tests/photometric_ext_oracle.py and
+tests/noise_alpha_oracle.py, which the device matches bit for bit; PARITY WITH imgaug / cv2 IS UNPINNED: the random stream is
+numpy's, not imgaug's; the simplex generator is the classic 2-D simplex noise, not the OpenSimplex package imgaug calls; the
+mask's grids are capped at 16 x 16 cells; cv2.resize's coefficients are restated at 1/32-pixel phases.
 Without ``photo_rng`` the stage's decision draw is consumed, the plan records it (``photometric_requested``) and the pixels
 are left as the geometric chain made them.
 Flips have probability 0 in the reference: their draws are consumed, they are never applied.
@@ -45,6 +52,9 @@ from . import _lib
 # 'noise' {scale, per_channel, seed}, 'dropout' {p, per_channel, seed}, 'invert' {channels}, 'add' {values, per_channel},
 # 'multiply' {factors, per_channel}, 'contrast' {alphas, per_channel}, 'grayscale' {alpha}, 'unbuilt' {name};
 # drawn only with extended=True: 'median_blur' {k}, 'hue_saturation' {value}, 'elastic' {applied, sigma; alpha, seed when applied}
+# drawn only with noise_alpha=True: 'simplex_alpha' {directed, alpha, direction (directed only), + the mask parameters},
+# 'frequency_alpha' {exponent, factors, contrast_alpha, + the mask parameters}; the mask parameters: iterations (a tuple of
+# {size, upscale: 'nearest' | 'linear' | 'cubic', seed}), aggregation: 'max' | 'avg', sigmoid, threshold
 Stage = collections.namedtuple("Stage", ["kind", "params", "size"])
 # size: (w, h) of the source image; original: the 10 % "feed the original" branch was taken (no further draws);
 # photometric_requested: the reference would have run its imgaug stage here; photometric: that stage's operations, drawn only
@@ -229,7 +239,7 @@ def _sample_crop(boxes, size, rng):
     return Stage("crop", {"box": box, "window": (x0, y0, x1, y1)}, (x1 - x0, y1 - y0))
 
 
-def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None, photo_extended=False):
+def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None, photo_extended=False, photo_noise_alpha=False):
     """Draws the parameters of the reference's ``__augment_image`` (augmentation.py:50-85) for one image of ``image_size`` =
     (w, h) and its ``markup`` and returns an ``AugmentationPlan``: the stages with their numbers and the image size after each.
 
@@ -241,8 +251,8 @@ def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None, photo
     ``random()`` (< 0.7) for the photometric stage: the plan records that it was requested.
     ``rng`` / ``np_rng``: objects with the interface of the ``random`` / ``numpy.random`` modules (the defaults).
     ``photo_rng``: a ``numpy.random.Generator`` for the photometric stage's own draws (imgaug keeps its own generator too);
-    when it is given and the stage was requested, ``plan.photometric = sample_photometric(3, photo_rng, photo_extended)``
-    (per-channel parameters for three channels; a grey image uses the first).  Nothing more is drawn from ``rng`` / ``np_rng`` either way.
+    when it is given and the stage was requested, ``plan.photometric = sample_photometric(3, photo_rng, photo_extended,
+    photo_noise_alpha)`` (per-channel parameters for three channels; a grey image uses the first).  Nothing more is drawn from ``rng`` / ``np_rng`` either way.
     A stage whose input is degenerate (markup bounds without width or height, a crop that rounds to an empty window) is
     skipped with a warning and the chain goes on."""
     rng = _random if rng is None else rng
@@ -280,7 +290,7 @@ def sample_plan(image_size, markup, rng=None, np_rng=None, photo_rng=None, photo
         push(Stage("perspective", {"coeffs": coeffs}, cur))
     photometric = rng.random() < PHOTOMETRIC_P
     if photometric and photo_rng is not None:
-        return AugmentationPlan(size, tuple(stages), False, True, sample_photometric(3, photo_rng, photo_extended))
+        return AugmentationPlan(size, tuple(stages), False, True, sample_photometric(3, photo_rng, photo_extended, photo_noise_alpha))
     return AugmentationPlan(size, tuple(stages), False, bool(photometric))
 
 
@@ -291,11 +301,15 @@ PHOTO_ENTRIES = ("blur", "sharpen", "emboss", "edge_detect", "noise", "dropout",
 PHOTO_UNBUILT = ("MedianBlur", "SimplexNoiseAlpha", "AddToHueAndSaturation", "FrequencyNoiseAlpha", "ElasticTransformation")
 # the three of them that sample_photometric(..., extended=True) draws as stages of their own
 PHOTO_EXTENDED = ("MedianBlur", "AddToHueAndSaturation", "ElasticTransformation")
+# the other two, which sample_photometric(..., noise_alpha=True) draws as stages of their own
+PHOTO_NOISE_ALPHA = ("SimplexNoiseAlpha", "FrequencyNoiseAlpha")
+NOISE_ALPHA_KINDS = ("simplex_alpha", "frequency_alpha")
+NOISE_ALPHA_MAX_GRID = 16             # cells per side of a mask grid: the limit of ubd_noise_alpha_images (imgaug has none)
 PHOTO_POINTWISE = (_lib.UBD_PHOTO_AFFINE, _lib.UBD_PHOTO_GREY, _lib.UBD_PHOTO_NOISE, _lib.UBD_PHOTO_DROPOUT, _lib.UBD_PHOTO_HSV)
 ELASTIC_SIGMA = 0.25
 
 
-def sample_photometric(channels, gen, extended=False):
+def sample_photometric(channels, gen, extended=False, noise_alpha=False):
     """The draws of the reference's imgaug stage (augmentation.py:280-330) from ``gen``, a ``numpy.random.Generator``: a tuple of
     ``Stage``s (``size`` None) in the order they are applied.  Order of the draws: ``n = gen.integers(0, 6)``;
     ``gen.permutation(13)[:n]`` over ``PHOTO_ENTRIES`` (SomeOf((0, 5)), random_order=True); per chosen entry its parameters in
@@ -308,7 +322,16 @@ def sample_photometric(channels, gen, extended=False):
     ``extended``: the three operations of ``PHOTO_EXTENDED`` draw their parameters in place of the ``unbuilt`` stage -- MedianBlur
     ``k = gen.integers(3, 12)``, an even k becoming k + 1 (imgaug's rule); AddToHueAndSaturation one ``gen.integers(-20, 21)`` for
     both channels; ElasticTransformation, after its coin and only when applied, ``gen.uniform(0.5, 3.5)`` (alpha) and a 64-bit
-    seed, sigma 0.25.  Every other entry, the count and the permutation draw as without it."""
+    seed, sigma 0.25.  Every other entry, the count and the permutation draw as without it.
+    ``noise_alpha``: independent of ``extended``; the two operations of ``PHOTO_NOISE_ALPHA`` draw their parameters in place of
+    the ``unbuilt`` stage, in this order.  The edge_detect entry (``"simplex_alpha"``): ``gen.integers(0, 2)`` (EdgeDetect /
+    DirectedEdgeDetect), alpha ``gen.uniform(0.5, 1.0)``, for the directed form direction ``gen.uniform(0, 1)``, then the mask.
+    The FrequencyNoiseAlpha branch of the multiply entry (``"frequency_alpha"``): exponent ``gen.uniform(-4, 0)``, ``channels``
+    Multiply factors ``gen.uniform(0.5, 1.5)`` (per_channel=True in the reference), one contrast alpha ``gen.uniform(0.5, 2.0)``,
+    then the mask.  The mask: iterations ``gen.integers(1, 4)``; per iteration ``size_px_max = gen.integers(lo, 17)`` (lo = 2
+    for simplex, 4 for frequency), the upscale method from one ``gen.random()`` (< 0.05 nearest, < 0.65 linear, else cubic)
+    and a 64-bit seed; then, frequency only, aggregation ``gen.integers(0, 2)`` (0 avg, 1 max) and the
+    sigmoid coin ``gen.random() < 0.5`` (simplex: max, sigmoid on); last the threshold ``gen.normal(0, 5)``."""
     c = int(channels)
 
     def per_channel(values):
@@ -318,6 +341,14 @@ def sample_photometric(channels, gen, extended=False):
 
     def seed():
         return int(gen.integers(0, 2 ** 64, dtype=np.uint64))
+
+    def mask(lo):
+        its = []
+        for _ in range(int(gen.integers(1, 4))):
+            size = int(gen.integers(lo, 17))
+            r = float(gen.random())                                      # p = 0.05 / 0.6 / 0.35
+            its.append({"size": size, "upscale": "nearest" if r < 0.05 else ("linear" if r < 0.65 else "cubic"), "seed": seed()})
+        return tuple(its)
 
     n = int(gen.integers(0, 6))
     stages = []
@@ -339,7 +370,15 @@ def sample_photometric(channels, gen, extended=False):
         elif name == "emboss":
             st = ("emboss", {"alpha": float(gen.uniform(0.0, 1.0)), "strength": float(gen.uniform(0.0, 2.0))})
         elif name == "edge_detect":
-            st = ("unbuilt", {"name": "SimplexNoiseAlpha"})
+            if noise_alpha:
+                directed = bool(int(gen.integers(0, 2)))
+                q = {"directed": directed, "alpha": float(gen.uniform(0.5, 1.0))}
+                if directed:
+                    q["direction"] = float(gen.uniform(0.0, 1.0))
+                q.update(iterations=mask(2), aggregation="max", sigmoid=True, threshold=float(gen.normal(0.0, 5.0)))
+                st = ("simplex_alpha", q)
+            else:
+                st = ("unbuilt", {"name": "SimplexNoiseAlpha"})
         elif name == "noise":
             scale = float(gen.uniform(0.0, 0.05 * 255))
             st = ("noise", {"scale": scale, "per_channel": bool(gen.random() < 0.5), "seed": seed()})
@@ -357,6 +396,12 @@ def sample_photometric(channels, gen, extended=False):
             if int(gen.integers(0, 2)) == 0:
                 factors, pc = per_channel(float(v) for v in gen.uniform(0.5, 1.5, size=c))
                 st = ("multiply", {"factors": factors, "per_channel": pc})
+            elif noise_alpha:
+                q = {"exponent": float(gen.uniform(-4.0, 0.0)), "factors": tuple(float(v) for v in gen.uniform(0.5, 1.5, size=c)),
+                     "contrast_alpha": float(gen.uniform(0.5, 2.0)), "iterations": mask(4)}
+                q.update(aggregation=("avg", "max")[int(gen.integers(0, 2))], sigmoid=bool(gen.random() < 0.5),
+                         threshold=float(gen.normal(0.0, 5.0)))
+                st = ("frequency_alpha", q)
             else:
                 st = ("unbuilt", {"name": "FrequencyNoiseAlpha"})
         elif name == "contrast":
@@ -400,11 +445,18 @@ def elastic_taps(sigma):
     return 16384 - 2 * w1, w1
 
 
+def _affine_p(ms, as_, c):
+    """p[] of an AFFINE map for c channels: m_c then a_c in Q16, the unused channels the identity"""
+    ms, as_ = list(ms)[:c], list(as_)[:c]
+    return [int(v) for v in ms + [65536] * (3 - c) + as_ + [0] * (3 - c)]
+
+
 def photometric_descs(stage, w, h, c):
     """The integer descriptor fields of one photometric stage for a w x h image of c channels (layout: ubd_photo_desc in
     include/ubd.h): {"mode", "flags", "seed", "p"} -- or None when the stage launches nothing: an unbuilt operation, Grayscale
-    or AddToHueAndSaturation of a grey image, a blur with sigma < 1e-3, an ElasticTransformation whose coin said no.  Pure host
-    code."""
+    or AddToHueAndSaturation of a grey image, a blur with sigma < 1e-3, an ElasticTransformation whose coin said no.  The two
+    mask-blended kinds (``NOISE_ALPHA_KINDS``) are no mode of that call: they RAISE ValueError here and are lowered by
+    ``noise_alpha_descs`` (None would let a stage that changes pixels pass for one that launches nothing).  Pure host code."""
     kind, q = stage.kind, stage.params
     c = int(c)
 
@@ -412,8 +464,7 @@ def photometric_descs(stage, w, h, c):
         return {"mode": mode, "flags": int(flags), "seed": int(seed), "p": [int(v) for v in p]}
 
     def affine(ms, as_):
-        ms, as_ = list(ms)[:c], list(as_)[:c]
-        return desc(_lib.UBD_PHOTO_AFFINE, ms + [65536] * (3 - c) + as_ + [0] * (3 - c))
+        return desc(_lib.UBD_PHOTO_AFFINE, _affine_p(ms, as_, c))
 
     def filter3(alpha, e):
         k = (1.0 - alpha) * np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], np.float64) + alpha * np.array(e, np.float64)
@@ -421,6 +472,8 @@ def photometric_descs(stage, w, h, c):
 
     if kind == "unbuilt":
         return None
+    if kind in NOISE_ALPHA_KINDS:
+        raise ValueError(f"stage {kind!r} is no mode of ubd_photometric_images: lower it with noise_alpha_descs")
     if kind == "invert":
         return affine([-65536 if v else 65536 for v in q["channels"]], [255 * 65536 if v else 0 for v in q["channels"]])
     if kind == "add":
@@ -459,12 +512,149 @@ def photometric_descs(stage, w, h, c):
     raise ValueError(f"unknown photometric stage kind {kind!r}")
 
 
+# ---------------------------------------------------------------------------------------------------- mask-blended stages
+def noise_alpha_grid_size(h, w, size_px_max):
+    """(gh, gw): the coarse size of a mask grid for an h x w image (imgaug's ``size_px_max`` rule: the longer side becomes
+    ``size_px_max``, the other keeps the aspect, at least 1; an image no larger than that keeps its size), both then clamped to
+    ``NOISE_ALPHA_MAX_GRID`` = 16 -- that clamp exists only here: 16 x 16 is the largest grid ubd_noise_alpha_images takes."""
+    h, w, s = int(h), int(w), int(size_px_max)
+    if max(h, w) > s:
+        gh, gw = max(1, h * s // max(h, w)), max(1, w * s // max(h, w))
+    else:
+        gh, gw = h, w
+    return min(gh, NOISE_ALPHA_MAX_GRID), min(gw, NOISE_ALPHA_MAX_GRID)
+
+
+def _quantise_grid(g):
+    return np.clip(np.rint(32768.0 * g), 0, 32768).astype(np.uint16)
+
+
+_SIMPLEX_GRAD = np.array([(1, 1), (-1, 1), (1, -1), (-1, -1), (1, 0), (-1, 0), (1, 0), (-1, 0), (0, 1), (0, -1), (0, 1), (0, -1)], np.float64)
+
+
+def simplex_grid(gh, gw, seed):
+    """(gh, gw) uint16 in 0..32768 (Q15): classic 2-D simplex noise (Perlin 2001, in Gustavson's public-domain formulation,
+    written from the algorithm) with the permutation table ``default_rng(seed).permutation(256)``, sampled at the integer
+    coordinates (x, y) of the grid, n in [-1, 1] mapped to (n + 1) / 2 and quantised with rint(32768 g).  imgaug calls the
+    OpenSimplex package instead: parity is unpinned."""
+    perm = np.random.default_rng(seed).permutation(256)
+    perm = np.concatenate([perm, perm, perm[:2]])
+    f2, g2 = 0.5 * (math.sqrt(3.0) - 1.0), (3.0 - math.sqrt(3.0)) / 6.0
+    yin, xin = np.mgrid[0:int(gh), 0:int(gw)].astype(np.float64)
+    s = (xin + yin) * f2                                                  # skew to the simplex cell
+    i, j = np.floor(xin + s), np.floor(yin + s)
+    t = (i + j) * g2
+    x0, y0 = xin - (i - t), yin - (j - t)                                 # distance from the cell origin
+    i1 = (x0 > y0).astype(np.int64)                                       # lower triangle: (1, 0), upper: (0, 1)
+    j1 = 1 - i1
+    ii, jj = i.astype(np.int64) & 255, j.astype(np.int64) & 255
+    n = np.zeros(xin.shape, np.float64)
+    for di, dj, off in ((0, 0, 0.0), (i1, j1, g2), (1, 1, 2.0 * g2)):     # the three corners of the simplex
+        x, y = x0 - di + off, y0 - dj + off
+        grad = _SIMPLEX_GRAD[perm[ii + di + perm[jj + dj]] % 12]
+        tt = 0.5 - x * x - y * y
+        n += np.where(tt < 0, 0.0, tt ** 4 * (grad[..., 0] * x + grad[..., 1] * y))
+    return _quantise_grid((70.0 * n + 1.0) / 2.0)
+
+
+def frequency_grid(gh, gw, exponent, seed):
+    """(gh, gw) uint16 in 0..32768 (Q15): imgaug's frequency noise.  ``R, A = default_rng(seed).random((2, gh, gw))``; the
+    spectrum R f**exponent exp(2 pi i A) with f = sqrt(fx^2 + fy^2) from ``np.fft.fftfreq`` and the [0, 0] term 0; the real part
+    of its inverse transform, min-max normalised to 0..1 (a constant field becomes 0.5), quantised with rint(32768 g)."""
+    gh, gw = int(gh), int(gw)
+    r, a = np.random.default_rng(seed).random((2, gh, gw))
+    f = np.sqrt(np.fft.fftfreq(gh)[:, None] ** 2 + np.fft.fftfreq(gw)[None, :] ** 2)
+    f[0, 0] = 1.0
+    spectrum = r * f ** float(exponent) * np.exp(2j * np.pi * a)
+    spectrum[0, 0] = 0.0
+    g = np.real(np.fft.ifft2(spectrum))
+    lo, hi = float(g.min()), float(g.max())
+    g = (g - lo) / (hi - lo) if hi > lo else np.full(g.shape, 0.5)
+    return _quantise_grid(g)
+
+
+def alpha_curve(sigmoid, threshold):
+    """257 uint16 in 0..16384 (Q14), the mask value at u = 128 i of Q15: with ``sigmoid`` imgaug's Sigmoid(mul=20, add=-10) moved by
+    the threshold, T[i] = rint(16384 / (1 + exp(-(20 i / 256 - 10 - threshold)))) in float64; without, T[i] = 64 i."""
+    i = np.arange(257, dtype=np.float64)
+    if not sigmoid:
+        return (64 * np.arange(257)).astype(np.uint16)
+    return np.rint(16384.0 / (1.0 + np.exp(-(20.0 * i / 256.0 - 10.0 - float(threshold))))).astype(np.uint16)
+
+
+EDGE_DETECT_KERNEL = ((0, 1, 0), (1, -4, 1), (0, 1, 0))
+
+
+def directed_edge_kernel(direction):
+    """imgaug's DirectedEdgeDetect matrix at alpha 1 for ``direction`` in 0..1 (a full turn): the direction vector at 360 d - 90
+    degrees; each of the 8 neighbours gets (1 - angle between it and the vector / 180 degrees)^4; normalised to sum 1, negated,
+    centre 1: the matrix sums to 0."""
+    rad = math.radians(360.0 * float(direction)) - 0.5 * math.pi
+    vec = np.array([math.cos(rad), math.sin(rad)])
+    m = np.zeros((3, 3), np.float64)
+    for y in (-1, 0, 1):
+        for x in (-1, 0, 1):
+            if (x, y) != (0, 0):
+                cell = np.array([x, y], np.float64)
+                ang = math.degrees(math.acos(float(np.clip(np.dot(cell / np.linalg.norm(cell), vec), -1.0, 1.0))))
+                m[y + 1, x + 1] = (1.0 - ang / 180.0) ** 4
+    m = -m / m.sum()
+    m[1, 1] = 1.0
+    return m
+
+
+_NA_UPSCALE = {"nearest": _lib.UBD_NA_NEAREST, "linear": _lib.UBD_NA_LINEAR, "cubic": _lib.UBD_NA_CUBIC}
+
+
+def noise_alpha_descs(stage, w, h, c):
+    """One mask-blended stage (``NOISE_ALPHA_KINDS``) for a w x h image of c channels -> (fields, tables): the descriptor fields
+    of ``ubd_noise_alpha_desc`` (include/ubd.h) -- {"first", "second": {"kind", "p"}, "grids": [{"gw", "gh", "upscale",
+    "grid_offset"}], "aggregation", "curve_offset"} -- and the uint16 tables they point into, the grids then the curve (offsets
+    count from the start of that array).  'simplex_alpha': first = FILTER3, the Q14 taps of (1 - alpha) identity + alpha E with E
+    the EdgeDetect matrix or ``directed_edge_kernel``, lowered as Sharpen is; second = IDENTITY.  'frequency_alpha': first =
+    AFFINE from the Multiply factors, second = AFFINE from the contrast alpha, with the formulas of ``photometric_descs``.  Pure
+    host code."""
+    kind, q = stage.kind, stage.params
+    c = int(c)
+
+    def affine(ms, as_):
+        return {"kind": _lib.UBD_NA_AFFINE, "p": _affine_p(ms, as_, c)}
+
+    if kind == "simplex_alpha":
+        e = np.array(directed_edge_kernel(q["direction"]) if q["directed"] else EDGE_DETECT_KERNEL, np.float64)
+        k = (1.0 - q["alpha"]) * np.array([[0, 0, 0], [0, 1, 0], [0, 0, 0]], np.float64) + q["alpha"] * e
+        first = {"kind": _lib.UBD_NA_FILTER3, "p": [int(v) for v in np.rint(k * 16384.0).astype(np.int64).reshape(-1)]}
+        second = {"kind": _lib.UBD_NA_IDENTITY, "p": []}
+    elif kind == "frequency_alpha":
+        first = affine([int(np.rint(f * 65536.0)) for f in q["factors"]], [0] * 3)
+        a = q["contrast_alpha"]
+        second = affine([int(np.rint(a * 65536.0))] * 3, [int(np.rint(128.0 * (1.0 - a) * 65536.0))] * 3)
+    else:
+        raise ValueError(f"not a mask-blended stage: {kind!r}")
+    grids, tables, pos = [], [], 0
+    for it in q["iterations"]:
+        gh, gw = noise_alpha_grid_size(h, w, it["size"])
+        g = simplex_grid(gh, gw, it["seed"]) if kind == "simplex_alpha" else frequency_grid(gh, gw, q["exponent"], it["seed"])
+        grids.append({"gw": gw, "gh": gh, "upscale": _NA_UPSCALE[it["upscale"]], "grid_offset": pos})
+        tables.append(g.reshape(-1))
+        pos += gh * gw
+    tables.append(alpha_curve(q["sigmoid"], q["threshold"]))
+    fields = {"first": first, "second": second, "grids": grids, "aggregation": _lib.UBD_NA_MAX if q["aggregation"] == "max" else _lib.UBD_NA_AVG,
+              "curve_offset": pos}
+    return fields, np.concatenate(tables).astype(np.uint16)
+
+
 # --------------------------------------------------------------------------------------------------------------- device
 WARP_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("src_xpitch", np.int32), ("src_ypitch", np.int32),
                       ("src_w", np.int32), ("src_h", np.int32), ("dst_w", np.int32), ("dst_h", np.int32), ("mode", np.int32),
                       ("reserved", np.int32), ("coeffs", np.float64, (8,))], align=True)      # ubd_warp_desc of include/ubd.h
 PHOTO_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("w", np.int32), ("h", np.int32), ("mode", np.int32),
                        ("flags", np.int32), ("seed", np.uint64), ("p", np.int32, (24,))], align=True)   # ubd_photo_desc
+_NA_BRANCH = np.dtype([("kind", np.int32), ("p", np.int32, (9,))], align=True)
+_NA_GRID = np.dtype([("gw", np.int32), ("gh", np.int32), ("upscale", np.int32), ("reserved", np.int32), ("grid_offset", np.int64)], align=True)
+NOISE_ALPHA_DESC = np.dtype([("src_offset", np.int64), ("dst_offset", np.int64), ("w", np.int32), ("h", np.int32), ("iterations", np.int32),
+                             ("aggregation", np.int32), ("first", _NA_BRANCH), ("second", _NA_BRANCH), ("grid", _NA_GRID, (3,)),
+                             ("curve_offset", np.int64)], align=True)                            # ubd_noise_alpha_desc, 192 bytes
 
 
 class _View:
@@ -612,24 +802,76 @@ def _photometric_pass(jobs, c, device):
             v.rebind(out.data_ptr() + st, v.w, v.h, out)
 
 
+def fill_noise_alpha_desc(d, f, table_base=0):
+    """the fields of ``noise_alpha_descs`` into one element of a ``NOISE_ALPHA_DESC`` array, the table offsets moved by ``table_base``"""
+    d["iterations"], d["aggregation"], d["curve_offset"] = len(f["grids"]), f["aggregation"], f["curve_offset"] + table_base
+    for name in ("first", "second"):
+        d[name]["kind"] = f[name]["kind"]
+        d[name]["p"][:len(f[name]["p"])] = f[name]["p"]
+    for k, g in enumerate(f["grids"]):
+        d["grid"][k]["gw"], d["grid"][k]["gh"], d["grid"][k]["upscale"] = g["gw"], g["gh"], g["upscale"]
+        d["grid"][k]["grid_offset"] = g["grid_offset"] + table_base
+
+
+def _noise_alpha_pass(jobs, c, device):
+    """One ubd_noise_alpha_images call: jobs = [(view, descriptor fields, tables)].  The jobs' tables travel as one array in one
+    pinned, stream-ordered transfer; every image is written to one new device buffer and its view replaced."""
+    lib = _lib.load()
+    starts, pos = [], 0
+    for v, _, _ in jobs:
+        starts.append(pos)
+        pos += (v.w * v.h * c + 255) & ~255                       # every image on a 256-byte boundary: dword stores
+    out = torch.empty(max(pos, 1), dtype=torch.uint8, device=device)
+    size = [v.w * v.h * c for v, _, _ in jobs]
+    src_base = min(v.ptr for v, _, _ in jobs)
+    src_bytes = max(v.ptr + n for (v, _, _), n in zip(jobs, size)) - src_base
+    descs = np.zeros(len(jobs), NOISE_ALPHA_DESC)
+    table_base = 0
+    for k, (v, f, tab) in enumerate(jobs):
+        d = descs[k]
+        d["src_offset"], d["dst_offset"], d["w"], d["h"] = v.ptr - src_base, starts[k], v.w, v.h
+        fill_noise_alpha_desc(d, f, table_base)
+        curve = tab[f["curve_offset"]:f["curve_offset"] + 257]
+        # the device trusts the table values (include/ubd.h): grids are Q15 in 0..32768, the curve Q14 in 0..16384
+        assert tab.dtype == np.uint16 and int(tab[:f["curve_offset"]].max(initial=0)) <= 32768 and int(curve.max()) <= 16384
+        table_base += tab.size
+    tables = np.concatenate([tab for _, _, tab in jobs])
+    pinned = torch.empty(tables.size, dtype=torch.int16, pin_memory=True)
+    pinned.numpy()[:] = tables.view(np.int16)
+    dev_tables = pinned.to(device, non_blocking=True)             # stream-ordered; the pinned block is recycled in stream order
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(lib.ubd_noise_alpha_images(ctypes.c_void_p(src_base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data,
+                                              dev_tables.data_ptr(), dev_tables.numel(), c, len(jobs), stream), "ubd_noise_alpha_images")
+    for (v, _, _), st in zip(jobs, starts):
+        v.rebind(out.data_ptr() + st, v.w, v.h, out)
+
+
 def photometric_views_on_device(views, plans, owned, device):
     """Runs ``plan.photometric`` of every image on its packed view, slot by slot: one ubd_photometric_images call per slot over
-    the images that have a built stage there.  Pointwise stages run in place, neighbourhood stages (MEDIAN and ELASTIC among
-    them) go to a new buffer that is
+    the images that have a built stage there, and one ubd_noise_alpha_images call over those whose stage is a mask-blended one
+    (``NOISE_ALPHA_KINDS``).  Pointwise stages run in place, neighbourhood stages (MEDIAN, ELASTIC and the mask-blended ones
+    among them) go to a new buffer that is
     swapped in; a view whose pixels are not this module's (``owned[k]`` false: a caller's tensor that no warp pass copied) is
     never written: its first stage goes to a new buffer.  Stream-ordered, no host synchronisation."""
     c = views[0].c
     owned = list(owned)
     chains = [() if plan.original else tuple(plan.photometric) for plan in plans]
     for slot in range(max((len(ch) for ch in chains), default=0)):
-        jobs = []
+        jobs, na_jobs = [], []
         for k, (v, ch) in enumerate(zip(views, chains)):
+            if slot < len(ch) and ch[slot].kind in NOISE_ALPHA_KINDS:
+                na_jobs.append((v,) + noise_alpha_descs(ch[slot], v.w, v.h, c))
+                owned[k] = True
+                continue
             f = photometric_descs(ch[slot], v.w, v.h, c) if slot < len(ch) else None
             if f is not None:
                 jobs.append((v, f, owned[k] and f["mode"] in PHOTO_POINTWISE))
                 owned[k] = True
         if jobs:
             _photometric_pass(jobs, c, device)
+        if na_jobs:
+            _noise_alpha_pass(na_jobs, c, device)
     return views
 
 
@@ -676,16 +918,17 @@ class SegLinksImageAugmentation:
     ``random`` / ``numpy.random`` modules (or the given generators), runs its geometric chain on the MI355X and returns a PIL
     image of the same mode.  Nothing is drawn and nothing changes for empty markup.  The caller's markup objects are not
     mutated.  The photometric (imgaug) stage runs only with ``photo_rng`` (a ``numpy.random.Generator``; module docstring: the
-    built operations, those that ``photo_extended`` adds, the unbuilt ones, parity with imgaug / OpenCV unpinned); without it ``plan.photometric_requested`` says
+    built operations, those that ``photo_extended`` and ``photo_noise_alpha`` add, parity with imgaug / OpenCV unpinned); without it ``plan.photometric_requested`` says
     whether the reference would have run it.  Needs an MI355X (RuntimeError otherwise: no CPU fallback)."""
 
-    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None, photo_extended=False):
+    def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None, photo_extended=False,
+                 photo_noise_alpha=False):
         if not torch.cuda.is_available():
             raise RuntimeError("SegLinksImageAugmentation needs an MI355X; there is no CPU fallback")
         if image.mode not in ("L", "RGB"):
             raise ValueError(f"image mode must be 'L' or 'RGB', got {image.mode!r}")
         self.__net_config = net_config
-        self.plan = sample_plan(image.size, markup, rng, np_rng, photo_rng, photo_extended) if plan is None else plan
+        self.plan = sample_plan(image.size, markup, rng, np_rng, photo_rng, photo_extended, photo_noise_alpha) if plan is None else plan
         self.__aug_image, self.__aug_markup = image, markup
         if not self.plan.stages and (self.plan.original or not self.plan.photometric):
             return

@@ -8,7 +8,8 @@
 // no product is fused into a sum, and the tests excuse only pixels whose exact value lies within 1e-4 (1 + scale) of a rounding
 // boundary.
 //
-// Not built: SimplexNoiseAlpha and FrequencyNoiseAlpha (imgaug's noise-mask generators).
+// The two remaining entries of that stage, SimplexNoiseAlpha and FrequencyNoiseAlpha (two processed copies of the image blended
+// by a smooth random mask), are ubd_noise_alpha_images in noise_alpha.hip; photo_shared.h holds what the two files share.
 //
 // Four kernels, descriptors in the kernel arguments (PH_MAX_IMGS per launch, 88 bytes each), the block finds its image by the
 // first-block table, as in warp.hip:
@@ -55,19 +56,12 @@
 // 9 taps |tap| <= 13 16384 times 255: 9 13 16384 255 + 8192 < 4.9e8 < 2^31; SEP rows sum w v <= 16384 255 < 2^23, t <= 32640,
 // columns sum w t <= 16384 32640 + 2^20 < 2^30; BOX S <= 49 255, 2 S + k k < 2^15; HSV products <= 1 044 582; ELASTIC field sums
 // <= 16384 32768 + 8192 < 2^30, |aq s| <= 2^27, a row of the gather |sum W v| <= 255 (131072 + 2 x 14553) < 2^26.
-#include "common.h"
+#include "photo_shared.h"       // the tile shape, the clamps, ph_reflect, ph_keys: shared with noise_alpha.hip
 #include <algorithm>
 #include <cmath>
 
 #define PH_MAX_IMGS 32          // images per launch: 88 bytes of descriptor each in the kernel arguments (limit 4 KB)
-#define PH_MAX_SIDE 16384
-#define PH_THREADS 256
-#define PH_PX 4                 // pixels per lane
-#define PH_TW 64
-#define PH_TH 16
-#define PH_HALO 4
 #define PH_ROWS (PH_TH + 2 * PH_HALO)
-#define PH_MAX_TAP (13 * 16384)
 #define PH_MED_HALO 5           // MEDIAN: k <= 11
 #define PH_EL_RAW_PITCH 67      // ELASTIC: dwords per LDS row of the raw field (66 used) and of the row-pass result (64 used)
 #define PH_EL_ROW_PITCH 65
@@ -84,16 +78,6 @@ struct ph_launch {
     ph_image img[PH_MAX_IMGS];
     int32_t m;
 };
-
-__device__ __forceinline__ int ph_clamp(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-// clamp(v >> n, 0, 255) as a clamp of v followed by a logical shift of the non-negative value: the same number (the shift is
-// monotonic), and two instructions (v_med3_i32, v_lshrrev_b32) whose result needs no masking when the bytes are packed
-template <int N> __device__ __forceinline__ int ph_shift_clamp(int v)
-{
-    const int top = (256 << N) - 1;
-    v = v < 0 ? 0 : (v > top ? top : v);
-    return (int)((unsigned)v >> N);
-}
 
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"), counter (c0, 0, j, 0)
 __device__ __forceinline__ void ph_philox(uint32_t c0, uint32_t j, uint64_t seed, uint32_t r[4])
@@ -213,21 +197,6 @@ __global__ __launch_bounds__(PH_THREADS) void photo_point_kernel(const uint8_t *
             if (k < cnt * C) q[k] = o.bytes[k];
     }
 }
-
-__device__ __forceinline__ int ph_reflect(int i, int n)
-{
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
-template <int C> struct ph_tile_shape {
-    static constexpr int IN_PITCH = C == 3 ? 57 * 4 : 19 * 4;           // bytes; >= 3 + (PH_TW + 2 PH_HALO) C
-    static constexpr int IN_DWORDS = C == 3 ? 56 : 19;                  // dwords that can hold source bytes of one row
-    static constexpr int T_PITCH = PH_TW * C + 2;                       // ushorts: 97 / 33 dwords
-};
 
 template <int C>
 __global__ __launch_bounds__(PH_THREADS) void photo_tile_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, ph_launch L)
@@ -468,16 +437,6 @@ __global__ __launch_bounds__(PH_THREADS) void photo_median_kernel(const uint8_t 
 }
 
 // --------------------------------------------------------------------------------------------------------------- ELASTIC
-// Keys bicubic weights (a = -3/4) at phase k / 32 in Q17: exact integers that sum to 131072
-__device__ __forceinline__ void ph_keys(int k, int wgt[4])
-{
-    const int u = 32 - k;
-    wgt[0] = -3 * k * u * u;
-    wgt[1] = 5 * k * k * k - 288 * k * k + 131072;
-    wgt[2] = 5 * u * u * u - 288 * u * u + 131072;
-    wgt[3] = -3 * u * k * k;
-}
-
 __device__ __forceinline__ uint32_t ph_pack16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 __device__ __forceinline__ int ph_lo16(uint32_t v) { return (int)(int16_t)(v & 0xffffu); }
 __device__ __forceinline__ int ph_hi16(uint32_t v) { return (int)v >> 16; }

@@ -159,16 +159,19 @@ class SegmapManager:
         return [ClassifiedObjectMarkup(bbox, class_id) for bbox, class_id in zip(q, c)]
 
     @staticmethod
-    def prepare_image_and_target(image, markup, net_config, augment=False, photo_rng=None, photo_extended=False):
+    def prepare_image_and_target(image, markup, net_config, augment=False, photo_rng=None, photo_extended=False,
+                                 photo_noise_alpha=False):
         """segmap_manager.py:24-39: with ``augment``, the geometric chain of the reference's augmentation first (one PIL image
         through ``SegLinksImageAugmentation``: parameters from ``random`` / ``numpy.random``, pixels warped on the MI355X,
         bit-identical to Pillow; with ``photo_rng``, a ``numpy.random.Generator``, also the built operations of the imgaug
-        photometric stage, with ``photo_extended`` MedianBlur, AddToHueAndSaturation and ElasticTransformation among them --
+        photometric stage, with ``photo_extended`` MedianBlur, AddToHueAndSaturation and ElasticTransformation among them,
+        with ``photo_noise_alpha`` SimplexNoiseAlpha and FrequencyNoiseAlpha too --
         which are built, which are not, and that parity with imgaug / OpenCV is unpinned: ubdvss_amd/augmentation.py), then rescale image + markup to the network's size rule, build the label map at
         ``net_config.get_scale()``.  Returns (image, markup, label map) like the reference."""
         if augment:
             from .augmentation import SegLinksImageAugmentation
-            aug = SegLinksImageAugmentation(image, markup, net_config, photo_rng=photo_rng, photo_extended=photo_extended)
+            aug = SegLinksImageAugmentation(image, markup, net_config, photo_rng=photo_rng, photo_extended=photo_extended,
+                                            photo_noise_alpha=photo_noise_alpha)
             image, markup = aug.get_modified_image(), aug.get_modified_markup()
         image, markup = SegmapManager._rescale_image_and_markup(image, markup, net_config)
         return image, markup, SegmapManager.build_segmentation_map(image, markup, scale=net_config.get_scale())
@@ -343,7 +346,7 @@ class SegmapManager:
 
     @staticmethod
     def prepare_batches_on_device(images, markups, net_config, augment=True, plans=None, device=None, photo_rng=None,
-                                  photo_extended=False):
+                                  photo_extended=False, photo_noise_alpha=False):
         """Training form of ``prepare_image_and_target(..., augment=True)`` (+ ``convert('L')`` for grey nets) for a batch on
         the MI355X.  Augmented images no longer share one size, and the reference groups a batch by resized shape
         (data_generators.py:133-140), so the result is a list with one entry per target size, in order of first appearance:
@@ -351,13 +354,14 @@ class SegmapManager:
         rescaled markups, the plans), every list in the order of ``indices``.
         Chain: the raw images are staged once -> the warp passes of all images (``ubd_warp_images``: every rotation, then every
         perspective / final copy; crops and quarter turns are views) -> the photometric stages of the plans
-        (``ubd_photometric_images``, one call per slot) -> ``ubd_resize_images`` per group ->
+        (``ubd_photometric_images`` and ``ubd_noise_alpha_images``, one call each per slot) -> ``ubd_resize_images`` per group ->
         ``ubd_build_label_maps`` per group; no host synchronisation and no device-to-host copy in between.
         ``plans``: one ``AugmentationPlan`` per image to replay (tests, reproducibility); otherwise ``augment=True`` draws them
         with ``augmentation.sample_plan`` from ``random`` / ``numpy.random`` in image order, ``augment=False`` uses empty plans.
         ``photo_rng``: a ``numpy.random.Generator`` handed to ``sample_plan`` for the imgaug photometric stage (None: the stage's
         draw is consumed and recorded, no pixels change); ``photo_extended``: handed to ``sample_plan`` too, the stage then also
-        draws MedianBlur, AddToHueAndSaturation and ElasticTransformation (off: they stay recorded no-ops).  What of that stage is built, what is not, and that parity with imgaug /
+        draws MedianBlur, AddToHueAndSaturation and ElasticTransformation (off: they stay recorded no-ops); ``photo_noise_alpha``: likewise for
+        SimplexNoiseAlpha and FrequencyNoiseAlpha -- with both flags the whole stage of the reference runs.  What of that stage is built, what is not, and that parity with imgaug /
         OpenCV is unpinned: ubdvss_amd/augmentation.py.  Images as in ``rescale_images_on_device``."""
         if not torch.cuda.is_available():
             raise RuntimeError("SegmapManager.prepare_batches_on_device needs an MI355X; there is no CPU fallback")
@@ -374,7 +378,8 @@ class SegmapManager:
             srcs = [s if s.shape[2] == 3 else (s.expand(-1, -1, 3).contiguous() if isinstance(s, torch.Tensor) else np.repeat(s, 3, axis=2))
                     for s in srcs]
         if plans is None:
-            plans = [augmentation.sample_plan((s.shape[1], s.shape[0]), m, photo_rng=photo_rng, photo_extended=photo_extended) if augment
+            plans = [augmentation.sample_plan((s.shape[1], s.shape[0]), m, photo_rng=photo_rng, photo_extended=photo_extended,
+                                             photo_noise_alpha=photo_noise_alpha) if augment
                      else augmentation.identity_plan((s.shape[1], s.shape[0]))
                      for s, m in zip(srcs, markups)]
         warped = augmentation.augment_arrays_on_device(srcs, plans, device)
