@@ -439,6 +439,46 @@ int ubd_evaluate_pixels(const float *class_logits, int pixel_stride, int n_class
                         int8_t *mask, ubd_pixel_record *per_image,
                         void *accumulator, void *workspace, size_t workspace_bytes, void *stream);
 
+/* --- visualisations (semantic_segmentation/visualizations.py:20-151, Visualizer.compute_visualizations) -------------------
+ * The four overlays of a batch in one pass over the image pixels, from what the forward pass, the postprocess and the
+ * evaluation left in device memory.  Every overlay is draw_segmentation_map (:138-151), Image.composite(Image.blend(image,
+ * solid(color), 0.5), image, mask); for 8-bit images and a 0 / 255 mask that is exactly, per channel,
+ * out = (in + color) >> 1 where the mask is set and out = in elsewhere; green = (0, 255, 0), red = (255, 0, 0).
+ *   images     : device (n, height, width, channels), channels 1 or 3; a grey image becomes RGB by repeating the channel.
+ *                UBD_IN_U8: the pixels as they are.  UBD_IN_F32: the reference's denorm, then astype(uint8):
+ *                UBD_PRE_MOBILENET x * 127.5 + 127.5 in fp32 (product and sum rounded separately), UBD_PRE_NONE x itself; both
+ *                truncate toward zero.  Values outside [0, 255] are CLAMPED and NaN gives 0: numpy leaves that cast undefined,
+ *                this is the project's definition.  Float images must be 4-byte aligned.
+ *   maps       : (n, map_h, map_w) each; height = s map_h and width = s map_w for ONE integer s >= 1 (s = 1: the augmentation
+ *                preview, s = 4: the net's scale).  A map reaches image size as Image.resize(NEAREST) does for an integer
+ *                ratio, map[y / s][x / s].  Any other pair of sizes is refused: the general nearest ratio
+ *                floor((x + 0.5) map_w / width) is NOT built.
+ *   out_gt                 <- gt_labels (int32): green where the label > 0 (visualize_segmentation_map of the label maps, :108-123)
+ *   out_seg_map            <- binary_map (int32, the {0, 1} map of ubd_postprocess): green where the entry > 0
+ *   out_postprocessed      <- quads (n, cap, 8) int32 and counts (n), the outputs of ubd_postprocess: green inside every found quad,
+ *                             filled at image resolution with ImageDraw.polygon's rule (draw_bboxes / draw_markup :94-135 with
+ *                             build_segmentation_map(scale = 1, for_drawing = True); the rule ubd_build_label_maps matches to
+ *                             Pillow).  Identical to Pillow on convex quads, which is what ubd_postprocess finds.  Two known
+ *                             classes differ, for this call and ubd_build_label_maps alike: a quad whose opposite corners
+ *                             coincide, and rare self-intersecting slivers -- (23,17) (16,19) (25,17) (19,18), three rows
+ *                             high with two corners in its top row, leaves pixel (22, 17) unset where Pillow sets it
+ *                             (csrc/raster_fill.h; tests/test_raster_fill_host.py pins the example).  The quads are in
+ *                             the coordinates of `images` and may lie partly or wholly outside them; counts[i] > cap is clamped
+ *                             to cap as in ubd_build_label_maps.
+ *   out_classification_gt  <- cls_mask (int8, the mask of ubd_evaluate_pixels): green where +1, red where -1 (:82-91)
+ * Each output is (n, height, width, 3) uint8.  An output is written if and only if it and its source are non-NULL; an output
+ * given without its source is an error; with no output at all the call returns 0 and launches nothing.  Outputs must not
+ * overlap the images or each other.  Dword accesses are used where an address is a multiple of 4, bytes elsewhere: any byte
+ * alignment of the uint8 tensors works.
+ * Limits: n >= 1, sides 1..16384, n * height * width * 3 < 2^31, cap >= 1 with quads.  Every violation returns non-zero with
+ * ubd_last_error() set and launches nothing; all of them are checked before the first HIP call.
+ * One launch; no host synchronisation, no allocation, capturable in a HIP graph. */
+int ubd_visualize_images(const void *images, int in_dtype, int preprocessing, int n, int height, int width, int channels,
+                         int map_h, int map_w, const int32_t *gt_labels, const int32_t *binary_map,
+                         const int32_t *quads, const int32_t *counts, int cap, const int8_t *cls_mask,
+                         uint8_t *out_gt, uint8_t *out_seg_map, uint8_t *out_postprocessed, uint8_t *out_classification_gt,
+                         void *stream);
+
 /* --- data parallelism (no reference counterpart: the reference is single-device) -------------------
  * One process per GPU, per-replica loss (losses.py:86-126 applied to the rank's own images), ONE sum all-reduce of the flat
  * fp32 gradient vector per step over RCCL / xGMI, 1/world applied by ubd_adam_step's grad_scale, parameters broadcast once.

@@ -79,6 +79,7 @@ SIGNATURES = {
     "ubd_evaluate_pixels_accumulator_bytes": (_sz, []),
     "ubd_evaluate_pixels_workspace_bytes": (_sz, [_i, _i, _i]),
     "ubd_evaluate_pixels": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ubd_visualize_images": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ubd_comm_unique_id": (_i, [_vp]),
     "ubd_comm_init": (_i, [_vp, _vp, _i, _i, _i]),
     "ubd_comm_destroy": (_i, [_vp]),

@@ -14,7 +14,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize"
 pids=()
 for f in $UNITS; do
   [ -f $f.hip ] || continue
@@ -23,6 +23,8 @@ for f in $UNITS; do
   [ "$f" = "postprocess" ] && extra="-ffp-contract=off"
   # Pillow-exact float32 scan-line arithmetic: no FMA contraction
   [ "$f" = "raster" ] && extra="-ffp-contract=off"
+  # the same scan-line arithmetic (raster_fill.h) and the fp32 denorm x * 127.5 + 127.5 as numpy rounds it: no FMA contraction
+  [ "$f" = "visualize" ] && extra="-ffp-contract=off"
   # Pillow-exact double coefficient arithmetic of the bicubic resampler: no FMA contraction
   [ "$f" = "resize" ] && extra="-ffp-contract=off"
   # Pillow-exact double arithmetic of the generic transform and its bilinear filter: no FMA contraction

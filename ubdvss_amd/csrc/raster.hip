@@ -16,12 +16,7 @@
 //
 // One thread per map pixel; objects are tested in order and the last one that covers the pixel wins (painter's order).
 #include "common.h"
-
-struct rq_edge { int x0, y0, x1, y1, xmin, xmax, ymin, ymax; float dx; bool horiz; };
-
-__device__ __forceinline__ int rq_round_up(float f) { return f >= 0.f ? (int)floorf(__fadd_rn(f, 0.5f)) : -(int)floorf(__fadd_rn(fabsf(f), 0.5f)); }
-__device__ __forceinline__ int rq_round_down(float f) { return f >= 0.f ? (int)ceilf(__fsub_rn(f, 0.5f)) : -(int)ceilf(__fsub_rn(fabsf(f), 0.5f)); }
-__device__ __forceinline__ float rq_x_at(const rq_edge &e, int y) { return __fadd_rn(__fmul_rn((float)(y - e.y0), e.dx), (float)e.x0); }
+#include "raster_fill.h"       // rq_covers: the scan-line rule, shared with visualize.hip
 
 // segmap_manager.py:96 + :106-133 on float64 markup: bbox / scale (IEEE double division, what numpy does for the reference),
 // then floor a coordinate when at least two of the four coordinates on the same axis are strictly larger, else ceil
@@ -37,77 +32,6 @@ __device__ void rq_proper_round(const double *bbox, int scale, int *out)
         for (int j = 0; j < 4; ++j) larger += v[2 * j + (k & 1)] > v[k] ? 1 : 0;
         out[k] = (int)(larger > 1 ? floor(v[k]) : ceil(v[k]));
     }
-}
-
-// Is pixel (px, py) inside ImageDraw.polygon(pts) on a canvas of map_h rows?  One scan line of Pillow's polygon fill
-// (oracle/label_raster.py fill_polygon is the sequential statement of the same rule).
-__device__ bool rq_covers(const int *pts, int px, int py, int map_h)
-{
-    rq_edge e[4];
-    int ymin = map_h - 1, ymax = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        rq_edge &d = e[i];
-        d.x0 = pts[2 * i]; d.y0 = pts[2 * i + 1]; d.x1 = pts[(2 * i + 2) & 7]; d.y1 = pts[(2 * i + 3) & 7];
-        d.xmin = min(d.x0, d.x1); d.xmax = max(d.x0, d.x1); d.ymin = min(d.y0, d.y1); d.ymax = max(d.y0, d.y1);
-        d.horiz = d.y0 == d.y1;
-        d.dx = d.horiz ? 0.f : __fdiv_rn((float)(d.x1 - d.x0), (float)(d.y1 - d.y0));
-        ymin = min(ymin, d.ymin); ymax = max(ymax, d.ymax);
-        if (d.horiz && py == d.y0 && px >= d.xmin && px <= d.xmax) return true;       // horizontal edges are drawn as they are
-    }
-    ymin = max(ymin, 0); ymax = min(ymax, map_h);
-    if (py < ymin || py > ymax) return false;
-    // intersections of this scan line in edge order; an edge's lower end point counts twice (except in the last row)
-    float xx[8];
-    int last[4], act[4], na = 0, nx = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (e[i].horiz || py < e[i].ymin || py > e[i].ymax) continue;
-        const float x = rq_x_at(e[i], py);
-        xx[nx++] = x;
-        if (py == e[i].ymax && py < ymax) xx[nx++] = x;
-        act[na] = i; last[na] = nx - 1; ++na;
-    }
-    // "connect discontiguous corners": two edges leaning to the same side that both start in one point of this row (in the
-    // last row: both end there) -- the later edge's intersection moves towards the span of the neighbouring row
-    for (int bi = 1; bi < na; ++bi) {
-        const rq_edge &b = e[act[bi]];
-        if (b.dx == 0.f) continue;
-        const int bex = b.y0 == py ? b.x0 : b.x1, bey = b.y0 == py ? b.y0 : b.y1;
-        for (int ai = 0; ai < bi; ++ai) {
-            const rq_edge &a = e[act[ai]];
-            if ((b.dx > 0.f && a.dx <= 0.f) || (b.dx < 0.f && a.dx >= 0.f)) continue;
-            const bool top = a.ymin == py && b.ymin == py && py < ymax;
-            const bool bottom = a.ymax == py && b.ymax == py && py == ymax;
-            if (top == bottom) continue;
-            const int aex = a.y0 == py ? a.x0 : a.x1, aey = a.y0 == py ? a.y0 : a.y1;
-            if (aex != bex || aey != bey) continue;
-            const float v = (float)aex;
-            const int ya = top ? py + 1 : py - 1;
-            const float xa = rq_x_at(a, ya), xb = rq_x_at(b, ya);
-            const float lo = fminf(xa, xb), hi = fmaxf(xa, xb);
-            if (lo > v) xx[last[bi]] = fmaxf(v, (float)(rq_round_up(lo) - 1));
-            else if (hi < v) xx[last[bi]] = fminf(v, __fadd_rn(hi, 1.f));
-            break;
-        }
-    }
-    for (int a = 1; a < nx; ++a) {                                   // insertion sort, nx <= 8
-        const float v = xx[a];
-        int b = a - 1;
-        while (b >= 0 && xx[b] > v) { xx[b + 1] = xx[b]; --b; }
-        xx[b + 1] = v;
-    }
-    int x_pos = nx ? (int)xx[0] : 0;
-    for (int i = 1; i < nx; i += 2) {
-        const int x_end = rq_round_down(xx[i]);
-        if (x_end < x_pos) continue;
-        int x_start = rq_round_up(xx[i - 1]);
-        if (x_pos > x_start) { x_start = x_pos; if (x_end < x_start) continue; }
-        if (x_start > x_end) continue;
-        if (px >= x_start && px <= x_end) return true;
-        x_pos = x_end + 1;
-    }
-    return false;
 }
 
 __global__ __launch_bounds__(256) void build_label_maps_kernel(const double *__restrict__ quads, const int *__restrict__ values,

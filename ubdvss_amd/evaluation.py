@@ -10,7 +10,8 @@ The pixel classification accuracies of ``_calc_pixel_classification_correctness_
 sums go to a second small accumulator and the correctness mask comes back as a device tensor.
 There is no CPU path: without a GPU the entry points raise ``RuntimeError``.
 
-Not here: ``ImageResultCategories``, visualisations, non-convex ground truth.
+``ImageResultCategories`` (:579-628) sorts an image's result into the folders the result saver writes; the overlays themselves
+are ``ubdvss_amd.visualizations``.  Not here: non-convex ground truth.
 """
 import ctypes
 import math
@@ -575,3 +576,55 @@ class DatasetMetricCalculator:
         for name in ("average_iou_by_area", "average_precision_by_area", "average_recall_by_area"):
             logs[name] = getattr(lowest, name)
         return logs
+
+
+class ImageResultCategories:
+    """The folders a result saver sorts an image's result into (the role of evaluation.py:579-628; the four names, the tuple
+    SUITABLE_CATEGORIES and the three getters are the interface).  A category applies to an image when its test holds at
+    ERROR_IOU_THRESHOLD and it is one of SUITABLE_CATEGORIES: precision errors are tested but not saved at present."""
+    RECALL_ERROR = 'errors/recall'
+    PRECISION_ERROR = 'errors/precision'
+    DETECTION_RATE_ERROR = 'errors/detection_rate'
+    ALL = 'all'
+
+    SUITABLE_CATEGORIES = (RECALL_ERROR, DETECTION_RATE_ERROR, ALL)
+
+    @classmethod
+    def _from_scores(cls, detection_rate, precision, recall):
+        """the applicable categories, in the order detection rate, precision, recall, all"""
+        tests = ((cls.DETECTION_RATE_ERROR, detection_rate < 1), (cls.PRECISION_ERROR, precision < 1),
+                 (cls.RECALL_ERROR, recall < 1), (cls.ALL, True))
+        return [name for name, applies in tests if applies and name in cls.SUITABLE_CATEGORIES]
+
+    @classmethod
+    def get_categories(cls, metrics):
+        """metrics: the FtMetrics of one image"""
+        precision, recall, _ = metrics.get_metrics()
+        return cls._from_scores(metrics.detection_rate, precision, recall)
+
+    @classmethod
+    def get_batch_categories(cls, records, iou_threshold=None):
+        """The categories of every image of a batch from the device records ``evaluate_batch`` returned ((n, T, 80) uint8), at
+        ``iou_threshold`` (default DatasetMetricCalculator.ERROR_IOU_THRESHOLD, the threshold evaluation.py:498 selects), with ONE
+        read of the records.  An image that was not scored (flags != 0) raises RuntimeError, as ``get_metrics`` does."""
+        wanted = DatasetMetricCalculator.ERROR_IOU_THRESHOLD if iou_threshold is None else iou_threshold
+        columns = [t for t, value in enumerate(DatasetMetricCalculator.IOU_THRESHOLDS) if math.isclose(value, wanted)]
+        if len(columns) != 1:
+            raise ValueError(f"{wanted} is not one of the evaluated IoU thresholds")
+        per_image = []
+        for i, r in enumerate(records_to_numpy(records)[:, columns[0]]):
+            if r["flags"]:
+                raise RuntimeError(f"image {i} of the batch was not scored (flags {int(r['flags'])}): more found objects than "
+                                   "max_objects_per_image, or malformed ground truth")
+            precision, recall, _ = detection_scores(int(r["tp"]), int(r["fp"]), int(r["fn"]))
+            per_image.append(cls._from_scores(int(r["detection_rate"]), precision, recall))
+        return per_image
+
+    @classmethod
+    def get_errors(cls, visualization_categories):
+        """the categories given without ALL: the error folders only"""
+        return list(filter(lambda name: name != cls.ALL, visualization_categories))
+
+    @classmethod
+    def get_folders(cls):
+        return cls.SUITABLE_CATEGORIES

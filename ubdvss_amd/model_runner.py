@@ -113,6 +113,77 @@ class ModelRunner:
                                      meta_infos=meta_infos, scales=scales)
         return evaluator.get_metrics()
 
+    def run(self, model, batches, n_images, save_dir=None, save_visualizations=False, rng=None):
+        """The contract of the reference's ModelRunner.run (model_runner.py:40-103): metrics, saved results and visualisations
+        of up to ``n_images`` images.  ``batches``: an iterable of batches in the form ``evaluate_batches`` takes,
+        (images, gt_objects, meta_infos[, gt_segmap]); it is read until ``n_images`` images have been seen (or it ends).  Per
+        batch the forward pass, the postprocess, the evaluation and -- where a batch is drawn -- the four overlays
+        (ubd_visualize_images) run on the device; the found objects are drawn in the coordinates of the images given and scored
+        in the originals' (meta.xscale / meta.yscale).  gt_segmap may be a host array: it is uploaded once per use.
+        Without ``save_dir`` the one batch that holds a randomly drawn image index is visualised; the index comes from ``rng``, a
+        numpy.random.Generator (unseeded when None, as the reference's np.random.randint).  With ``save_dir`` (then meta_infos
+        are required: they name the files) the ground truth and the found objects of every image are written as CSV and, with
+        ``save_visualizations``, every image is saved into the folders of its ImageResultCategories at ERROR_IOU_THRESHOLD.
+        Returns (scalar_logs, visualizations): the dict of ``get_metrics`` and the last batch drawn as {'gt' (with label maps),
+        'seg_map', 'postprocessed'[, 'classification_gt']} of device uint8 tensors (N, H, W, 3) ({} when none was drawn)."""
+        from .evaluation import DatasetMetricCalculator, ImageResultCategories
+        from .result_saver import ResultSaver
+        from .visualizations import Visualizer
+        metrics = DatasetMetricCalculator(self._net_config)
+        writer = ResultSaver(save_dir, save_visualizations)
+        generator = np.random.default_rng() if rng is None else rng
+        preview_index = int(generator.integers(0, n_images))       # drawn even when save_dir makes it unused: one draw per run
+        drawn = {}
+        first = 0                                                   # index of the batch's first image in the run
+        for batch in batches:
+            if first >= n_images:
+                break
+            images, gt_objects, meta_infos = batch[:3]
+            labels = batch[3] if len(batch) > 3 else None
+            if save_dir and meta_infos is None:
+                raise AssertionError("save_dir needs meta_infos: they name the files")
+            if meta_infos is not None and len(meta_infos) != len(images):
+                raise AssertionError("one meta_info per image is required")
+            x = self._batch_to_device(model, images)
+            logits, binary_map, quads, classes, counts = self.predict_on_device(model, x)
+            self.flush()                                # pipelined runner: this batch's postprocess before its evaluation
+            scales = None if meta_infos is None else np.array([[m.xscale, m.yscale] for m in meta_infos], dtype=np.float64)
+            records, mask = metrics.evaluate_batch(gt_objects, (quads, classes, counts), gt_segmap=labels,
+                                                   classification_logits=logits if labels is not None else None,
+                                                   meta_infos=meta_infos, scales=scales)
+            folders = None
+            if save_dir:
+                writer.save_gt_and_prediction(gt_objects, self.rescale(self._found_lists(quads, classes, counts), meta_infos), meta_infos)
+                folders = ImageResultCategories.get_batch_categories(records)
+                draw_it = bool(save_visualizations) and any(len(f) > 0 for f in folders)
+            else:
+                draw_it = first <= preview_index < first + len(x)
+            if draw_it:
+                drawn = Visualizer.compute_visualizations_on_device(x, labels, binary_map, (quads, counts), mask,
+                                                                    preprocessing=self._net_config.get_preprocessing_type())
+                if folders is not None:
+                    writer.save_visualizations(folders, meta_infos, drawn)
+            first += len(x)
+        return metrics.get_metrics(), drawn
+
+    @staticmethod
+    def _batch_to_device(model, images):
+        """a batch as ``predict`` takes it (numpy or tensor; uint8 raw pixels, anything else float32) on the model's device"""
+        if not torch.is_tensor(images):
+            x = np.asarray(images)
+            if x.dtype != np.uint8:
+                x = x.astype(np.float32, copy=False)
+            images = torch.from_numpy(np.ascontiguousarray(x))
+        return images.to(model.device)
+
+    def _found_lists(self, quads, classes, counts):
+        """device results -> host object lists (one read of each tensor); raises when an image overflowed the capacity"""
+        counts_h = counts.cpu().numpy()
+        if (counts_h > self._cap).any():
+            raise RuntimeError(f"more than max_objects_per_image={self._cap} objects in an image "
+                               f"(max found {int(counts_h.max())}); raise the capacity")
+        return self._object_lists(counts_h, quads.cpu().numpy(), classes.cpu().numpy() if classes is not None else None)
+
     def predict(self, model, images, rescale=False, meta_infos=None):
         """Same contract as the reference (model_runner.py:105-138): returns
         (detection map (N,h,w,1) of {0,1}, classification_logits (N,h,w,n_cls), found_objects)."""
