@@ -57,9 +57,9 @@ struct env_switch { const char *name; size_t field; const char *value; int set; 
 static const env_switch ENV_SWITCHES[] = {
     SW("UBD_DILCONV", use_wino, "direct", 0), SW("UBD_DILCONV", wino_x6, "direct", 0), SW("UBD_DILCONV", wino_x6, "wino32", 0),
     SW("UBD_WINO6_LAYOUT", wino6_natural, "natural", 1),
-    SW("UBD_STEM", fuse_stem, "fused", 1), SW("UBD_STEM", fuse_force, "fused", 1),
-    SW("UBD_STEM", fuse_stem, "fused123", 2), SW("UBD_STEM", fuse_force, "fused123", 1),
-    SW("UBD_STEM", fuse_stem, "unfused", 0),
+    SW("UBD_STEM", fuse_stem, "fused", UBD_STEM_FUSED23), SW("UBD_STEM", fuse_force, "fused", 1),
+    SW("UBD_STEM", fuse_stem, "fused123", UBD_STEM_FUSED123), SW("UBD_STEM", fuse_force, "fused123", 1),
+    SW("UBD_STEM", fuse_stem, "unfused", UBD_STEM_SEPARATE),
     SW("UBD_TEST_NUM_CUS", num_cus, NUMBER, 0),
     SW("UBD_DILBWD", split_dilbwd, "split", 1), SW("UBD_DILBWD", no_pair_dilbwd, "pair8", 1),
     SW("UBD_SEPBWD", split_sepbwd32, "split", 1),
@@ -95,7 +95,7 @@ extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
     h->k_out = 1 + cfg->n_classes;
     h->num_cus = prop.multiProcessorCount;
     h->use_wino = h->wino_x6 = h->chain_reduce = 1;             // the defaults that are not 0
-    h->fuse_stem = cfg->fml_compatible != 0 ? 2 : 0;
+    h->fuse_stem = cfg->fml_compatible != 0 ? UBD_STEM_FUSED123 : UBD_STEM_SEPARATE;
     for (const env_switch &sw : ENV_SWITCHES) {
         const char *e = getenv(sw.name);
         if (!e) continue;
@@ -103,7 +103,7 @@ extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
         if (sw.value == NUMBER) { if (atoi(e) > 0) *field = atoi(e); }
         else if (sw.value == ANY || strcmp(e, sw.value) == 0) *field = sw.set;
     }
-    { const char *s = getenv("UBD_STEM"); if (s && strcmp(s, "cold123") == 0 && cfg->fml_compatible != 0) { h->fuse_stem = 3; h->fuse_force = 1; } }      // fml padding only
+    { const char *s = getenv("UBD_STEM"); if (s && strcmp(s, "cold123") == 0 && cfg->fml_compatible != 0) { h->fuse_stem = UBD_STEM_COLD123; h->fuse_force = 1; } }      // fml padding only: not a table row
     // Keras model.get_weights() order
     size_t off = 0;
     int cin = cfg->c_in;

@@ -4,7 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/ubd.h"
+#include "stem_plan.h"
 
 #define UBD_C 24              // n_filters (net.py:289)
 #define UBD_NUM_DIL 6         // dense dilated layers L4..L9 (net.py:298-304)
@@ -36,12 +38,7 @@ struct ubd_handle {
     int split_sepbwd32;       // UBD_SEPBWD=split: fp32 train step with the stand-alone data-gradient kernels of the separable layers (sep_dx_kernel) instead of G tiles built inside the weight-gradient kernels (diagnostics / tests)
     int chain_reduce;         // 1 (default): bf16 train step: weight-gradient kernels total the previous producer's partial rows at their end (0, UBD_REDUCE=batched: the two stand-alone launches)
     int direct_dil16;         // UBD_DILCONV16=direct: 16-bit forward dilated layers with the direct (unstaged) kernel (diagnostics / tests)
-    // Inference stem: 2 = L1 -> L2 -> L3 in one kernel (stem123.h; UBD_STEM=fused123), 3 = that kernel with one cold-started tile per work unit
-    // (UBD_STEM=cold123, fml padding only; what 2 takes by itself for small launches), 1 = L1, then L2 -> L3 fused with L2's output in LDS (stem23.h;
-    // UBD_STEM=fused), 0 = three kernels (UBD_STEM=unfused).  Default: 2 with the fml padding (the variant that inherits the 33rd L2 column from the tile
-    // to its left: 0.405 vs 0.417 ms per forward pass at 32 x 512 x 512), else 0 -- with TF 'same' padding the fused kernel only ties the separate
-    // kernels.  Training always runs the separate kernels.
-    int fuse_stem;
+    int fuse_stem;            // UBD_STEM_*: the inference stem, with fuse_force the input of ubd_plan_stem (stem_plan.h, where both are defined)
     int use_wino;             // 1: Winograd F(2x2,3x3) dilated layers (default), 0: direct implicit GEMM (UBD_DILCONV=direct)
     int loss_chain;           // UBD_LOSS=chain: the loss as its five dependent launches (the batch-global mode's form) instead of the one-launch kernel (diagnostics / tests)
     int wino_x6;              // forward Winograd products as three-way bf16 split products on the bf16 MFMA (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
@@ -189,6 +186,24 @@ void ubd_set_error(const char *fmt, ...);
 
 static inline size_t ubd_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the stems' input: fp32 pixels fed as they are go to LDS by DMA in 16-byte pieces -- byte offsets inside one image below `limit` (what
+// the kernel's offset arithmetic holds), 16-byte aligned base (an offset view of a tensor takes the register-staged variant)
+static inline bool ubd_pixels_by_lds_dma(bool f32_in, float sub, float div, int H, int W, int c_in, size_t limit, const void *x)
+{
+    return f32_in && sub == 0.f && div == 1.f && (size_t)H * W * c_in * 4 < limit && ((uintptr_t)x & 15) == 0;
+}
+// a single output channel: the head can ride in the epilogue of L9 (its 24 weights and its bias are adjacent in the parameter vector)
+static inline bool ubd_head_in_epilogue(const ubd_handle *h) { return h->k_out == 1 && h->off_head_b == h->off_head_k + UBD_C; }
+// run-time values as template arguments of a launch: f(std::true_type or std::false_type) ...
+template <int V> using ubd_int = std::integral_constant<int, V>;
+template <typename F> static inline void ubd_dispatch_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// ... and f(ubd_int c_in, ubd_int u8): the input forms the stem kernels are built for (c_in 1 or 3: ubd_create)
+template <typename F> static inline void ubd_dispatch_input(int c_in, bool u8, F f)
+{
+    if (c_in == 1) { if (u8) f(ubd_int<1>{}, ubd_int<1>{}); else f(ubd_int<1>{}, ubd_int<0>{}); }
+    else { if (u8) f(ubd_int<3>{}, ubd_int<1>{}); else f(ubd_int<3>{}, ubd_int<0>{}); }
+}
+
 // ---- workspace carving (all offsets 256-byte aligned) -------------------------------
 // packed MFMA weight fragments, see forward.hip
 #define UBD_DIL_FRAG_FLOATS (9 * 6 * 2 * 64)     // per dilated layer
@@ -229,7 +244,6 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
 int ubd_pp_fill_job(ubd_handle *hd, const float *logits, int n, int map_h, int map_w, float logit_threshold, int scale, float min_area,
                     int32_t *binary_map, int32_t *quads, int32_t *classes, int32_t *counts, int cap, void *workspace,
                     size_t workspace_bytes, int threads, pp_lds_args *job);
-bool ubd_forward_uses_fused_stem(const ubd_handle *h, int n, int H, int W);
 void ubd_launch_dilconv(const ubd_handle *h, int epi, const float *frag, const float *aux, int dilation,
                         const float *in, float *out, int n, int H4, int W4, hipStream_t st);
 int ubd_grid_for(long waves_needed, int num_cus, int waves_per_block, int blocks_per_cu);

@@ -442,6 +442,9 @@ __global__ __launch_bounds__(256, (CIN == UBD_C) ? (STRIDE == 1 ? 3 : 2) : 5) vo
 #ifdef UBD_STAMPS   // diagnostic build only: device buffer that receives in-kernel s_memtime stamps
 static unsigned long long *g_ubd_stamps = nullptr;
 extern "C" void ubd_debug_set_stamps(void *p) { g_ubd_stamps = (unsigned long long *)p; }
+#define UBD_STAMP_ARG(p) , p       // the stem kernels' last parameter exists in the diagnostic build only
+#else
+#define UBD_STAMP_ARG(p)
 #endif
 #include "pp_lds.h"
 #include "stem23.h"
@@ -655,10 +658,9 @@ static void launch_sep(const ubd_handle *h, const void *x, int in_u8, float *y, 
     const int per_cu = (CIN == UBD_C) ? (STRIDE == 1 ? 3 : 2) : 5;   // register / LDS-limited residency
     int grid = h->num_cus * per_cu;
     if (grid > tiles || CIN != UBD_C) grid = tiles;      // 1/3 channels: one tile per block, residency (not a register prefetch) hides the load latency
-    if (in_u8)
-        hipLaunchKernelGGL((sepconv_kernel<CIN, STRIDE, 1>), dim3(grid), dim3(256), 0, st, x, y, frag, bias, n, H, W, OH, OW, pad_lo, sc, sh);
-    else
-        hipLaunchKernelGGL((sepconv_kernel<CIN, STRIDE, 0>), dim3(grid), dim3(256), 0, st, x, y, frag, bias, n, H, W, OH, OW, pad_lo, sc, sh);
+    ubd_dispatch_bool(in_u8 != 0, [&](auto u8) {
+        hipLaunchKernelGGL((sepconv_kernel<CIN, STRIDE, decltype(u8)::value>), dim3(grid), dim3(256), 0, st, x, y, frag, bias, n, H, W, OH, OW, pad_lo, sc, sh);
+    });
 }
 
 void ubd_launch_pack_direct(const ubd_handle *h, const float *params, float *wfrag, hipStream_t st)
@@ -672,11 +674,7 @@ void ubd_launch_pack_direct(const ubd_handle *h, const float *params, float *wfr
 
 static void launch_pack(const ubd_handle *h, const float *params, float *wfrag, hipStream_t st)
 {
-    pack_args pa;
-    for (int s = 0; s < 3; ++s) { pa.off_sep_dw[s] = h->off_sep_dw[s]; pa.off_sep_pw[s] = h->off_sep_pw[s]; }
-    for (int k = 0; k < UBD_NUM_DIL; ++k) pa.off_dil_k[k] = h->off_dil_k[k];
-    pa.c_in = h->cfg.c_in;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(64), dim3(256), 0, st, params, wfrag, pa);
+    ubd_launch_pack_direct(h, params, wfrag, st);
     if (h->use_wino) ubd_launch_pack_wino(h, params, wfrag + UBD_FWD_DIRECT_FLOATS, 0, st);
     if (h->wino_x6) ubd_launch_pack_wino6(h, params, (unsigned *)(wfrag + UBD_FWD_WINO6_OFF), st);
 }
@@ -739,26 +737,40 @@ extern "C" int ubd_dilated_layer(ubd_handle *h, const float *params, int layer, 
     return 0;
 }
 
-// Runs L1..L9 + head.  acts[0..8] receive the hidden activations (L1..L9 outputs).
-static bool fused_stem_applies(const ubd_handle *h, int n, int H)
+// shape / in_dtype checks shared by the fp32 and the 16-bit entries (in_dtype may carry UBD_IN_PREPACKED)
+static int check_forward_input(int n, int H, int W, int in_dtype)
 {
-    // the fused stem kernels give every CU whole strips of tiles (n * H4 / 4 of them): they need ~2 strips per CU to fill the chip
-    // (a single 512 x 512 image has 32); smaller launches take the three separate kernels unless UBD_STEM forces a variant
-    const int H4 = H / 4;
-    const long stem_strips = (long)n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3);
-    const bool stem_big = h->fuse_force || stem_strips >= 2L * h->num_cus;
-    return stem_big && h->fuse_stem == 2 && h->cfg.fml_compatible != 0;
+    UBD_REQUIRE(n > 0 && H > 0 && W > 0 && (H % 4) == 0 && (W % 4) == 0, "ubd_forward: height and width must be positive multiples of 4 (got %d x %d)", H, W);
+    UBD_REQUIRE((in_dtype & ~UBD_IN_PREPACKED) == UBD_IN_F32 || (in_dtype & ~UBD_IN_PREPACKED) == UBD_IN_U8, "ubd_forward: bad in_dtype %d", in_dtype);
+    return 0;
 }
-// launches too small for strips (one image: 32 strips for 256 CUs): the same kernel with ONE tile as its work unit (stem123.h, COLD) instead of
-// three separate launches; UBD_STEM=cold123 forces it at any size (tests)
-static bool cold_stem_applies(const ubd_handle *h, int n, int H)
-{
-    if (h->cfg.fml_compatible == 0) return false;
-    if (h->fuse_stem == 3) return true;
-    return h->fuse_stem == 2 && !h->fuse_force && !fused_stem_applies(h, n, H);
-}
-bool ubd_forward_uses_fused_stem(const ubd_handle *h, int n, int H, int W) { (void)W; return h->cfg.dtype == UBD_F32 && fused_stem_applies(h, n, H); }
 
+// L1 -> L2 -> L3 in one kernel (stem123.h): neither a1 nor a2 is touched.  COLD: one cold-started tile per work unit, tiles of a row 15 L3
+// columns apart, no tickets, no job; else every block walks whole strips and `job` (may be null) rides along
+template <bool COLD>
+static void launch_stem123(const ubd_handle *h, const float *params, const void *images, bool u8, float *a3, const float *sf0, const float *sf1,
+                           const float *sf2, int n, int H, int W, float sc, float sh, long units, int *ticket, const pp_lds_args *job, int a3_l2p,
+                           hipStream_t st)
+{
+    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+    const int grid = units < h->num_cus ? (int)units : h->num_cus;       // one 8-wave block per CU (LDS)
+    pp_lds_args pj;
+    memset(&pj, 0, sizeof(pj));                                  // n = 0: no postprocess job rides along
+    if (job) pj = *job;
+    const float *b0 = params + h->off_sep_b[0], *b1 = params + h->off_sep_b[1], *b2 = params + h->off_sep_b[2];
+    const bool plain = ubd_pixels_by_lds_dma(!u8, sc, sh, H, W, h->cfg.c_in, 1ull << 30, images);   // offsets of one image in 30 bits
+    ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
+        auto launch = [&](auto pl) {
+            hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD>), dim3(grid), dim3(s23_cfg::NT), 0, st,
+                               images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p
+                               UBD_STAMP_ARG(COLD ? (unsigned long long *)nullptr : g_ubd_stamps));
+        };
+        if constexpr (decltype(in_u8)::value == 0) { if (plain) return launch(ubd_int<1>{}); }
+        launch(ubd_int<0>{});
+    });
+}
+
+// Runs L1..L9 + head.  acts[0..8] receive the hidden activations (L1..L9 outputs).
 int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
                      int n, int H, int W, float *logits, char *ws, const ubd_fwd_layout &L, hipStream_t st, bool inference,
                      const pp_lds_args *pp_job)
@@ -766,8 +778,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     UBD_REQUIRE(h->cfg.dtype == UBD_F32, "ubd_forward: only UBD_F32 activations are implemented in this build");
     const bool prepacked = (in_dtype & UBD_IN_PREPACKED) != 0;
     in_dtype &= ~UBD_IN_PREPACKED;
-    UBD_REQUIRE(n > 0 && H > 0 && W > 0 && (H % 4) == 0 && (W % 4) == 0, "ubd_forward: height and width must be positive multiples of 4 (got %d x %d)", H, W);
-    UBD_REQUIRE(in_dtype == UBD_IN_F32 || in_dtype == UBD_IN_U8, "ubd_forward: bad in_dtype %d", in_dtype);
+    if (int rc = check_forward_input(n, H, W, in_dtype)) return rc;
     UBD_REQUIRE(!(in_dtype == UBD_IN_U8 && h->cfg.c_in == UBD_C), "ubd_forward: u8 input needs c_in 1 or 3");
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
     // the Winograd kernel marks out-of-image rows / columns with 2^30 offset terms: a quarter-resolution activation must
@@ -792,98 +803,51 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     if (preprocessing == UBD_PRE_MOBILENET) { sc = 127.5f; sh = 127.5f; }
     const int u8 = in_dtype == UBD_IN_U8;
     float *cur = (float *)(ws + L.off_acts[0]);
-    const long stem_strips = (long)n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3);
-    const bool stem_big = h->fuse_force || stem_strips >= 2L * h->num_cus;
-    const bool fuse_all = inference && fused_stem_applies(h, n, H);
-    UBD_REQUIRE(!pp_job || fuse_all, "ubd_forward: a postprocess job needs the fused stem kernel (internal error)");
-    const bool cold_all = inference && !fuse_all && !pp_job && cold_stem_applies(h, n, H);
+    static_assert(UBD_STEM_STRIP_ROWS == s23_cfg::TH3, "stem_plan.h counts the strips the stem kernels walk");
+    const ubd_stem_plan plan = ubd_plan_stem(h->fuse_stem, h->fuse_force != 0, h->cfg.fml_compatible != 0, h->num_cus, n, H, inference, pp_job != nullptr);
+    UBD_REQUIRE(!plan.job_without_strips, "ubd_forward: a postprocess job needs the fused stem kernel (internal error)");
+    const bool one_kernel = plan.form == UBD_STEM_FORM_STRIPS || plan.form == UBD_STEM_FORM_COLD;
     // Column layouts of a3 and L4..L8's outputs (wino6.hip, P_p): L4, L5 and L9 (dilation d = 1, 2, 1) read P_2d, where one sample load
     // covers one run of 16 pixels instead of 16 pixels d apart.  L4 stores P_4 (runs of 8), L5 stores the natural order (16 pixels 4
     // apart) that L6..L8 read as before (d >= 4: runs of 4..16 already), L8 stores P_2 (runs of 8) for L9, and L9 stores natural logits
     // or activations.  L6 reading P_8 (runs of 8 from L5, 16 pixels 8 apart in its own stores) measured 0.8 us slower per pass.  Only with
     // the one-kernel stem, which writes a3, and the bf16-split Winograd layers; every other path keeps the natural order throughout.
     static const int phase_lay[UBD_NUM_DIL + 1] = {2, 4, 1, 1, 1, 2, 1};
-    const bool phase_major = h->wino_x6 && !h->wino6_natural && (fuse_all || cold_all);
+    const bool phase_major = h->wino_x6 && !h->wino6_natural && one_kernel;
     const int a3_l2p = phase_major ? 1 : 0;
-    if (cold_all) {
-        // L1 -> L2 -> L3 in one kernel, one cold-started tile per work unit (stem123.h COLD): tiles of a row 15 L3 columns apart
-        const long tiles = (long)n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3) * (W4 <= 16 ? 1 : 1 + (W4 - 16 + 14) / 15);
-        int grid = h->num_cus;
-        if (grid > tiles) grid = (int)tiles;
-        pp_lds_args pj;
-        memset(&pj, 0, sizeof(pj));
-        const float *b0 = params + h->off_sep_b[0], *b1 = params + h->off_sep_b[1], *b2 = params + h->off_sep_b[2];
-        int *ticket = (int *)(ws + L.off_tickets);               // not touched by this form
-#ifdef UBD_STAMPS
-#define S123C_STAMP_ARG , (unsigned long long *)nullptr
-#else
-#define S123C_STAMP_ARG
-#endif
-#define UBD_LAUNCH_S123C(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV, true>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p S123C_STAMP_ARG)
-        const bool plain = !u8 && sc == 0.f && sh == 1.f && (size_t)H * W * h->cfg.c_in * 4 < (1ull << 30) && ((uintptr_t)images & 15) == 0;
-        if (h->cfg.c_in == 1) { if (u8) UBD_LAUNCH_S123C(1, 1, 0); else if (plain) UBD_LAUNCH_S123C(1, 0, 1); else UBD_LAUNCH_S123C(1, 0, 0); }
-        else { if (u8) UBD_LAUNCH_S123C(3, 1, 0); else if (plain) UBD_LAUNCH_S123C(3, 0, 1); else UBD_LAUNCH_S123C(3, 0, 0); }
-#undef UBD_LAUNCH_S123C
-    } else if (fuse_all) {
-        // L1 -> L2 -> L3 in one kernel (stem123.h): neither a1 nor a2 is touched
-        const int strips = n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3);
-        int grid = h->num_cus;
-        if (grid > strips) grid = strips;
-        pp_lds_args pj;
-        memset(&pj, 0, sizeof(pj));                              // n = 0: no postprocess job rides along
-        if (pp_job) pj = *pp_job;
-        const float *b0 = params + h->off_sep_b[0], *b1 = params + h->off_sep_b[1], *b2 = params + h->off_sep_b[2];
-        int *ticket = (int *)(ws + L.off_tickets);               // zeroed with the weight pack above; the kernel resets them itself
-#ifdef UBD_STAMPS
-#define S123_STAMP_ARG , g_ubd_stamps
-#else
-#define S123_STAMP_ARG
-#endif
-#define UBD_LAUNCH_S123(CINV, U8V, PLV) hipLaunchKernelGGL((stem123_kernel<CINV, U8V, PLV>), dim3(grid), dim3(s23_cfg::NT), 0, st, images, cur, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p S123_STAMP_ARG)
-        const bool plain = !u8 && sc == 0.f && sh == 1.f && (size_t)H * W * h->cfg.c_in * 4 < (1ull << 30) && ((uintptr_t)images & 15) == 0;   // fp32 fed as it is: 16-byte LDS-DMA path (offsets of one image in 30 bits, 16-byte aligned base)
-        if (h->cfg.c_in == 1) { if (u8) UBD_LAUNCH_S123(1, 1, 0); else if (plain) UBD_LAUNCH_S123(1, 0, 1); else UBD_LAUNCH_S123(1, 0, 0); }
-        else { if (u8) UBD_LAUNCH_S123(3, 1, 0); else if (plain) UBD_LAUNCH_S123(3, 0, 1); else UBD_LAUNCH_S123(3, 0, 0); }
-#undef UBD_LAUNCH_S123
-    } else if (h->cfg.c_in == 1)
+    int *ticket = (int *)(ws + L.off_tickets);                   // zeroed with the weight pack above; the strip walk resets them itself, the cold form does not touch them
+    if (plan.form == UBD_STEM_FORM_COLD)
+        launch_stem123<true>(h, params, images, u8, cur, sf0, sf1, sf2, n, H, W, sc, sh, plan.strips * (W4 <= 16 ? 1 : 1 + (W4 - 16 + 14) / 15),
+                             ticket, nullptr, a3_l2p, st);
+    else if (plan.form == UBD_STEM_FORM_STRIPS)
+        launch_stem123<false>(h, params, images, u8, cur, sf0, sf1, sf2, n, H, W, sc, sh, plan.strips, ticket, pp_job, a3_l2p, st);
+    else if (h->cfg.c_in == 1)
         launch_sep<1, 2>(h, images, u8, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sc, sh, st);
     else
         launch_sep<3, 2>(h, images, u8, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sc, sh, st);
-    if (fuse_all || cold_all) {
-    } else if (inference && stem_big && h->fuse_stem) {
+    if (plan.form == UBD_STEM_FORM_L1_STEM23) {
         // L2 -> L3 in one kernel: L2's activation stays in LDS (stem23.h); the a2 buffer is not touched
-        const int strips = n * ((H4 + s23_cfg::TH3 - 1) / s23_cfg::TH3);   // a block walks whole row strips of tiles
-        int grid = h->num_cus;                                   // one 8-wave block per CU (120 KB of LDS)
-        if (grid > strips) grid = strips;
-#ifdef UBD_STAMPS
-#define S23_STAMP_ARG , g_ubd_stamps
-#else
-#define S23_STAMP_ARG
-#endif
-        if (pad_s2)
-            hipLaunchKernelGGL(stem23_kernel<true>, dim3(grid), dim3(s23_cfg::NT), 0, st, a1, cur, sf1, params + h->off_sep_b[1], sf2, params + h->off_sep_b[2],
-                               n, H2, W2, H4, W4, pad_s2 S23_STAMP_ARG);
-        else
-            hipLaunchKernelGGL(stem23_kernel<false>, dim3(grid), dim3(s23_cfg::NT), 0, st, a1, cur, sf1, params + h->off_sep_b[1], sf2, params + h->off_sep_b[2],
-                               n, H2, W2, H4, W4, pad_s2 S23_STAMP_ARG);
-    } else {
+        const int grid = plan.strips < h->num_cus ? (int)plan.strips : h->num_cus;   // one 8-wave block per CU (120 KB of LDS) walks whole row strips of tiles
+        ubd_dispatch_bool(pad_s2 != 0, [&](auto pad) {
+            hipLaunchKernelGGL(stem23_kernel<decltype(pad)::value>, dim3(grid), dim3(s23_cfg::NT), 0, st, a1, cur, sf1, params + h->off_sep_b[1], sf2,
+                               params + h->off_sep_b[2], n, H2, W2, H4, W4, pad_s2 UBD_STAMP_ARG(g_ubd_stamps));
+        });
+    } else if (plan.form == UBD_STEM_FORM_SEPARATE) {
         launch_sep<UBD_C, 1>(h, a1, 0, a2, sf1, params + h->off_sep_b[1], n, H2, W2, H2, W2, 1, 0.f, 1.f, st);
         launch_sep<UBD_C, 2>(h, a2, 0, cur, sf2, params + h->off_sep_b[2], n, H2, W2, H4, W4, pad_s2, 0.f, 1.f, st);
     }
 
     // inference with a single output channel: the head rides in the epilogue of L9 and L9's activation is never written
-    const bool fuse_head = inference && h->use_wino && h->k_out == 1 && h->off_head_b == h->off_head_k + UBD_C;
+    const bool fuse_head = inference && h->use_wino && ubd_head_in_epilogue(h);
     for (int k = 0; k < UBD_NUM_DIL; ++k) {
         float *nxt = (float *)(ws + L.off_acts[k + 1]);
-        if (fuse_head && k == UBD_NUM_DIL - 1 && h->wino_x6) {
-            ubd_launch_dilconv_wino6(h, 2, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
-                                     UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k,
-                                     phase_major ? phase_lay[k] : 1, 1);
-            UBD_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
         if (fuse_head && k == UBD_NUM_DIL - 1) {
-            ubd_launch_dilconv_wino(h, 2, wfrag + UBD_FWD_DIRECT_FLOATS + (size_t)k * UBD_WINO_FRAG_FLOATS, params + h->off_dil_b[k], UBD_F32,
-                                    UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k);
+            if (h->wino_x6)
+                ubd_launch_dilconv_wino6(h, 2, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
+                                         UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k, phase_major ? phase_lay[k] : 1, 1);
+            else
+                ubd_launch_dilconv_wino(h, 2, wfrag + UBD_FWD_DIRECT_FLOATS + (size_t)k * UBD_WINO_FRAG_FLOATS, params + h->off_dil_b[k], UBD_F32,
+                                        UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k);
             UBD_CHECK_HIP(hipGetLastError());
             return 0;
         }
@@ -898,20 +862,26 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     return 0;
 }
 
+// fp32 inference on the caller's workspace; pp_job: a postprocess job for the strip-walking stem (may be null)
+static int forward_f32(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing, int n, int H, int W, float *logits,
+                       void *workspace, size_t workspace_bytes, void *stream, const pp_lds_args *pp_job)
+{
+    ubd_fwd_layout L;
+    ubd_fwd_layout_compute(h, n, H, W, 0, &L);
+    UBD_REQUIRE(workspace_bytes >= L.total, "ubd_forward: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    return ubd_forward_impl(h, params, images, in_dtype, preprocessing, n, H, W, logits, (char *)workspace, L, (hipStream_t)stream, true, pp_job);
+}
+
 extern "C" int ubd_forward(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
                            int n, int height, int width, float *logits, void *workspace, size_t workspace_bytes,
                            void *stream)
 {
     UBD_REQUIRE(h && params && images && logits && workspace, "ubd_forward: null argument");
     if (h->cfg.dtype != UBD_F32) {
-        UBD_REQUIRE(n > 0 && height > 0 && width > 0 && (height % 4) == 0 && (width % 4) == 0, "ubd_forward: height and width must be positive multiples of 4 (got %d x %d)", height, width);
-        UBD_REQUIRE((in_dtype & ~UBD_IN_PREPACKED) == UBD_IN_F32 || (in_dtype & ~UBD_IN_PREPACKED) == UBD_IN_U8, "ubd_forward: bad in_dtype %d", in_dtype);
+        if (int rc = check_forward_input(n, height, width, in_dtype)) return rc;
         return ubd_forward16(h, params, images, in_dtype, preprocessing, n, height, width, logits, (char *)workspace, workspace_bytes, (hipStream_t)stream);
     }
-    ubd_fwd_layout L;
-    ubd_fwd_layout_compute(h, n, height, width, 0, &L);
-    UBD_REQUIRE(workspace_bytes >= L.total, "ubd_forward: workspace too small (%zu < %zu)", workspace_bytes, L.total);
-    return ubd_forward_impl(h, params, images, in_dtype, preprocessing, n, height, width, logits, (char *)workspace, L, (hipStream_t)stream, true);
+    return forward_f32(h, params, images, in_dtype, preprocessing, n, height, width, logits, workspace, workspace_bytes, stream, nullptr);
 }
 
 // ubd_forward of one batch + ubd_postprocess of ANOTHER (earlier) batch's logits, enqueued together: when the forward pass runs
@@ -925,18 +895,14 @@ extern "C" int ubd_forward_postprocess(ubd_handle *h, const float *params, const
 {
     UBD_REQUIRE(h && params && images && logits && workspace, "ubd_forward_postprocess: null argument");
     UBD_REQUIRE(pp_logits != logits, "ubd_forward_postprocess: the logits being postprocessed must not be the buffer this call writes");
-    if (h->cfg.dtype == UBD_F32 && n > 0 && height > 0 && (height % 4) == 0 && ubd_forward_uses_fused_stem(h, n, height, width)) {
+    if (h->cfg.dtype == UBD_F32 && n > 0 && height > 0 && (height % 4) == 0 &&
+        ubd_plan_stem(h->fuse_stem, h->fuse_force != 0, h->cfg.fml_compatible != 0, h->num_cus, n, height, true, true).form == UBD_STEM_FORM_STRIPS) {
         pp_lds_args job;
         const int fits = ubd_pp_fill_job(h, pp_logits, pp_n, pp_map_h, pp_map_w, logit_threshold, scale, min_area, binary_map, quads, classes,
                                          counts, cap, pp_workspace, pp_workspace_bytes,
                                          s23_cfg::NT, &job);
         if (fits < 0) return 1;
-        if (fits == 1) {
-            ubd_fwd_layout L;
-            ubd_fwd_layout_compute(h, n, height, width, 0, &L);
-            UBD_REQUIRE(workspace_bytes >= L.total, "ubd_forward: workspace too small (%zu < %zu)", workspace_bytes, L.total);
-            return ubd_forward_impl(h, params, images, in_dtype, preprocessing, n, height, width, logits, (char *)workspace, L, (hipStream_t)stream, true, &job);
-        }
+        if (fits == 1) return forward_f32(h, params, images, in_dtype, preprocessing, n, height, width, logits, workspace, workspace_bytes, stream, &job);
     }
     int rc = ubd_postprocess(h, pp_logits, pp_n, pp_map_h, pp_map_w, logit_threshold, scale, min_area, binary_map, quads, classes, counts, cap,
                              pp_workspace, pp_workspace_bytes, stream);

@@ -1102,28 +1102,19 @@ static void launch_sep12(const ubd_handle *h, const void *x, unsigned short *a1,
 {
     const int H2 = H / 2, W2 = W / 2;
     const long tiles = (long)n * ((H2 + 15) / 16) * ((W2 + 15) / 16);
-    long grid = (long)h->num_cus * 3;                          // three blocks per CU (registers; LDS 50 KiB with two patch buffers)
-    if (grid > tiles) grid = tiles;
-    long grid4 = (long)h->num_cus * 4;
-    if (grid4 > tiles) grid4 = tiles;
-    // inference: one patch buffer and four blocks per CU (34 KiB, 120 registers); train step: two buffers, three blocks (0.172 -> 0.169 ms for
-    // cfg5 / 1.200 -> 1.192 ms for the bf16 train step against the other assignment)
-    int xb = write_a1 ? 2 : 1;
-#define UBD_SEP12_LAUNCH(PLAIN, WR)                                                                                                   \
-    do { if (xb == 1) hipLaunchKernelGGL((sep12_16_kernel<CIN, IN_MODE, PLAIN, WR, T, 1>), dim3(grid4), dim3(256), 0, st, x, a1, a2, frag1, bias1, frag2,    \
-                       bias2, n, H, W, H2, W2, pad_lo, sub, div); else hipLaunchKernelGGL((sep12_16_kernel<CIN, IN_MODE, PLAIN, WR, T, 2>), dim3(grid), dim3(256), 0, st, x, a1, a2, frag1, bias1, frag2,    \
-                       bias2, n, H, W, H2, W2, pad_lo, sub, div); } while (0)
-    // fp32 pixels fed as they are, offsets inside one image below 2^31: LDS-DMA
-    const bool plain = IN_MODE == 0 && sub == 0.f && div == 1.f && (size_t)H * W * CIN * 4 < (1ull << 31) && ((uintptr_t)x & 15) == 0;   // 16-byte DMA pieces: an offset view of a tensor takes the register-staged variant
-    if constexpr (IN_MODE == 0) {
-        if (plain) {
-            if (write_a1) UBD_SEP12_LAUNCH(true, true); else UBD_SEP12_LAUNCH(true, false);
-            return;
-        }
+    // inference: one patch buffer and four blocks per CU (34 KiB, 120 registers); train step: two buffers, three blocks (registers; LDS 50 KiB) (0.172 ->
+    // 0.169 ms for cfg5 / 1.200 -> 1.192 ms for the bf16 train step against the other assignment)
+    auto launch = [&](auto pl, bool one_buffer) {
+        const long per_cu = (long)h->num_cus * (one_buffer ? 4 : 3);
+        ubd_dispatch_bool(write_a1, [&](auto wr) { ubd_dispatch_bool(one_buffer, [&](auto one) {
+            hipLaunchKernelGGL((sep12_16_kernel<CIN, IN_MODE, decltype(pl)::value, decltype(wr)::value, T, decltype(one)::value ? 1 : 2>), dim3(per_cu < tiles ? per_cu : tiles),
+                               dim3(256), 0, st, x, a1, a2, frag1, bias1, frag2, bias2, n, H, W, H2, W2, pad_lo, sub, div);
+        }); });
+    };
+    if constexpr (IN_MODE == 0) {                                  // offsets inside one image below 2^31
+        if (ubd_pixels_by_lds_dma(true, sub, div, H, W, CIN, 1ull << 31, x)) return launch(std::true_type{}, !write_a1);
     }
-    xb = 2;                                                    // register-staged input: the three-blocks-per-CU build (128 registers would spill); one patch buffer either way
-    if (write_a1) UBD_SEP12_LAUNCH(false, true); else UBD_SEP12_LAUNCH(false, false);
-#undef UBD_SEP12_LAUNCH
+    launch(std::false_type{}, false);                          // register-staged input: the three-blocks-per-CU build (128 registers would spill); one patch buffer either way
 }
 
 template <int CIN, int IN_MODE, typename T>
@@ -1135,19 +1126,16 @@ static void launch_sep123(const ubd_handle *h, const void *x, unsigned short *a1
     const long tiles = (long)n * ((H4 + 7) / 8) * ((W4 + 7) / 8);
     long grid = (long)h->num_cus * 3;                          // three blocks per CU (54 KB of LDS each)
     if (grid > tiles) grid = tiles;
-#define UBD_SEP123_LAUNCH(PLAIN, WR)                                                                                                        \
-    hipLaunchKernelGGL((sep123_16_kernel<CIN, IN_MODE, PLAIN, WR, T>), dim3(grid), dim3(256), 0, st, x, a1, a2, a3, frag1, bias1, (const u32x4 *)ready23, \
-                       bias2, bias3, n, H, W, H2, W2, H4, W4, pad_lo, sub, div S123_16_STAMP_ARG)
-    // fp32 pixels fed as they are, offsets inside one image below 2^31: LDS-DMA
-    const bool plain = IN_MODE == 0 && sub == 0.f && div == 1.f && (size_t)H * W * CIN * 4 < (1ull << 31) && ((uintptr_t)x & 15) == 0;   // 16-byte DMA pieces: an offset view of a tensor takes the register-staged variant
-    if constexpr (IN_MODE == 0) {
-        if (plain) {
-            if (write_a12) UBD_SEP123_LAUNCH(true, true); else UBD_SEP123_LAUNCH(true, false);
-            return;
-        }
+    auto launch = [&](auto pl) {
+        ubd_dispatch_bool(write_a12, [&](auto wr) {
+            hipLaunchKernelGGL((sep123_16_kernel<CIN, IN_MODE, decltype(pl)::value, decltype(wr)::value, T>), dim3(grid), dim3(256), 0, st, x, a1, a2, a3, frag1,
+                               bias1, (const u32x4 *)ready23, bias2, bias3, n, H, W, H2, W2, H4, W4, pad_lo, sub, div S123_16_STAMP_ARG);
+        });
+    };
+    if constexpr (IN_MODE == 0) {                                  // offsets inside one image below 2^31
+        if (ubd_pixels_by_lds_dma(true, sub, div, H, W, CIN, 1ull << 31, x)) return launch(std::true_type{});
     }
-    if (write_a12) UBD_SEP123_LAUNCH(false, true); else UBD_SEP123_LAUNCH(false, false);
-#undef UBD_SEP123_LAUNCH
+    launch(std::false_type{});
 }
 
 static unsigned magic_u32(unsigned d) { return d <= 1u ? 0u : (unsigned)(((1ull << 32) + d - 1) / d); }
@@ -1169,27 +1157,27 @@ static void launch_dil16(const ubd_handle *h, int epi, const unsigned *frag, con
         const d16s_geom geo = d16s_geometry(n, H4, W4, d);
         if (g2 > items) g2 = (int)items;
         g2 = (g2 + 7) / 8 * 8;                                     // the item ranges are cut per XCD: all eight need a block
-        if (epi == 0)
-            hipLaunchKernelGGL((dilconv16s_kernel<T, 0>), dim3(g2), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                               (const u32x4 *)frag, bias, n, H4, W4, d, (const float *)nullptr, (float *)nullptr, geo D16S_STAMP_ARG);
-        else if (epi == 2)      // out = fp32 logits, mask = fp32 head: the activation is not stored
-            hipLaunchKernelGGL((dilconv16s_kernel<T, 2>), dim3(g2), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)nullptr,
-                               (const u32x4 *)frag, bias, n, H4, W4, d, (const float *)mask, (float *)out, geo D16S_STAMP_ARG);
-        else                    // out = activation, logits3 = fp32 logits
-            hipLaunchKernelGGL((dilconv16s_kernel<T, 3>), dim3(g2), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                               (const u32x4 *)frag, bias, n, H4, W4, d, (const float *)mask, logits3, geo D16S_STAMP_ARG);
-    } else if (epi == 0)
-        hipLaunchKernelGGL((dilconv16_kernel<T, 0>), dim3(grid), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                           (const u32x4 *)frag, bias, (const unsigned short *)nullptr, n, H4, W4, d, mg_tx, mg_h, (float *)nullptr);
-    else if (epi == 2)      // out = fp32 logits (n, H4, W4, 1), mask = fp32 head (24 weights + bias)
-        hipLaunchKernelGGL((dilconv16_kernel<T, 2>), dim3(grid), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                           (const u32x4 *)frag, bias, (const unsigned short *)mask, n, H4, W4, d, mg_tx, mg_h, (float *)nullptr);
-    else if (epi == 3)      // out = activation, logits3 = fp32 logits, mask = fp32 head
-        hipLaunchKernelGGL((dilconv16_kernel<T, 3>), dim3(grid), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                           (const u32x4 *)frag, bias, (const unsigned short *)mask, n, H4, W4, d, mg_tx, mg_h, logits3);
-    else
-        hipLaunchKernelGGL((dilconv16_kernel<T, 1>), dim3(grid), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
-                           (const u32x4 *)frag, bias, (const unsigned short *)mask, n, H4, W4, d, mg_tx, mg_h, (float *)nullptr);
+        // epi 0: plain layer; 2: out = fp32 logits, mask = fp32 head, the activation is not stored; 3: out = activation, logits3 = fp32 logits
+        const unsigned short *in16 = (const unsigned short *)in;
+        unsigned short *act = epi == 2 ? nullptr : (unsigned short *)out;
+        const float *head = epi == 0 ? nullptr : (const float *)mask;
+        float *lg = epi == 0 ? nullptr : epi == 2 ? (float *)out : logits3;
+        auto launch = [&](auto e) {
+            hipLaunchKernelGGL((dilconv16s_kernel<T, decltype(e)::value>), dim3(g2), dim3(256), 0, st, in16, act, (const u32x4 *)frag, bias, n, H4, W4, d, head, lg,
+                               geo D16S_STAMP_ARG);
+        };
+        if (epi == 0) launch(ubd_int<0>{}); else if (epi == 2) launch(ubd_int<2>{}); else launch(ubd_int<3>{});
+        return;
+    }
+    // epi 0: plain layer; 1: mask = ReLU mask of the data gradient; 2: out = fp32 logits (n, H4, W4, 1), mask = fp32 head (24 weights + bias);
+    // 3: out = activation, logits3 = fp32 logits, mask = fp32 head
+    const unsigned short *m16 = epi == 0 ? nullptr : (const unsigned short *)mask;
+    float *lg = epi == 3 ? logits3 : nullptr;
+    auto launch = [&](auto e) {
+        hipLaunchKernelGGL((dilconv16_kernel<T, decltype(e)::value>), dim3(grid), dim3(256), 0, st, (const unsigned short *)in, (unsigned short *)out,
+                           (const u32x4 *)frag, bias, m16, n, H4, W4, d, mg_tx, mg_h, lg);
+    };
+    if (epi == 0) launch(ubd_int<0>{}); else if (epi == 2) launch(ubd_int<2>{}); else if (epi == 3) launch(ubd_int<3>{}); else launch(ubd_int<1>{});
 }
 
 // 16-bit dense dilated layer (epi 0: forward, epi 1: data gradient with ReLU mask); element type from the handle
@@ -1243,47 +1231,30 @@ static int forward16_impl(ubd_handle *h, const float *params, const void *images
         // L1 -> L2 -> L3 in one kernel (sep123_16.h): neither a1 nor a2 is read back; the train step keeps both for the backward pass
         const float *b0 = params + h->off_sep_b[0], *b1 = params + h->off_sep_b[1], *b2 = params + h->off_sep_b[2];
         const unsigned *ready23 = wfrag16 + (size_t)UBD_NUM_DIL * UBD_DIL16_FRAG_U32;
-        if (h->cfg.c_in == 1) {
-            if (u8) launch_sep123<1, 1, T>(h, images, a1, a2, cur, sf0, b0, ready23, b1, b2, n, H, W, pad_s2, sub, div, !inference, st);
-            else launch_sep123<1, 0, T>(h, images, a1, a2, cur, sf0, b0, ready23, b1, b2, n, H, W, pad_s2, sub, div, !inference, st);
-        } else {
-            if (u8) launch_sep123<3, 1, T>(h, images, a1, a2, cur, sf0, b0, ready23, b1, b2, n, H, W, pad_s2, sub, div, !inference, st);
-            else launch_sep123<3, 0, T>(h, images, a1, a2, cur, sf0, b0, ready23, b1, b2, n, H, W, pad_s2, sub, div, !inference, st);
-        }
+        ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
+            launch_sep123<decltype(cin)::value, decltype(in_u8)::value, T>(h, images, a1, a2, cur, sf0, b0, ready23, b1, b2, n, H, W, pad_s2, sub, div, !inference, st);
+        });
     } else if (h->split_stem16 == 1) {
-        if (h->cfg.c_in == 1) {
-            if (u8) launch_sep16<1, 2, 1, T>(h, images, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sub, div, st);
-            else launch_sep16<1, 2, 0, T>(h, images, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sub, div, st);
-        } else {
-            if (u8) launch_sep16<3, 2, 1, T>(h, images, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sub, div, st);
-            else launch_sep16<3, 2, 0, T>(h, images, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sub, div, st);
-        }
+        ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
+            launch_sep16<decltype(cin)::value, 2, decltype(in_u8)::value, T>(h, images, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sub, div, st);
+        });
         launch_sep16<UBD_C, 1, 2, T>(h, a1, a2, sf1, params + h->off_sep_b[1], n, H2, W2, H2, W2, 1, 0.f, 1.f, st);
     } else {
         // L1 -> L2 in one kernel; the train step keeps L1's activation (the backward pass reads it)
         const float *b0 = params + h->off_sep_b[0], *b1 = params + h->off_sep_b[1];
-        if (h->cfg.c_in == 1) {
-            if (u8) launch_sep12<1, 1, T>(h, images, a1, a2, sf0, b0, sf1, b1, n, H, W, pad_s2, sub, div, !inference, st);
-            else launch_sep12<1, 0, T>(h, images, a1, a2, sf0, b0, sf1, b1, n, H, W, pad_s2, sub, div, !inference, st);
-        } else {
-            if (u8) launch_sep12<3, 1, T>(h, images, a1, a2, sf0, b0, sf1, b1, n, H, W, pad_s2, sub, div, !inference, st);
-            else launch_sep12<3, 0, T>(h, images, a1, a2, sf0, b0, sf1, b1, n, H, W, pad_s2, sub, div, !inference, st);
-        }
+        ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
+            launch_sep12<decltype(cin)::value, decltype(in_u8)::value, T>(h, images, a1, a2, sf0, b0, sf1, b1, n, H, W, pad_s2, sub, div, !inference, st);
+        });
     }
     if (h->split_stem16 != 0)
         launch_sep16<UBD_C, 2, 2, T>(h, a2, cur, sf2, params + h->off_sep_b[2], n, H2, W2, H4, W4, pad_s2, 0.f, 1.f, st);
-    // inference with a single output channel: the head rides in the epilogue of L9 and L9's activation is never written
-    const bool fuse_head = inference && h->k_out == 1 && h->off_head_b == h->off_head_k + UBD_C;
+    const bool head_in_l9 = ubd_head_in_epilogue(h);               // a single output channel
     for (int k = 0; k < UBD_NUM_DIL; ++k) {
         unsigned short *nxt = (unsigned short *)(ws + L.off_acts[k + 1]);
-        if (!inference && h->k_out == 1 && k == UBD_NUM_DIL - 1 && h->off_head_b == h->off_head_k + UBD_C) {
-            // train step: L9 stores its activation (the backward pass reads it) and applies the head in the same epilogue
-            ubd_launch_dilconv16(h, 3, wfrag16 + (size_t)k * UBD_DIL16_FRAG_U32, params + h->off_dil_b[k], params + h->off_head_k, UBD_DILATIONS[k], cur, nxt, n, H4, W4, st, logits);
-            UBD_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
-        if (fuse_head && k == UBD_NUM_DIL - 1) {
-            ubd_launch_dilconv16(h, 2, wfrag16 + (size_t)k * UBD_DIL16_FRAG_U32, params + h->off_dil_b[k], params + h->off_head_k, UBD_DILATIONS[k], cur, logits, n, H4, W4, st);
+        if (head_in_l9 && k == UBD_NUM_DIL - 1) {
+            // inference: L9's activation is never written; train step: L9 stores it (the backward pass reads it) and applies the head in the same epilogue
+            ubd_launch_dilconv16(h, inference ? 2 : 3, wfrag16 + (size_t)k * UBD_DIL16_FRAG_U32, params + h->off_dil_b[k], params + h->off_head_k, UBD_DILATIONS[k], cur,
+                                 inference ? (void *)logits : (void *)nxt, n, H4, W4, st, inference ? nullptr : logits);
             UBD_CHECK_HIP(hipGetLastError());
             return 0;
         }
@@ -1313,8 +1284,8 @@ int ubd_forward16_layout(ubd_handle *h, const float *params, const void *images,
 int ubd_forward16(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing, int n, int H, int W,
                   float *logits, char *ws, size_t ws_bytes, hipStream_t st)
 {
-    UBD_REQUIRE(ws_bytes >= ubd_forward16_workspace_bytes(n, H, W), "ubd_forward: workspace too small for the 16-bit path");
     ubd_fwd16_layout L;
     ubd_fwd16_layout_compute(n, H, W, 0, &L);
+    UBD_REQUIRE(ws_bytes >= L.total, "ubd_forward: workspace too small for the 16-bit path");
     return ubd_forward16_layout(h, params, images, in_dtype, preprocessing, n, H, W, logits, ws, L, st, true);
 }
