@@ -163,6 +163,47 @@ int ubd_adam_step(float *params, const float *grads, float *m, float *v, size_t 
 int ubd_build_label_maps(const double *quads, const int32_t *values, const int32_t *counts, int n, int cap,
                          int map_h, int map_w, int scale, int32_t *labels, void *stream);
 
+/* --- polygon ground truth (semantic_segmentation/markup_readers.py:257-285, SegmentationMapMarkupReader) ---
+ * Data sets whose ground truth is a segmentation map give one convex hull per external component, not a quad.  The three calls
+ * below take such polygons with up to UBD_POLY_MAX_VERTS vertices. */
+#define UBD_POLY_MAX_VERTS 64
+
+/* Label maps from polygon markup: ubd_build_label_maps for objects of 3..max_verts vertices.
+ *   verts  : device double (n, cap, max_verts, 2) x, y in image pixels; max_verts 3..UBD_POLY_MAX_VERTS
+ *   nverts : device int32 (n, cap) vertices of every object
+ * An object with 4 vertices is a quad: it goes through _proper_round and the quad rule and gets exactly the pixels
+ * ubd_build_label_maps writes for it (the opposite-corner fold included).  Any other object with 3..max_verts vertices is divided
+ * by the scale in double and truncated toward zero (segmap_manager.py:114-116: the reference does not snap a polygon that is
+ * not a quad), then filled with ImageDraw.polygon's rule for n edges (csrc/polygon_fill.h; tests/test_polygon_fill_host.py pins
+ * it to Pillow on convex polygons).  Objects are painted in order, later over earlier; quads and polygons may be mixed.  Objects
+ * with any other vertex count are skipped (the Python host rejects them).  values, counts, labels, scale as in
+ * ubd_build_label_maps.  Limits: map_w <= 8192, map_h and n <= 65535 (non-zero return, nothing launched).  One launch (one
+ * block per map row), no host synchronisation, capturable in a HIP graph. */
+int ubd_build_label_maps_polygons(const double *verts, const int32_t *nverts, const int32_t *values, const int32_t *counts,
+                                  int n, int cap, int max_verts, int map_h, int map_w, int scale, int32_t *labels, void *stream);
+
+/* Segmentation maps -> hull polygons (markup_readers.py:271-285: findContours(RETR_EXTERNAL) -> cv2.convexHull per contour).
+ *   maps   : device uint8 (n, map_h, map_w); foreground is a byte that is not 0
+ *   verts  : device int32 (n, cap, UBD_POLY_MAX_VERTS, 2) x, y in map pixels
+ *   nverts : device int32 (n, cap) the TRUE hull size of every object; only the first UBD_POLY_MAX_VERTS vertices are stored,
+ *            so nverts > UBD_POLY_MAX_VERTS tells the caller that the polygon is incomplete
+ *   counts : device int32 (n) objects found; counts[i] > cap: the list of image i was truncated to cap entries (as ubd_postprocess)
+ * Objects: the external 8-connected components, every one of them (the reader's min_area = -1), by the rule of ubd_postprocess
+ * (a component inside a hole of another is not an object), in the order ubd_postprocess returns them (cv2's: last discovered
+ * first).  Polygon: the strictly convex hull of the component's pixels (= the hull of its contour).  Vertex cycle: that of
+ * cv2.convexHull(contour) with its defaults (clockwise = False) as restated here -- it starts at the vertex with the greatest x
+ * (the greatest y among equals) and moves towards the vertex with the greatest y; this is the cycle of the postprocess' hull
+ * (oracle/cv_post.c convex_hull) reversed and rotated to that start.  Hulls of 1 and 2 vertices (single pixels, straight
+ * one-pixel lines) are emitted as they are.  As for the rest of the postprocess, parity with cv2 itself is unpinned: OpenCV is
+ * not available where this is built.
+ * Takes no handle.  Limits (non-zero return, ubd_last_error, nothing launched): n >= 1, sides 1..32767, n * map_h * map_w < 2^31,
+ * cap 1..UBD_EVAL_MAX_GT, workspace_bytes >= ubd_segmap_polygons_workspace_bytes (0 for sizes outside the limits).  Global-memory
+ * labelling at every map size (the call runs once per data set, not per step); no host synchronisation, no allocation,
+ * capturable in a HIP graph. */
+size_t ubd_segmap_polygons_workspace_bytes(int n, int map_h, int map_w, int cap);
+int ubd_segmap_polygons(const uint8_t *maps, int n, int map_h, int map_w, int32_t *verts, int32_t *nverts, int32_t *counts,
+                        int cap, void *workspace, size_t workspace_bytes, void *stream);
+
 /* --- image preparation ------------------------------------------------------
  * Replaces Image.resize((dst_w, dst_h), Image.BICUBIC) of SegmapManager._rescale_image_and_markup (segmap_manager.py:135-173)
  * and, for dst_c == 1 from RGB, the Image.convert('L') of data_generators.py:177, for n uint8 images of any sizes to one size.
@@ -407,6 +448,21 @@ int ubd_evaluate_objects(const int32_t *quads, const int32_t *classes, const int
  * double areas of the ground truths [max_gt], areas of the found quads [cap], intersections [max_gt][cap], IoU [max_gt][cap]. */
 int ubd_evaluate_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int64_t *offset_bytes,
                                int64_t *stride_doubles);
+
+/* ubd_evaluate_objects for convex ground-truth polygons of 3..max_verts vertices, max_verts 3..UBD_POLY_MAX_VERTS (hulls read
+ * from segmentation maps: ubd_segmap_polygons).  Arguments, accumulator, records, flags, tie rules and the fixed reduction order
+ * are those of ubd_evaluate_objects; a polygon with fewer than 3 or more than max_verts vertices flags its image
+ * UBD_EVAL_FLAG_BAD_GT.  The workspace keeps max_verts vertices per polygon slot: ubd_evaluate_polygons_workspace_bytes and
+ * ubd_evaluate_polygons_tables_layout are the siblings of the two calls above.  On ground truth of at most UBD_EVAL_MAX_VERTS
+ * vertices the records and the accumulator are bit-identical to ubd_evaluate_objects'. */
+size_t ubd_evaluate_polygons_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes, int max_verts);
+int ubd_evaluate_polygons(const int32_t *quads, const int32_t *classes, const int32_t *counts, int n, int cap,
+                          const double *scales, const double *gt_xy, int n_gt_vertices, const int32_t *gt_first,
+                          const int32_t *gt_class, const int32_t *gt_image_first, int max_gt, const double *thresholds,
+                          int n_thresholds, int n_classes, int max_verts, ubd_eval_record *per_image, void *accumulator,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int ubd_evaluate_polygons_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int max_verts,
+                                        int64_t *offset_bytes, int64_t *stride_doubles);
 
 /* --- pixel classification accuracy (semantic_segmentation/evaluation.py:546-575, _calc_pixel_classification_correctness_mask) ---
  * For n maps of map_h x map_w: pred = argmax over the n_classes class logits of a pixel (np.argmax: first maximum, first NaN),

@@ -23,6 +23,7 @@ UBD_NA_NEAREST, UBD_NA_LINEAR, UBD_NA_CUBIC = 0, 1, 2
 UBD_NA_MAX, UBD_NA_AVG = 0, 1
 UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS = 8, 256, 256, 16
 UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
+UBD_POLY_MAX_VERTS = 64
 UBD_MAX_CLASSES = 31
 
 
@@ -68,6 +69,9 @@ SIGNATURES = {
     "ubd_train_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _f, _f, _f, _f, _f, _vp]),
     "ubd_build_label_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_build_label_maps_polygons": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_segmap_polygons_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ubd_segmap_polygons": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "ubd_resize_images": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
     "ubd_warp_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_photometric_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
@@ -76,6 +80,9 @@ SIGNATURES = {
     "ubd_evaluate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ubd_evaluate_objects": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_evaluate_tables_layout": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_evaluate_polygons_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "ubd_evaluate_polygons": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ubd_evaluate_polygons_tables_layout": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_evaluate_pixels_accumulator_bytes": (_sz, []),
     "ubd_evaluate_pixels_workspace_bytes": (_sz, [_i, _i, _i]),
     "ubd_evaluate_pixels": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

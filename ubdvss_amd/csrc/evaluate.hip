@@ -18,6 +18,13 @@
 // Launches per call (and per 64 images): prepare (rescale, winding, areas) -> tables (one wave per ground-truth row, lanes over
 // found quads) -> match (one block per image: adjacency, classes of correspondences, group and by-area unions, records) ->
 // accumulate (ONE block walks the images in order: bit-identical sums run to run; no floating-point atomics).
+//
+// Two entries share the kernels through template <int MAXV>, the vertices a polygon slot of the workspace holds: ubd_evaluate_objects
+// (MAXV = UBD_EVAL_MAX_VERTS = 8, ground truth of 3..8 vertices) and ubd_evaluate_polygons (MAXV = UBD_POLY_MAX_VERTS = 64, hulls
+// read from segmentation maps).  Only the slot stride and the prepare phase's staging differ: at 8 vertices a polygon is
+// normalised in registers, at 64 in its workspace slot (1 KB per thread would go to scratch).  The work units of a union are
+// (polygon, edge) numbered polygon * MAXV + edge and dealt to the EV_WAVES waves round robin: MAXV is a multiple of EV_WAVES, so
+// an edge lands in the same wave, in the same order, for either MAXV, and the two entries give the same bits on common ground.
 #include "common.h"
 #include <algorithm>
 
@@ -34,7 +41,7 @@
 
 struct ev_layout {                            // workspace carving, offsets in bytes
     int P;                                    // polygon slots per image = max_gt + cap
-    size_t off_xy;                            // double (n, P, 16)
+    size_t off_xy;                            // double (n, P, 2 * MAXV)
     size_t off_nv;                            // int32  (n, P)   vertex count, 0 = not a polygon of this image
     size_t off_tab;                           // double (n, tab_stride): areas gt [max_gt], areas found [cap], inter [max_gt][cap], iou [max_gt][cap]
     size_t tab_stride;                        // doubles per image
@@ -43,11 +50,11 @@ struct ev_layout {                            // workspace carving, offsets in b
     size_t total;
 };
 
-static void ev_layout_compute(int n, int max_gt, int cap, int T, int C, ev_layout *L)
+static void ev_layout_compute(int n, int max_gt, int cap, int T, int C, int maxv, ev_layout *L)
 {
     L->P = max_gt + cap;
     size_t o = 0;
-    L->off_xy = o; o = ubd_align_up(o + (size_t)n * L->P * 16 * sizeof(double), 256);
+    L->off_xy = o; o = ubd_align_up(o + (size_t)n * L->P * 2 * maxv * sizeof(double), 256);
     L->off_nv = o; o = ubd_align_up(o + (size_t)n * L->P * sizeof(int32_t), 256);
     L->tab_stride = (size_t)max_gt + cap + 2 * (size_t)max_gt * cap;
     L->off_tab = o; o = ubd_align_up(o + (size_t)n * L->tab_stride * sizeof(double), 256);
@@ -60,6 +67,7 @@ struct ev_launch {                            // by value: the HOST arrays of th
     int m;                                    // images of this launch
     int img0;                                 // first image of this launch within the call
     int max_gt, cap, T, C;
+    int max_verts;                            // most vertices a ground-truth polygon may have (<= MAXV)
     int n_gt_verts;                           // vertices in gt_xy: every polygon's vertex range [gt_first[p], gt_first[p + 1]) is checked against it
                                               // (gt_first itself is the caller's: total_gt + 1 entries, indexed by the HOST image_first values only)
     int gt0[EV_MAX_IMGS + 1];                 // first ground-truth polygon of each image
@@ -67,7 +75,7 @@ struct ev_launch {                            // by value: the HOST arrays of th
 };
 
 struct ev_image {                             // one image's views
-    const double *xy;                         // (P, 16)
+    const double *xy;                         // (P, 2 * MAXV)
     const int32_t *nv;                        // (P)
     const double *area_g, *area_f;            // [max_gt], [cap]
     const double *inter, *iou;                // [max_gt][cap]
@@ -120,6 +128,7 @@ __device__ __forceinline__ double ev_signed_area(const double *P, int nv)
 }
 
 // ---- phase 1: polygons of the call -> counter-clockwise fp64 polygons + areas; record flags ------------------------------------
+template <int MAXV>
 __global__ __launch_bounds__(EV_THREADS) void ev_prepare_kernel(const int32_t *__restrict__ quads, const int32_t *__restrict__ counts,
                                                                 const double *__restrict__ scales, const double *__restrict__ gt_xy,
                                                                 const int32_t *__restrict__ gt_first, char *__restrict__ ws,
@@ -130,21 +139,23 @@ __global__ __launch_bounds__(EV_THREADS) void ev_prepare_kernel(const int32_t *_
     const int cnt = counts[img];
     const bool overflow = cnt > A.cap || cnt < 0;
     const int F = overflow ? 0 : cnt;
-    double *xy = (double *)(ws + L.off_xy) + (size_t)img * L.P * 16;
+    double *xy = (double *)(ws + L.off_xy) + (size_t)img * L.P * (2 * MAXV);
     int32_t *nvv = (int32_t *)(ws + L.off_nv) + (size_t)img * L.P;
     double *tab = (double *)(ws + L.off_tab) + (size_t)img * L.tab_stride;
+    constexpr bool IN_REGS = MAXV <= EV_MAX_V;          // else the polygon is normalised in its workspace slot
     __shared__ int bad;
     if (threadIdx.x == 0) bad = overflow ? 1 : 0;
     __syncthreads();
     for (int s = threadIdx.x; s < L.P; s += EV_THREADS) {
-        double v[2 * EV_MAX_V];
+        double regs[IN_REGS ? 2 * MAXV : 2];
+        double *v = IN_REGS ? regs : xy + (size_t)s * (2 * MAXV);
         int nv = 0;
         if (s < A.max_gt) {
             if (s < G) {
                 const int p = A.gt0[li] + s;
                 const int v0 = gt_first[p], v1 = gt_first[p + 1];
                 nv = v1 - v0;
-                if (v0 < 0 || nv < 3 || nv > EV_MAX_V || v1 > A.n_gt_verts) { nv = 0; atomicOr(&bad, 2); }
+                if (v0 < 0 || nv < 3 || nv > A.max_verts || v1 > A.n_gt_verts) { nv = 0; atomicOr(&bad, 2); }
                 for (int k = 0; k < nv; ++k) { v[2 * k] = gt_xy[2 * (size_t)(v0 + k)]; v[2 * k + 1] = gt_xy[2 * (size_t)(v0 + k) + 1]; }
             }
         } else if (s - A.max_gt < F) {
@@ -171,7 +182,8 @@ __global__ __launch_bounds__(EV_THREADS) void ev_prepare_kernel(const int32_t *_
                 area = ev_signed_area(v, nv);
             }
         }
-        for (int k = 0; k < nv; ++k) { xy[(size_t)s * 16 + 2 * k] = v[2 * k]; xy[(size_t)s * 16 + 2 * k + 1] = v[2 * k + 1]; }
+        if (IN_REGS)
+            for (int k = 0; k < nv; ++k) { xy[(size_t)s * (2 * MAXV) + 2 * k] = v[2 * k]; xy[(size_t)s * (2 * MAXV) + 2 * k + 1] = v[2 * k + 1]; }
         nvv[s] = nv;
         if (s < A.max_gt) tab[s] = area; else tab[A.max_gt + (s - A.max_gt)] = area;
     }
@@ -180,6 +192,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_prepare_kernel(const int32_t *_
 }
 
 // ---- phase 2: G x F intersection and IoU tables (evaluation.py:210-227); one wave per ground-truth row ---------------------------
+template <int MAXV>
 __global__ __launch_bounds__(64) void ev_tables_kernel(const int32_t *__restrict__ counts, char *__restrict__ ws, ev_layout L, ev_launch A)
 {
     const int li = blockIdx.y, img = A.img0 + li, g = blockIdx.x;
@@ -187,15 +200,15 @@ __global__ __launch_bounds__(64) void ev_tables_kernel(const int32_t *__restrict
     if (g >= G) return;
     const int cnt = counts[img];
     const int F = (cnt > A.cap || cnt < 0) ? 0 : cnt;
-    const double *xy = (const double *)(ws + L.off_xy) + (size_t)img * L.P * 16;
+    const double *xy = (const double *)(ws + L.off_xy) + (size_t)img * L.P * (2 * MAXV);
     const int32_t *nvv = (const int32_t *)(ws + L.off_nv) + (size_t)img * L.P;
     double *tab = (double *)(ws + L.off_tab) + (size_t)img * L.tab_stride;
     double *inter_t = tab + A.max_gt + A.cap, *iou_t = inter_t + (size_t)A.max_gt * A.cap;
-    const double *Pg = xy + (size_t)g * 16;
+    const double *Pg = xy + (size_t)g * (2 * MAXV);
     const int ng = nvv[g];
     const double ag = tab[g];
     for (int f = threadIdx.x; f < F; f += 64) {
-        const double *Pf = xy + (size_t)(A.max_gt + f) * 16;
+        const double *Pf = xy + (size_t)(A.max_gt + f) * (2 * MAXV);
         const int nf = nvv[A.max_gt + f];
         const double af = tab[A.max_gt + f];
         double inter = 0.0;
@@ -225,20 +238,21 @@ __global__ __launch_bounds__(64) void ev_tables_kernel(const int32_t *__restrict
 // list[0..m): polygon slots.  ivl: this wave's LDS interval list (2 * (EV_MAX_GT + EV_MAX_FOUND) doubles).  Every thread returns
 // the same value.  Work unit = (polygon, edge): waves take units round robin, lanes walk the other polygons; the fixed assignment
 // and the fixed reduction trees make the sum independent of timing.
+template <int MAXV>
 __device__ double ev_union_area(const ev_image &im, const short *list, int m, double *ivl, double *wsum)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double acc = 0.0;
     if (m > 0) {
-        const double *P0 = im.xy + (size_t)list[0] * 16;
+        const double *P0 = im.xy + (size_t)list[0] * (2 * MAXV);
         const double rx = P0[0], ry = P0[1];
-        for (int u = w; u < m * EV_MAX_V; u += EV_WAVES) {
-            const int is = u / EV_MAX_V, e = u % EV_MAX_V;
+        for (int u = w; u < m * MAXV; u += EV_WAVES) {
+            const int is = u / MAXV, e = u % MAXV;
             const int si = list[is];
             const int nvi = im.nv[si];
             const double ai = si < im.max_gt ? im.area_g[si] : im.area_f[si - im.max_gt];
             if (e >= nvi || !(ai > 0.0)) continue;
-            const double *Pi = im.xy + (size_t)si * 16;
+            const double *Pi = im.xy + (size_t)si * (2 * MAXV);
             const int e1 = e + 1 == nvi ? 0 : e + 1;
             const double ax = Pi[2 * e], ay = Pi[2 * e + 1], bx = Pi[2 * e1], by = Pi[2 * e1 + 1];
             if (ax == bx && ay == by) continue;
@@ -250,7 +264,7 @@ __device__ double ev_union_area(const ev_image &im, const short *list, int m, do
                 if (js < m && js != is) {
                     const int sj = list[js];
                     const double aj = sj < im.max_gt ? im.area_g[sj] : im.area_f[sj - im.max_gt];
-                    if (aj > 0.0) have = ev_edge_interval(ax, ay, bx, by, im.xy + (size_t)sj * 16, im.nv[sj], sj < si, lo, hi);
+                    if (aj > 0.0) have = ev_edge_interval(ax, ay, bx, by, im.xy + (size_t)sj * (2 * MAXV), im.nv[sj], sj < si, lo, hi);
                 }
                 const unsigned long long mask = __ballot(have);
                 if (have) {
@@ -294,6 +308,7 @@ __device__ double ev_union_area(const ev_image &im, const short *list, int m, do
 }
 
 // ---- phase 3: matching, group and by-area unions, per-threshold records (evaluation.py:229-404) ---------------------------------
+template <int MAXV>
 __global__ __launch_bounds__(EV_THREADS) void ev_match_kernel(const int32_t *__restrict__ classes, const int32_t *__restrict__ counts,
                                                               const int32_t *__restrict__ gt_class, char *__restrict__ ws, ev_layout L,
                                                               ev_launch A, const int32_t *__restrict__ flags,
@@ -326,7 +341,7 @@ __global__ __launch_bounds__(EV_THREADS) void ev_match_kernel(const int32_t *__r
         return;
     }
     ev_image im;
-    im.xy = (const double *)(ws + L.off_xy) + (size_t)img * L.P * 16;
+    im.xy = (const double *)(ws + L.off_xy) + (size_t)img * L.P * (2 * MAXV);
     im.nv = (const int32_t *)(ws + L.off_nv) + (size_t)img * L.P;
     const double *tab = (const double *)(ws + L.off_tab) + (size_t)img * L.tab_stride;
     im.area_g = tab; im.area_f = tab + A.max_gt;
@@ -373,9 +388,9 @@ __global__ __launch_bounds__(EV_THREADS) void ev_match_kernel(const int32_t *__r
     // by area (evaluation.py:389-404): union of all ground truths against union of all found quads
     for (int k = tid; k < G + F; k += EV_THREADS) s_list[k] = (short)(k < G ? k : A.max_gt + (k - G));
     __syncthreads();
-    const double area_G = ev_union_area(im, s_list, G, s_ivl[w], s_wsum);
-    const double area_F = ev_union_area(im, s_list + G, F, s_ivl[w], s_wsum);
-    const double area_all = ev_union_area(im, s_list, G + F, s_ivl[w], s_wsum);
+    const double area_G = ev_union_area<MAXV>(im, s_list, G, s_ivl[w], s_wsum);
+    const double area_F = ev_union_area<MAXV>(im, s_list + G, F, s_ivl[w], s_wsum);
+    const double area_all = ev_union_area<MAXV>(im, s_list, G + F, s_ivl[w], s_wsum);
     const double inter_GF = fmin(fmax(area_G + area_F - area_all, 0.0), fmin(area_G, area_F));
     const double p_area = area_F > 0.0 ? inter_GF / area_F : 0.0;
     const double r_area = area_G > 0.0 ? inter_GF / area_G : 0.0;
@@ -400,8 +415,8 @@ __global__ __launch_bounds__(EV_THREADS) void ev_match_kernel(const int32_t *__r
             }
             __syncthreads();
             const int m = s_m;
-            const double a_group = ev_union_area(im, s_list, m, s_ivl[w], s_wsum);
-            const double a_all = ev_union_area(im, s_list, m + 1, s_ivl[w], s_wsum);
+            const double a_group = ev_union_area<MAXV>(im, s_list, m, s_ivl[w], s_wsum);
+            const double a_all = ev_union_area<MAXV>(im, s_list, m + 1, s_ivl[w], s_wsum);
             const double a_box = pass == 0 ? im.area_g[o] : im.area_f[o];
             const double inter = fmin(fmax(a_group + a_box - a_all, 0.0), fmin(a_group, a_box));
             if (tid == 0) { if (pass == 0) s_iou_g[o] = ev_iou(a_group, a_box, inter); else s_iou_f[o] = ev_iou(a_group, a_box, inter); }
@@ -508,25 +523,105 @@ extern "C" size_t ubd_evaluate_accumulator_bytes(int n_thresholds, int n_classes
     return ((size_t)EV_ACC_HEAD + (size_t)EV_ACC_PER_T * n_thresholds + (size_t)n_thresholds * n_classes * n_classes) * 8;
 }
 
-extern "C" size_t ubd_evaluate_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes)
+static_assert(EV_MAX_V % EV_WAVES == 0 && UBD_POLY_MAX_VERTS % EV_WAVES == 0, "an edge must land in the same wave for either slot size");
+
+static size_t ev_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes, int maxv)
 {
     if (n < 1 || max_gt < 1 || max_gt > EV_MAX_GT || cap < 1 || cap > EV_MAX_FOUND || n_thresholds < 1 || n_thresholds > EV_MAX_T ||
         n_classes < 0 || n_classes > UBD_MAX_CLASSES)
         return 0;
     ev_layout L;
-    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, &L);
+    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, maxv, &L);
     return L.total + (size_t)n * sizeof(int32_t) + 256;          // + the per-image flags
+}
+
+extern "C" size_t ubd_evaluate_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes)
+{
+    return ev_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes, EV_MAX_V);
+}
+
+extern "C" size_t ubd_evaluate_polygons_workspace_bytes(int n, int max_gt, int cap, int n_thresholds, int n_classes, int max_verts)
+{
+    if (max_verts < 3 || max_verts > UBD_POLY_MAX_VERTS) return 0;
+    return ev_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes, UBD_POLY_MAX_VERTS);
+}
+
+static int ev_tables_layout(const char *who, int n, int max_gt, int cap, int n_thresholds, int n_classes, int maxv, int64_t *offset_bytes,
+                            int64_t *stride_doubles)
+{
+    UBD_REQUIRE(offset_bytes && stride_doubles, "%s: null argument", who);
+    UBD_REQUIRE(ev_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes, maxv) != 0, "%s: bad sizes", who);
+    ev_layout L;
+    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, maxv, &L);
+    *offset_bytes = (int64_t)L.off_tab;
+    *stride_doubles = (int64_t)L.tab_stride;
+    return 0;
 }
 
 extern "C" int ubd_evaluate_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int64_t *offset_bytes,
                                           int64_t *stride_doubles)
 {
-    UBD_REQUIRE(offset_bytes && stride_doubles, "ubd_evaluate_tables_layout: null argument");
-    UBD_REQUIRE(ubd_evaluate_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes) != 0, "ubd_evaluate_tables_layout: bad sizes");
+    return ev_tables_layout("ubd_evaluate_tables_layout", n, max_gt, cap, n_thresholds, n_classes, EV_MAX_V, offset_bytes, stride_doubles);
+}
+
+extern "C" int ubd_evaluate_polygons_tables_layout(int n, int max_gt, int cap, int n_thresholds, int n_classes, int max_verts,
+                                                   int64_t *offset_bytes, int64_t *stride_doubles)
+{
+    UBD_REQUIRE(max_verts >= 3 && max_verts <= UBD_POLY_MAX_VERTS, "ubd_evaluate_polygons_tables_layout: max_verts must be 3..%d, got %d",
+                UBD_POLY_MAX_VERTS, max_verts);
+    return ev_tables_layout("ubd_evaluate_polygons_tables_layout", n, max_gt, cap, n_thresholds, n_classes, UBD_POLY_MAX_VERTS, offset_bytes,
+                            stride_doubles);
+}
+
+template <int MAXV>
+static int ev_evaluate(const char *who, const int32_t *quads, const int32_t *classes, const int32_t *counts, int n, int cap,
+                       const double *scales, const double *gt_xy, int n_gt_vertices, const int32_t *gt_first,
+                       const int32_t *gt_class, const int32_t *gt_image_first, int max_gt, const double *thresholds,
+                       int n_thresholds, int n_classes, int max_verts, ubd_eval_record *per_image, void *accumulator, void *workspace,
+                       size_t workspace_bytes, void *stream)
+{
+    UBD_REQUIRE(quads && counts && gt_xy && gt_first && gt_image_first && thresholds, "%s: null argument", who);
+    UBD_REQUIRE(accumulator, "%s: null accumulator", who);
+    UBD_REQUIRE(workspace, "%s: null workspace", who);
+    UBD_REQUIRE(n >= 1, "%s: n must be >= 1, got %d", who, n);
+    UBD_REQUIRE(cap >= 1 && cap <= EV_MAX_FOUND, "%s: cap must be 1..%d, got %d", who, EV_MAX_FOUND, cap);
+    UBD_REQUIRE(n_thresholds >= 1 && n_thresholds <= EV_MAX_T, "%s: n_thresholds must be 1..%d, got %d", who, EV_MAX_T, n_thresholds);
+    UBD_REQUIRE(n_classes >= 0 && n_classes <= UBD_MAX_CLASSES, "%s: n_classes must be 0..%d, got %d", who, UBD_MAX_CLASSES, n_classes);
+    UBD_REQUIRE(n_classes == 0 || (classes && gt_class), "%s: classes and gt_class are required when n_classes > 0", who);
+    UBD_REQUIRE(max_gt >= 1 && max_gt <= EV_MAX_GT, "%s: max_gt must be 1..%d, got %d", who, EV_MAX_GT, max_gt);
+    UBD_REQUIRE(max_verts >= 3 && max_verts <= MAXV, "%s: max_verts must be 3..%d, got %d", who, MAXV, max_verts);
+    UBD_REQUIRE(n_gt_vertices >= 0, "%s: n_gt_vertices is negative", who);
+    UBD_REQUIRE(gt_image_first[0] >= 0, "%s: gt_image_first[0] is negative", who);
+    for (int i = 0; i < n; ++i) {
+        const int64_t g = (int64_t)gt_image_first[i + 1] - gt_image_first[i];
+        UBD_REQUIRE(g >= 0, "%s: gt_image_first decreases at image %d", who, i);
+        UBD_REQUIRE(g <= EV_MAX_GT, "%s: image %d has %lld ground-truth polygons, the limit is %d", who, i, (long long)g, EV_MAX_GT);
+        UBD_REQUIRE(g <= max_gt, "%s: image %d has %lld ground-truth polygons, max_gt is %d", who, i, (long long)g, max_gt);
+    }
+    for (int t = 0; t < n_thresholds; ++t)
+        UBD_REQUIRE(thresholds[t] == thresholds[t], "%s: threshold %d is not a number", who, t);
     ev_layout L;
-    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, &L);
-    *offset_bytes = (int64_t)L.off_tab;
-    *stride_doubles = (int64_t)L.tab_stride;
+    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, MAXV, &L);
+    const size_t need = ev_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes, MAXV);
+    UBD_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+    char *ws = (char *)workspace;
+    int32_t *flags = (int32_t *)(ws + L.total);
+    hipStream_t st = (hipStream_t)stream;
+    for (int i0 = 0; i0 < n; i0 += EV_MAX_IMGS) {
+        ev_launch A{};
+        A.m = std::min(EV_MAX_IMGS, n - i0);
+        A.img0 = i0; A.max_gt = max_gt; A.cap = cap; A.T = n_thresholds; A.C = n_classes; A.max_verts = max_verts;
+        A.n_gt_verts = n_gt_vertices;
+        int gmax = 1;
+        for (int k = 0; k <= A.m; ++k) A.gt0[k] = gt_image_first[i0 + k];
+        for (int k = 0; k < A.m; ++k) gmax = std::max(gmax, A.gt0[k + 1] - A.gt0[k]);
+        for (int t = 0; t < n_thresholds; ++t) A.thr[t] = thresholds[t];
+        hipLaunchKernelGGL(ev_prepare_kernel<MAXV>, dim3(A.m), dim3(EV_THREADS), 0, st, quads, counts, scales, gt_xy, gt_first, ws, L, A, flags);
+        hipLaunchKernelGGL(ev_tables_kernel<MAXV>, dim3(gmax, A.m), dim3(64), 0, st, counts, ws, L, A);
+        hipLaunchKernelGGL(ev_match_kernel<MAXV>, dim3(A.m), dim3(EV_THREADS), 0, st, classes, counts, gt_class, ws, L, A, (const int32_t *)flags, per_image);
+        hipLaunchKernelGGL(ev_accumulate_kernel, dim3(1), dim3(EV_THREADS), 0, st, (const char *)ws, L, A, accumulator);
+        UBD_CHECK_HIP(hipGetLastError());
+    }
     return 0;
 }
 
@@ -536,46 +631,20 @@ extern "C" int ubd_evaluate_objects(const int32_t *quads, const int32_t *classes
                                     int n_thresholds, int n_classes, ubd_eval_record *per_image, void *accumulator, void *workspace,
                                     size_t workspace_bytes, void *stream)
 {
-    UBD_REQUIRE(quads && counts && gt_xy && gt_first && gt_image_first && thresholds, "ubd_evaluate_objects: null argument");
-    UBD_REQUIRE(accumulator, "ubd_evaluate_objects: null accumulator");
-    UBD_REQUIRE(workspace, "ubd_evaluate_objects: null workspace");
-    UBD_REQUIRE(n >= 1, "ubd_evaluate_objects: n must be >= 1, got %d", n);
-    UBD_REQUIRE(cap >= 1 && cap <= EV_MAX_FOUND, "ubd_evaluate_objects: cap must be 1..%d, got %d", EV_MAX_FOUND, cap);
-    UBD_REQUIRE(n_thresholds >= 1 && n_thresholds <= EV_MAX_T, "ubd_evaluate_objects: n_thresholds must be 1..%d, got %d", EV_MAX_T, n_thresholds);
-    UBD_REQUIRE(n_classes >= 0 && n_classes <= UBD_MAX_CLASSES, "ubd_evaluate_objects: n_classes must be 0..%d, got %d", UBD_MAX_CLASSES, n_classes);
-    UBD_REQUIRE(n_classes == 0 || (classes && gt_class), "ubd_evaluate_objects: classes and gt_class are required when n_classes > 0");
-    UBD_REQUIRE(max_gt >= 1 && max_gt <= EV_MAX_GT, "ubd_evaluate_objects: max_gt must be 1..%d, got %d", EV_MAX_GT, max_gt);
-    UBD_REQUIRE(n_gt_vertices >= 0, "ubd_evaluate_objects: n_gt_vertices is negative");
-    UBD_REQUIRE(gt_image_first[0] >= 0, "ubd_evaluate_objects: gt_image_first[0] is negative");
-    for (int i = 0; i < n; ++i) {
-        const int64_t g = (int64_t)gt_image_first[i + 1] - gt_image_first[i];
-        UBD_REQUIRE(g >= 0, "ubd_evaluate_objects: gt_image_first decreases at image %d", i);
-        UBD_REQUIRE(g <= EV_MAX_GT, "ubd_evaluate_objects: image %d has %lld ground-truth polygons, the limit is %d", i, (long long)g, EV_MAX_GT);
-        UBD_REQUIRE(g <= max_gt, "ubd_evaluate_objects: image %d has %lld ground-truth polygons, max_gt is %d", i, (long long)g, max_gt);
-    }
-    for (int t = 0; t < n_thresholds; ++t)
-        UBD_REQUIRE(thresholds[t] == thresholds[t], "ubd_evaluate_objects: threshold %d is not a number", t);
-    ev_layout L;
-    ev_layout_compute(n, max_gt, cap, n_thresholds, n_classes, &L);
-    const size_t need = ubd_evaluate_workspace_bytes(n, max_gt, cap, n_thresholds, n_classes);
-    UBD_REQUIRE(workspace_bytes >= need, "ubd_evaluate_objects: workspace too small (%zu < %zu)", workspace_bytes, need);
-    char *ws = (char *)workspace;
-    int32_t *flags = (int32_t *)(ws + L.total);
-    hipStream_t st = (hipStream_t)stream;
-    for (int i0 = 0; i0 < n; i0 += EV_MAX_IMGS) {
-        ev_launch A{};
-        A.m = std::min(EV_MAX_IMGS, n - i0);
-        A.img0 = i0; A.max_gt = max_gt; A.cap = cap; A.T = n_thresholds; A.C = n_classes;
-        A.n_gt_verts = n_gt_vertices;
-        int gmax = 1;
-        for (int k = 0; k <= A.m; ++k) A.gt0[k] = gt_image_first[i0 + k];
-        for (int k = 0; k < A.m; ++k) gmax = std::max(gmax, A.gt0[k + 1] - A.gt0[k]);
-        for (int t = 0; t < n_thresholds; ++t) A.thr[t] = thresholds[t];
-        hipLaunchKernelGGL(ev_prepare_kernel, dim3(A.m), dim3(EV_THREADS), 0, st, quads, counts, scales, gt_xy, gt_first, ws, L, A, flags);
-        hipLaunchKernelGGL(ev_tables_kernel, dim3(gmax, A.m), dim3(64), 0, st, counts, ws, L, A);
-        hipLaunchKernelGGL(ev_match_kernel, dim3(A.m), dim3(EV_THREADS), 0, st, classes, counts, gt_class, ws, L, A, (const int32_t *)flags, per_image);
-        hipLaunchKernelGGL(ev_accumulate_kernel, dim3(1), dim3(EV_THREADS), 0, st, (const char *)ws, L, A, accumulator);
-        UBD_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
+    return ev_evaluate<EV_MAX_V>("ubd_evaluate_objects", quads, classes, counts, n, cap, scales, gt_xy, n_gt_vertices, gt_first, gt_class,
+                                 gt_image_first, max_gt, thresholds, n_thresholds, n_classes, EV_MAX_V, per_image, accumulator, workspace,
+                                 workspace_bytes, stream);
+}
+
+extern "C" int ubd_evaluate_polygons(const int32_t *quads, const int32_t *classes, const int32_t *counts, int n, int cap,
+                                     const double *scales, const double *gt_xy, int n_gt_vertices, const int32_t *gt_first,
+                                     const int32_t *gt_class, const int32_t *gt_image_first, int max_gt, const double *thresholds,
+                                     int n_thresholds, int n_classes, int max_verts, ubd_eval_record *per_image, void *accumulator,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    UBD_REQUIRE(max_verts >= 3 && max_verts <= UBD_POLY_MAX_VERTS, "ubd_evaluate_polygons: max_verts must be 3..%d, got %d",
+                UBD_POLY_MAX_VERTS, max_verts);
+    return ev_evaluate<UBD_POLY_MAX_VERTS>("ubd_evaluate_polygons", quads, classes, counts, n, cap, scales, gt_xy, n_gt_vertices, gt_first,
+                                           gt_class, gt_image_first, max_gt, thresholds, n_thresholds, n_classes, max_verts, per_image,
+                                           accumulator, workspace, workspace_bytes, stream);
 }

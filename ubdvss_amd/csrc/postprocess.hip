@@ -632,3 +632,129 @@ extern "C" int ubd_postprocess(ubd_handle *hd, const float *logits, int n, int m
     UBD_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// ------------------------------------------------------------------------------------ segmentation maps -> hull polygons
+// ubd_segmap_polygons (markup_readers.py:271-285): the ground truth of a data set given as segmentation maps.  The labelling is
+// the global-memory front end above with min_area = -1 (every external component is kept, its bit-quad area is not needed), the
+// row extents and hull_from_rows are the postprocess' own; only the first and the last step are new: foreground from a byte
+// map, and the hull written out as a polygon instead of going on to minAreaRect.
+// blockDim must be a multiple of 64; lanes of a wave hold 64 consecutive flat pixels.  pp_init_kernel's run initialisation on a byte
+// map: a copy, not a template over the foreground test, so that the postprocess' own kernel stays the text it was.
+__global__ __launch_bounds__(256) void sp_init_kernel(const unsigned char *__restrict__ maps, long npix, int hw, int w,
+                                                      unsigned char *__restrict__ fg, int *__restrict__ label)
+{
+    const int lane = threadIdx.x & 63;
+    const long nround = (npix + 63) / 64 * 64;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < nround; p += (long)gridDim.x * blockDim.x) {
+        const bool valid = p < npix;
+        int f = 0, img = 0, loc = 0, x = 0;
+        if (valid) {
+            img = (int)(p / hw); loc = (int)(p % hw); x = loc % w;
+            f = maps[p] != 0 ? 1 : 0;
+            fg[p] = (unsigned char)f;
+        }
+        int fl = __shfl_up(f, 1, 64);
+        if (lane == 0 && valid && x > 0) fl = maps[p - 1] != 0 ? 1 : 0;
+        const bool same_left = valid && x > 0 && fl == f;
+        const unsigned long long breaks = __ballot(!same_left);  // bit l: lane l starts a run (or is invalid)
+        if (valid) {
+            const unsigned long long below = breaks & ((2ull << lane) - 1ull);   // lanes <= mine
+            int start_off;                                        // distance back to the run start
+            if (below) start_off = lane - (63 - __clzll(below));
+            else start_off = lane + 1;                            // run continues into the previous wave: link there
+            int *lab = label + (size_t)img * (hw + 1);
+            lab[loc + 1] = loc + 1 - start_off;
+            if (loc == 0) lab[0] = 0;
+        }
+    }
+}
+
+// One lane per object: hull from the row extents, then the cycle of cv2.convexHull(clockwise=False): hull_from_rows' cycle
+// reversed, started at the vertex with the greatest x (greatest y among equals).  Written at the object's rank in cv2's
+// return order (last discovered first), as pp_emit_kernel ranks the quads.
+__global__ __launch_bounds__(64) void sp_hulls_kernel(int n, int h, int w, const int *__restrict__ nkept, const int *__restrict__ stage,
+                                                      const int *__restrict__ ymax, int *__restrict__ rows_ws, int cap,
+                                                      int *__restrict__ verts, int *__restrict__ nverts, int *__restrict__ counts)
+{
+    const long total = (long)n * cap;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        const int img = (int)(t / cap), k = (int)(t % cap);
+        const int found = nkept[img];
+        if (k == 0) counts[img] = found;
+        const int nk = min(found, cap);
+        if (k >= nk) continue;
+        const int *st = stage + (size_t)img * cap * STAGE_INTS;
+        const int root = st[k * STAGE_INTS];
+        int rank = 0;
+        for (int j = 0; j < nk; ++j) rank += (st[j * STAGE_INTS] > root) ? 1 : 0;
+        const int y0 = root / w;
+        const int nrows = ymax[(size_t)img * cap + k] - y0 + 1;
+        int *rows = rows_ws + ((size_t)img * cap + k) * (size_t)(6 * h);
+        ipt *pts = (ipt *)(rows + 2 * h);                             // 4h ints = room for 2h points
+        const int nh = hull_from_rows(rows + 2 * y0, nrows, y0, pts);
+        int s = 0;
+        for (int j = 1; j < nh; ++j)
+            if (pts[j].x > pts[s].x || (pts[j].x == pts[s].x && pts[j].y > pts[s].y)) s = j;
+        int *out = verts + ((size_t)img * cap + rank) * (size_t)(2 * UBD_POLY_MAX_VERTS);
+        const int nout = min(nh, UBD_POLY_MAX_VERTS);
+        for (int j = 0; j < nout; ++j) {
+            int from = s - j;
+            if (from < 0) from += nh;
+            out[2 * j] = pts[from].x; out[2 * j + 1] = pts[from].y;
+        }
+        nverts[(size_t)img * cap + rank] = nh;
+    }
+}
+
+static bool sp_sizes_ok(int n, int map_h, int map_w, int cap)
+{
+    return n >= 1 && map_h >= 1 && map_w >= 1 && map_h < 32768 && map_w < 32768 && (long)n * map_h * map_w < (1L << 31) && cap >= 1 &&
+           cap <= UBD_EVAL_MAX_GT;
+}
+
+extern "C" size_t ubd_segmap_polygons_workspace_bytes(int n, int map_h, int map_w, int cap)
+{
+    if (!sp_sizes_ok(n, map_h, map_w, cap)) return 0;
+    pp_layout L;
+    pp_layout_compute(n, map_h, map_w, cap, 0, &L);
+    return L.total;
+}
+
+extern "C" int ubd_segmap_polygons(const uint8_t *maps, int n, int map_h, int map_w, int32_t *verts, int32_t *nverts, int32_t *counts,
+                                   int cap, void *workspace, size_t workspace_bytes, void *stream)
+{
+    UBD_REQUIRE(maps && verts && nverts && counts && workspace, "ubd_segmap_polygons: null argument");
+    UBD_REQUIRE(n >= 1 && map_h >= 1 && map_w >= 1 && map_h < 32768 && map_w < 32768, "ubd_segmap_polygons: bad sizes n=%d h=%d w=%d (n >= 1, sides 1..32767)", n, map_h, map_w);
+    UBD_REQUIRE((long)n * map_h * map_w < (1L << 31), "ubd_segmap_polygons: batch too large (n * h * w must stay below 2^31)");
+    UBD_REQUIRE(cap >= 1 && cap <= UBD_EVAL_MAX_GT, "ubd_segmap_polygons: cap must be 1..%d, got %d", UBD_EVAL_MAX_GT, cap);
+    pp_layout L;
+    pp_layout_compute(n, map_h, map_w, cap, 0, &L);
+    UBD_REQUIRE(workspace_bytes >= L.total, "ubd_segmap_polygons: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    int *nroots = (int *)(ws + L.off_nroots), *nkept = (int *)(ws + L.off_nkept);
+    int *label = (int *)(ws + L.off_label);
+    unsigned char *fg = (unsigned char *)(ws + L.off_fg);
+    int *owner = (int *)(ws + L.off_owner), *rootslot = (int *)(ws + L.off_rootslot);
+    int *roots = (int *)(ws + L.off_roots), *area2 = (int *)(ws + L.off_area2), *kept = (int *)(ws + L.off_kept);
+    int *stage = (int *)(ws + L.off_stage), *ymax = (int *)(ws + L.off_ymax), *rows = (int *)(ws + L.off_rows);
+    const int hw = map_h * map_w;
+    const long npix = (long)n * hw;
+    int grid = (int)((npix + 255) / 256);
+    if (grid > 256 * 8) grid = 256 * 8;
+    UBD_CHECK_HIP(hipMemsetAsync(ws, 0, L.off_label, st));          // the two per-image counters
+    hipLaunchKernelGGL(sp_init_kernel, dim3(grid), dim3(256), 0, st, maps, npix, hw, map_w, fg, label);
+    hipLaunchKernelGGL(pp_merge_kernel, dim3(grid), dim3(256), 0, st, fg, label, npix, map_h, map_w);
+    hipLaunchKernelGGL(pp_flatten_kernel, dim3(grid), dim3(256), 0, st, label, n, hw);
+    hipLaunchKernelGGL(pp_roots_kernel, dim3(grid), dim3(256), 0, st, fg, label, npix, map_h, map_w, nroots, roots, rootslot, area2, L.root_cap);
+    hipLaunchKernelGGL(pp_owner_kernel, dim3(grid), dim3(256), 0, st, fg, label, rootslot, npix, map_h, map_w, owner);
+    // min_area = -1: area2 is 0 at every root (pp_roots_kernel), 0 > -1 keeps them all
+    hipLaunchKernelGGL(pp_keep_kernel, dim3(n), dim3(256), 0, st, n, map_h, nroots, roots, area2, L.root_cap, -1.f, nkept, kept, stage, ymax, rows, cap, (float *)nullptr, 0);
+    hipLaunchKernelGGL(pp_extents_kernel, dim3(grid), dim3(256), 0, st, owner, kept, npix, map_h, map_w, L.root_cap, cap, rows, ymax);
+    const long total = (long)n * cap;
+    int hgrid = (int)((total + 63) / 64);
+    if (hgrid > 256 * 8) hgrid = 256 * 8;
+    hipLaunchKernelGGL(sp_hulls_kernel, dim3(hgrid), dim3(64), 0, st, n, map_h, map_w, nkept, stage, ymax, rows, cap, verts, nverts, counts);
+    UBD_CHECK_HIP(hipGetLastError());
+    return 0;
+}

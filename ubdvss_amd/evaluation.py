@@ -11,7 +11,9 @@ sums go to a second small accumulator and the correctness mask comes back as a d
 There is no CPU path: without a GPU the entry points raise ``RuntimeError``.
 
 ``ImageResultCategories`` (:579-628) sorts an image's result into the folders the result saver writes; the overlays themselves
-are ``ubdvss_amd.visualizations``.  Not here: non-convex ground truth.
+are ``ubdvss_amd.visualizations``.  Ground truth of up to 8 vertices goes through ``ubd_evaluate_objects``; as soon as a
+polygon of a call has more (hulls read from segmentation maps, ``ubdvss_amd.markup_readers``: up to 64) the call goes through
+``ubd_evaluate_polygons``, which gives the same bits on common ground.  Not here: non-convex outlines as such.
 """
 import ctypes
 import math
@@ -140,16 +142,17 @@ def _check_class_ids(ids, n_classes, where):
             raise ValueError(f"{where}: object type id {int(c)} is outside 0..{n_classes - 1}")
 
 
-def check_ground_truth_polygon(coords, image_idx=0, object_idx=0):
-    """A ground-truth polygon the device accepts: 3..8 vertices, finite, convex (either winding; collinear vertices allowed).
+def check_ground_truth_polygon(coords, image_idx=0, object_idx=0, max_vertices=_lib.UBD_EVAL_MAX_VERTS):
+    """A ground-truth polygon the device accepts: 3..max_vertices vertices (8 for ubd_evaluate_objects, up to 64 for
+    ubd_evaluate_polygons), finite, convex (either winding; collinear vertices allowed).
     Returns the (k, 2) float64 vertices; raises ValueError naming the image and the object otherwise."""
     where = f"ground truth of image {image_idx}, object {object_idx}"
     p = np.asarray(coords, dtype=np.float64).reshape(-1)
     if p.size % 2 or p.size < 6:
         raise ValueError(f"{where}: a polygon needs at least 3 vertices (x, y pairs), got {p.size} numbers")
     p = p.reshape(-1, 2)
-    if len(p) > _lib.UBD_EVAL_MAX_VERTS:
-        raise ValueError(f"{where}: {len(p)} vertices, the limit is {_lib.UBD_EVAL_MAX_VERTS}")
+    if len(p) > max_vertices:
+        raise ValueError(f"{where}: {len(p)} vertices, the limit is {max_vertices}")
     if not np.isfinite(p).all():
         raise ValueError(f"{where}: coordinates are not finite")
     if not _is_convex(p):
@@ -167,7 +170,9 @@ def _require_gpu():
 def pack_ground_truth(gt_polygons, gt_classes=None, image_offset=0, n_classes=None):
     """gt_polygons: per image a list of flat coordinate lists.  Returns host arrays (xy float64 (V, 2), first int32 (P + 1),
     cls int32 (P) or None, image_first int32 (n + 1), max_gt).  Raises ValueError for an image without ground truth
-    (evaluation.py:482), too many polygons in one image, a polygon the device does not accept, or (n_classes given) a class id outside 0..n_classes-1."""
+    (evaluation.py:482), too many polygons in one image, a polygon the device does not accept (more than 64 vertices, not
+    convex, ...), or (n_classes given) a class id outside 0..n_classes-1.  Which entry point takes the call follows from the
+    data: ``np.diff(first).max()`` is the most vertices a polygon has."""
     xy, first, cls, image_first = [], [0], [], [0]
     max_gt = 1
     for i, polys in enumerate(gt_polygons):
@@ -177,7 +182,7 @@ def pack_ground_truth(gt_polygons, gt_classes=None, image_offset=0, n_classes=No
             raise ValueError(f"image {image_offset + i} has {len(polys)} ground-truth objects, the limit is {_lib.UBD_EVAL_MAX_GT}")
         max_gt = max(max_gt, len(polys))
         for o, c in enumerate(polys):
-            p = check_ground_truth_polygon(c, image_offset + i, o)
+            p = check_ground_truth_polygon(c, image_offset + i, o, _lib.UBD_POLY_MAX_VERTS)
             xy.append(p)
             first.append(first[-1] + len(p))
         if gt_classes is not None:
@@ -221,22 +226,33 @@ def evaluate_objects(quads, classes, counts, gt_polygons, gt_classes, thresholds
     cls_d = torch.from_numpy(cls).to(dev) if cls is not None else None
     if scales is not None and not hasattr(scales, "data_ptr"):
         scales = torch.from_numpy(np.ascontiguousarray(np.asarray(scales, dtype=np.float64).reshape(n, 2))).to(dev)
-    need = int(lib.ubd_evaluate_workspace_bytes(n, max_gt, cap, T, C))
+    # by data: ground truth of at most 8 vertices takes ubd_evaluate_objects as ever, anything larger ubd_evaluate_polygons
+    most_verts = int(np.diff(first).max())
+    polygons = most_verts > _lib.UBD_EVAL_MAX_VERTS
+    need = int(lib.ubd_evaluate_polygons_workspace_bytes(n, max_gt, cap, T, C, most_verts) if polygons
+               else lib.ubd_evaluate_workspace_bytes(n, max_gt, cap, T, C))
     if need == 0:
         raise ValueError(f"evaluation sizes outside the limits: n={n} max_gt={max_gt} cap={cap} thresholds={T} classes={C} "
                          f"(cap <= {_lib.UBD_EVAL_MAX_FOUND}, thresholds <= {_lib.UBD_EVAL_MAX_THRESHOLDS})")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     rec = torch.empty((n, T, _REC_BYTES), dtype=torch.uint8, device=dev) if per_image else None
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.ubd_evaluate_objects(
-        quads.data_ptr(), classes.data_ptr() if (classes is not None and C > 0) else None, counts.data_ptr(), n, cap,
-        scales.data_ptr() if scales is not None else None, xy_d.data_ptr(), int(len(xy)), first_d.data_ptr(),
-        cls_d.data_ptr() if cls_d is not None else None, image_first.ctypes.data, max_gt, thr.ctypes.data, T, C,
-        rec.data_ptr() if rec is not None else None, accumulator.data_ptr(), ws.data_ptr(), need, stream), "ubd_evaluate_objects")
+    head = (quads.data_ptr(), classes.data_ptr() if (classes is not None and C > 0) else None, counts.data_ptr(), n, cap,
+            scales.data_ptr() if scales is not None else None, xy_d.data_ptr(), int(len(xy)), first_d.data_ptr(),
+            cls_d.data_ptr() if cls_d is not None else None, image_first.ctypes.data, max_gt, thr.ctypes.data, T, C)
+    tail = (rec.data_ptr() if rec is not None else None, accumulator.data_ptr(), ws.data_ptr(), need, stream)
+    if polygons:
+        _lib.check(lib.ubd_evaluate_polygons(*head, most_verts, *tail), "ubd_evaluate_polygons")
+    else:
+        _lib.check(lib.ubd_evaluate_objects(*head, *tail), "ubd_evaluate_objects")
     # the inputs and the workspace were allocated on this stream: the caching allocator reuses them in stream order
     if return_tables:
         off, stride = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(lib.ubd_evaluate_tables_layout(n, max_gt, cap, T, C, ctypes.byref(off), ctypes.byref(stride)), "ubd_evaluate_tables_layout")
+        if polygons:
+            _lib.check(lib.ubd_evaluate_polygons_tables_layout(n, max_gt, cap, T, C, most_verts, ctypes.byref(off), ctypes.byref(stride)),
+                       "ubd_evaluate_polygons_tables_layout")
+        else:
+            _lib.check(lib.ubd_evaluate_tables_layout(n, max_gt, cap, T, C, ctypes.byref(off), ctypes.byref(stride)), "ubd_evaluate_tables_layout")
         return rec, (ws, off.value, stride.value, max_gt)
     return rec
 
@@ -427,7 +443,7 @@ def _metrics_from_record(r, confusion, all_type_names, with_cls):
 
 
 class FtMetricsCalculator:
-    """evaluation.py:168-328 for one image through the device call.  gt_boxes: convex polygons of 3..8 vertices (flat
+    """evaluation.py:168-328 for one image through the device call.  gt_boxes: convex polygons of 3..64 vertices (flat
     coordinate lists); found_boxes: integer quadrilaterals.  The types are names out of all_object_types."""
 
     def __init__(self, gt_boxes, found_boxes, gt_object_types=None, found_object_types=None, all_object_types=None,
@@ -439,7 +455,7 @@ class FtMetricsCalculator:
         if len(self._gt) == 0:
             raise ValueError("empty gt bboxes in image 0 (it should contain at least one bbox)")
         for o, b in enumerate(self._gt):
-            check_ground_truth_polygon(b, 0, o)
+            check_ground_truth_polygon(b, 0, o, _lib.UBD_POLY_MAX_VERTS)
         self._found = [np.asarray(b).reshape(-1) for b in found_boxes]
         self._gt_ids = self._found_ids = None
         if self._with_cls:

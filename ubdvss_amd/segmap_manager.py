@@ -179,7 +179,8 @@ class SegmapManager:
     @staticmethod
     def build_segmentation_map(image, markup, scale=1, for_drawing=False):
         """Training label map (behaviour of segmap_manager.py:81-104): every quad is divided by ``scale``, its
-        corners are snapped outward (``_proper_round``) and the polygon is filled, later objects over earlier
+        corners are snapped outward (``_proper_round``; a polygon of another vertex count, 3..64 -- markup read from
+        segmentation maps -- is truncated instead, as the reference does) and the polygon is filled, later objects over earlier
         ones, with 255 (``for_drawing``), class id + 1 (classified markup) or 1.  Returns a PIL 'L' image of
         size (W/scale, H/scale)."""
         width, height = image.size
@@ -197,7 +198,9 @@ class SegmapManager:
 
     @staticmethod
     def build_segmentation_maps_on_device(image_size, markups, scale=1, for_drawing=False, device=None, strict_markup=False):
-        """Batch form of ``build_segmentation_map`` on the MI355X (ubd_build_label_maps): ``markups`` is a list (one entry
+        """Batch form of ``build_segmentation_map`` on the MI355X (ubd_build_label_maps; ubd_build_label_maps_polygons when an
+        object is not a quad but a polygon of 5..64 vertices, markup read from segmentation maps; a triangle raises ValueError as
+        it did before polygons were accepted): ``markups`` is a list (one entry
         per image) of lists of ObjectMarkup / ClassifiedObjectMarkup, ``image_size`` = (width, height) like ``PIL.Image.size``.
         Returns an int32 device tensor (N, height/scale, width/scale) -- the y_true layout of the loss / train step.
         Degenerate quads whose OPPOSITE corners coincide on the map (a point or a folded segment -- a labelling error) are drawn
@@ -214,7 +217,17 @@ class SegmapManager:
         # float64 markup, as it reaches the reference's `object_markup.bbox / scale` (segmap_manager.py:96): rescaled or
         # augmented quads are fractional, and _proper_round floors / ceils the QUOTIENT -- truncating the markup first
         # would move a corner by a whole map pixel (12.3 / 4 ceils to 4, 12 / 4 to 3)
-        quads = np.zeros((n, cap, 8), np.float64)
+        sizes = [[np.asarray(obj.bbox).size for obj in objs] for objs in markups]
+        for i, row in enumerate(sizes):
+            for j, size in enumerate(row):
+                # three points stay refused here, as they always were (tests/test_gpu_raster.py pins it); the device call draws them
+                if size % 2 or not 8 <= size <= 2 * _lib.UBD_POLY_MAX_VERTS:
+                    raise ValueError(f"object markup must be a quadrilateral (8 numbers) or a polygon of 5..{_lib.UBD_POLY_MAX_VERTS} "
+                                     f"vertices, got {size} numbers (image {i}, object {j})")
+        max_verts = max([4] + [size // 2 for row in sizes for size in row])
+        polygons = any(size != 8 for row in sizes for size in row)      # a batch of quads only still takes ubd_build_label_maps
+        verts = np.zeros((n, cap, max_verts * 2), np.float64)
+        nverts = np.zeros((n, cap), np.int32)
         values = np.zeros((n, cap), np.int32)
         counts = np.zeros((n,), np.int32)
         for i, objs in enumerate(markups):
@@ -224,21 +237,28 @@ class SegmapManager:
                 if value > 255:
                     raise AssertionError("No more than 255 classes are supported")
                 bbox = np.asarray(obj.bbox, dtype=np.float64).reshape(-1)
-                if bbox.size != 8:
-                    raise ValueError(f"object markup must be a quadrilateral (8 numbers), got {bbox.size} (image {i}, object {j})")
-                quads[i, j] = bbox
+                verts[i, j, :bbox.size] = bbox
+                nverts[i, j] = bbox.size // 2
                 values[i, j] = value
-        SegmapManager._check_folded_quads(quads, counts, scale, strict_markup)
-        qd, vd, cd = (torch.from_numpy(a).to(device) for a in (quads, values, counts))
+        quads = np.ascontiguousarray(verts[:, :, :8])
+        SegmapManager._check_folded_quads(quads, counts, scale, strict_markup, nverts == 4)
         labels = torch.empty((n, height // scale, width // scale), dtype=torch.int32, device=device)
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if not polygons:
+            qd, vd, cd = (torch.from_numpy(a).to(device) for a in (quads, values, counts))
+            with torch.cuda.device(device):
+                _lib.check(lib.ubd_build_label_maps(qd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, height // scale, width // scale,
+                                                    int(scale), labels.data_ptr(), stream), "ubd_build_label_maps")
+            return labels
+        pd, nd, vd, cd = (torch.from_numpy(a).to(device) for a in (verts, nverts, values, counts))
         with torch.cuda.device(device):
-            _lib.check(lib.ubd_build_label_maps(qd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, height // scale, width // scale,
-                                                int(scale), labels.data_ptr(), stream), "ubd_build_label_maps")
+            _lib.check(lib.ubd_build_label_maps_polygons(pd.data_ptr(), nd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, max_verts,
+                                                         height // scale, width // scale, int(scale), labels.data_ptr(), stream),
+                       "ubd_build_label_maps_polygons")
         return labels
 
     @staticmethod
-    def _check_folded_quads(quads, counts, scale, strict=False):
+    def _check_folded_quads(quads, counts, scale, strict=False, is_quad=None):
         """The device fill rule is Pillow's for every quadrilateral except a zero-area fold whose OPPOSITE corners coincide
         after snapping (four edges in one point: Pillow's corner joining there depends on its internal edge order and is not
         restated, oracle/label_raster.py).  The reference draws whatever ``ImageDraw.polygon`` draws for such markup
@@ -251,6 +271,8 @@ class SegmapManager:
         snapped = np.where(n_larger > 1, np.floor(pts), np.ceil(pts))
         folded = ((snapped[:, :, 0] == snapped[:, :, 2]).all(-1) | (snapped[:, :, 1] == snapped[:, :, 3]).all(-1))
         folded &= np.arange(quads.shape[1])[None, :] < np.asarray(counts)[:, None]
+        if is_quad is not None:                              # polygon markup in the batch: the rule concerns its quads only
+            folded &= is_quad
         if folded.any():
             i, j = np.argwhere(folded)[0]
             msg = (f"{int(folded.sum())} object(s) whose opposite corners coincide on the label map, first: object {j} of image {i} "
@@ -372,6 +394,12 @@ class SegmapManager:
             raise ValueError("one plan per image is required")
         if not len(images):
             raise ValueError("no images")
+        if augment or plans is not None:                       # the augmentation moves quads; polygon markup is out of scope
+            for i, m in enumerate(markups):
+                for j, obj in enumerate(m or []):
+                    if np.asarray(obj.bbox).size != 8:
+                        raise ValueError(f"augmentation of polygon markup is not supported: object {j} of image {i} has "
+                                         f"{np.asarray(obj.bbox).size // 2} vertices (use augment=False)")
         device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         srcs = [_image_source(im, device) for im in images]
         if any(s.shape[2] == 3 for s in srcs):                 # a grey source among RGB ones: convert('RGB') replicates it
@@ -400,7 +428,8 @@ class SegmapManager:
     def _proper_round(markup_bbox):
         """Outward snapping of a quad's corners (behaviour of segmap_manager.py:106-133): a coordinate is floored
         when at least two of the four coordinates on the same axis are strictly larger (the object extends to
-        the larger side), otherwise it is ceiled; anything that is not 4 points is truncated to int32."""
+        the larger side), otherwise it is ceiled; anything that is not 4 points (a hull read from a segmentation map) is
+        truncated to int32, as the reference does (segmap_manager.py:114-116)."""
         pts = np.asarray(markup_bbox, dtype=np.float64)
         if pts.size != 8:
             return np.asarray(markup_bbox).astype(np.int32)
