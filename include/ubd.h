@@ -151,6 +151,26 @@ int ubd_train_step(ubd_handle *h, const float *params, const void *images, int i
 int ubd_adam_step(float *params, const float *grads, float *m, float *v, size_t count,
                   int t, float lr, float beta1, float beta2, float eps, float grad_scale, void *stream);
 
+/* --- epoch logs (train.py:176-188: what Keras' BaseLogger keeps while fit_generator runs, and evaluate_generator for val_) ---
+ * Adds one step's loss vector to the size-weighted sums of an epoch, on the device, so that the loop reads them ONCE per epoch
+ * instead of reading the loss after every step.
+ *   loss     : device fp32 [UBD_LOSS_FLOATS], as ubd_loss / ubd_train_step just wrote it on the same stream
+ *   n_images : the step's batch size (>= 1)
+ *   acc      : device, ubd_epoch_accumulator_bytes() bytes = (2 + UBD_EPOCH_VALUES) doubles, zeroed by the caller at the start
+ *              of an epoch:  acc[0] += n_images (Keras' `seen`);  acc[1] += 1 when the total loss is not finite;
+ *              acc[2 + i] += value_i * n_images for, in this order: loss, detection_pixel_acc, detection_pixel_precision,
+ *              detection_pixel_recall, detection_pixel_f1, classification_pixel_acc, positive_loss, negative_loss,
+ *              hard_negative_loss, detection_loss, classification_loss.
+ * The values are those of keras_metrics.py:110-191 formed in double from the fp32 entries: tp / max(1, tp + fp),
+ * ((2 p) r) / (p + r) or 0 when p + r == 0, cls_ok / max(1, n_pos), (tp + tn) / max(1, n_pixels); product and sum are rounded
+ * separately.  All eleven are always added (the host takes the ones its mode reports); a value that is not finite goes into its
+ * sum as it would in BaseLogger.  An epoch's log is acc[2 + i] / acc[0]: the mean of the per-batch values, not a pooled metric.
+ * One launch of one wave, no atomics (launches on one stream are ordered); no handle, no host synchronisation, no allocation,
+ * capturable in a HIP graph. */
+#define UBD_EPOCH_VALUES 11
+size_t ubd_epoch_accumulator_bytes(void);
+int ubd_epoch_accumulate(const float *loss, int n_images, double *acc, void *stream);
+
 /* --- training labels --------------------------------------------------------
  * Replaces SegmapManager.build_segmentation_map (segmap_manager.py:81-104) + _proper_round (:106-133) for a whole batch:
  * every object quad (8 float64 x1,y1..x4,y4 in IMAGE pixels; fractional after _rescale_image_and_markup / augmentation) is

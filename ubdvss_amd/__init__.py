@@ -12,7 +12,9 @@ from .model_runner import ModelRunner  # noqa: F401
 from .segmap_manager import SegmapManager  # noqa: F401
 from .augmentation import SegLinksImageAugmentation, AugmentationPlan, Stage, sample_plan, sample_photometric, apply_plan_to_markup  # noqa: F401
 from . import losses  # noqa: F401
-from .trainer import Trainer, Adam  # noqa: F401
+from .trainer import Trainer, Adam, History  # noqa: F401
+from .data_generators import BatchGenerator, MetaInfo  # noqa: F401
+from . import keras_callbacks  # noqa: F401
 from .visualizations import Visualizer  # noqa: F401
 from .evaluation import ImageResultCategories  # noqa: F401
 from .result_saver import ResultSaver  # noqa: F401

@@ -25,6 +25,8 @@ UBD_EVAL_MAX_VERTS, UBD_EVAL_MAX_GT, UBD_EVAL_MAX_FOUND, UBD_EVAL_MAX_THRESHOLDS
 UBD_EVAL_FLAG_OVERFLOW, UBD_EVAL_FLAG_BAD_GT = 1, 2
 UBD_POLY_MAX_VERTS = 64
 UBD_MAX_CLASSES = 31
+UBD_LOSS_FLOATS = 16
+UBD_EPOCH_VALUES = 11
 
 
 class UbdConfig(ctypes.Structure):
@@ -68,6 +70,8 @@ SIGNATURES = {
     "ubd_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_train_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _f, _f, _f, _f, _f, _vp]),
+    "ubd_epoch_accumulator_bytes": (_sz, []),
+    "ubd_epoch_accumulate": (_i, [_vp, _i, _vp, _vp]),
     "ubd_build_label_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_build_label_maps_polygons": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_segmap_polygons_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -14,7 +14,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats"
 pids=()
 for f in $UNITS; do
   [ -f $f.hip ] || continue
@@ -33,6 +33,8 @@ for f in $UNITS; do
   [ "$f" = "photometric" ] && extra="-ffp-contract=off"
   # exact fp64 cross products of the evaluation geometry (collinearity tests compare them with 0): no FMA contraction
   [ "$f" = "evaluate" ] && extra="-ffp-contract=off"
+  # epoch sums acc + value * n with product and sum rounded separately, bit-equal to the host restatement: no FMA contraction
+  [ "$f" = "epoch_stats" ] && extra="-ffp-contract=off"
   # no SLP packing of adjacent fp32 adds into v_pk_add_f32: beside MFMAs the packed form issues slower than two scalar adds
   [ "$f" = "wino" ] && extra="$extra -fno-slp-vectorize"
   [ "$f" = "wino6" ] && extra="$extra -fno-slp-vectorize"

@@ -53,6 +53,22 @@ def allreduce_gradients(flat_grads, group=None):
     return 1.0 / w
 
 
+def allreduce_epoch_sums(sums, group=None):
+    """SUM over the ranks of the epoch accumulators (fp64, the tensor of ``Trainer.fit``: seen, non-finite count and the eleven
+    weighted sums per row), once per epoch through torch.distributed -- also when the gradients go through the handle's own
+    communicator, which carries fp32 gradients only.  Every rank gets the same sums, hence the same logs, so the learning-rate
+    and best-checkpoint decisions taken from them cannot diverge.  Returns the reduced tensor (``sums`` itself, reduced in
+    place; a gloo group reduces a host copy of a device tensor and that copy is returned).  Not measured on hardware with
+    more than one GPU."""
+    if sums.dtype != torch.float64:
+        raise ValueError(f"epoch sums are float64, got {sums.dtype}")
+    if world_size(group) > 1:
+        if sums.is_cuda and dist.get_backend(group) != "nccl":
+            sums = sums.cpu()
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    return sums
+
+
 def broadcast_parameters(flat_params, src=0, group=None):
     if world_size(group) > 1:
         dist.broadcast(flat_params, src=src, group=group)

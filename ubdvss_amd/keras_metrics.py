@@ -38,3 +38,25 @@ def get_all_metrics(classification_mode=False):
     if classification_mode:
         names += ["detection_loss", "classification_loss"]
     return names
+
+
+# the order of the device accumulator's value slots (include/ubd.h, ubd_epoch_accumulate): acc[2 + i] is the sum of EPOCH_VALUES[i]
+EPOCH_VALUES = ["loss", "detection_pixel_acc", "detection_pixel_precision", "detection_pixel_recall", "detection_pixel_f1",
+                "classification_pixel_acc", "positive_loss", "negative_loss", "hard_negative_loss", "detection_loss",
+                "classification_loss"]
+
+
+def epoch_logs_from_sums(acc_host, classification_mode=False, prefix=""):
+    """One epoch's logs from the host copy of a ``ubd_epoch_accumulate`` accumulator: ``{prefix + name: sum / seen}`` for ``loss``
+    and the names of ``get_all_metrics(classification_mode)``, in that order.  This is Keras 2.2's size-weighted mean of the
+    per-batch values -- what ``BaseLogger`` reports for training and ``evaluate_generator`` for ``val_`` -- so the f1 of an epoch
+    is the mean of the batches' f1, not the f1 of pooled counters.  ``seen == 0`` (no step was accumulated) raises ValueError:
+    there is no mean to report."""
+    acc = [float(x) for x in acc_host]
+    if len(acc) != 2 + len(EPOCH_VALUES):
+        raise ValueError(f"expected {2 + len(EPOCH_VALUES)} accumulator slots, got {len(acc)}")
+    seen = acc[0]
+    if seen == 0:
+        raise ValueError("epoch_logs_from_sums: the accumulator has seen no image")
+    sums = dict(zip(EPOCH_VALUES, acc[2:]))
+    return {prefix + name: sums[name] / seen for name in ["loss"] + get_all_metrics(classification_mode)}

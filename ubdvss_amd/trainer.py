@@ -6,14 +6,31 @@ Multi-GPU: one process per GPU; when ``torch.distributed`` is initialised the fl
 vector (33 028 floats for the RGB model) is summed with ONE all-reduce over RCCL/xGMI and divided
 by the world size inside the fused Adam kernel.  The loss (incl. its batch-global top-k) is
 evaluated per replica (option 1).
+
+``Trainer.fit`` / ``Trainer.evaluate`` are the loop itself (``fit_generator`` / ``evaluate_generator`` as train.py:176-188 uses
+them): every step adds its loss vector to a device accumulator (``ubd_epoch_accumulate``) and the host reads the two
+accumulators -- training and validation -- ONCE per epoch; nothing inside an epoch waits for the device.
 """
 import ctypes
+import logging
 
 import numpy as np
 import torch
 
-from . import _lib, distributed
+from . import _lib, distributed, keras_metrics
 from .net import PreprocessingType
+
+
+class History:
+    """keras.callbacks.History: ``epoch`` numbers and ``history[name]`` = the value of every epoch's log."""
+
+    def __init__(self):
+        self.epoch, self.history = [], {}
+
+    def on_epoch_end(self, epoch, logs):
+        self.epoch.append(epoch)
+        for k, v in logs.items():
+            self.history.setdefault(k, []).append(v)
 
 
 class Adam:
@@ -37,6 +54,11 @@ class Trainer:
         self.iterations = 0
         self._ws = None
         self._pg = process_group
+        # epoch logs: row 0 the training sums, row 1 the validation sums (include/ubd.h, ubd_epoch_accumulate); one tensor, one read
+        self._epoch_slots = int(self._lib.ubd_epoch_accumulator_bytes()) // 8
+        self._epoch_acc = torch.zeros((2, self._epoch_slots), dtype=torch.float64, device=dev)
+        self._val_loss = torch.zeros(_lib.UBD_LOSS_FLOATS, dtype=torch.float32, device=dev)
+        self._loss_ws = None
 
     def broadcast_weights(self, src=0):
         if getattr(self.model, "_native_comm", None):           # the handle's own RCCL communicator (ubd_broadcast_params)
@@ -110,3 +132,104 @@ class Trainer:
         xt = torch.from_numpy(np.ascontiguousarray(x)).to(dev)     # uint8 stays uint8: NetConfig preprocessing fused on device
         yt = torch.from_numpy(np.ascontiguousarray(np.asarray(targets)).astype(np.int32)).to(dev)
         return float(self.train_step_on_device(xt, yt)[0].item())
+
+    # ---------------------------------------------------------------- the loop (train.py:176-188)
+    def _batch_on_device(self, images, targets):
+        """One generator batch, numpy or tensors, on the model's device: uint8 images stay raw pixels (NetConfig's preprocessing
+        is fused into the first layer), anything else is fed as float32 -- the rule of every other entry point."""
+        dev = self.model.device
+        if not torch.is_tensor(images):
+            x = np.asarray(images)
+            if x.dtype != np.uint8:
+                x = x.astype(np.float32, copy=False)
+            images = torch.from_numpy(np.ascontiguousarray(x))
+        elif images.dtype != torch.uint8:
+            images = images.to(torch.float32)
+        if not torch.is_tensor(targets):
+            targets = torch.from_numpy(np.ascontiguousarray(np.asarray(targets)).astype(np.int32))
+        return images.to(dev, non_blocking=True), targets.to(device=dev, dtype=torch.int32, non_blocking=True)
+
+    def _accumulate(self, loss, n_images, row):
+        with torch.cuda.device(self.model.device):
+            _lib.check(self._lib.ubd_epoch_accumulate(loss.data_ptr(), int(n_images), self._epoch_acc[row].data_ptr(),
+                                                      self.model._stream()), "ubd_epoch_accumulate")
+
+    def test_step_on_device(self, images, targets):
+        """Keras' test-mode step: the inference forward pass and the loss without its gradient.  Leaves the 16 floats in the
+        returned device vector (valid until the next call); no gradient, no Adam."""
+        mdl = self.model
+        logits = mdl.predict_on_device(images)
+        n, mh, mw, _ = logits.shape
+        targets = targets.reshape(n, mh, mw).to(torch.int32).contiguous()
+        nbytes = int(self._lib.ubd_loss_workspace_bytes(mdl._h, n, mh, mw))
+        if self._loss_ws is None or self._loss_ws.numel() < nbytes:
+            self._loss_ws = torch.empty(nbytes, dtype=torch.uint8, device=mdl.device)
+        with torch.cuda.device(mdl.device):
+            _lib.check(self._lib.ubd_loss(mdl._h, logits.data_ptr(), targets.data_ptr(), n, mh, mw, self._val_loss.data_ptr(), None,
+                                          self._loss_ws.data_ptr(), self._loss_ws.numel(), mdl._stream()), "ubd_loss")
+        return self._val_loss
+
+    def _run_steps(self, generator, steps, row, train):
+        for _ in range(int(steps)):
+            batch = next(generator)
+            x, y = self._batch_on_device(batch[0], batch[1])
+            loss = self.train_step_on_device(x, y) if train else self.test_step_on_device(x, y)
+            self._accumulate(loss, x.shape[0], row)
+
+    def _read_epoch_sums(self, rows=slice(0, 2)):
+        """THE device-to-host read of an epoch: the accumulator rows asked for in one transfer, summed over the ranks first."""
+        acc = self._epoch_acc[rows]
+        if self._pg is not False and distributed.world_size(self._pg) > 1:     # also with a native communicator: it carries fp32 gradients only
+            acc = distributed.allreduce_epoch_sums(acc, group=self._pg)
+        return acc.cpu().numpy()
+
+    def _is_chief(self):
+        return self._pg is False or distributed.rank(self._pg) == 0
+
+    def evaluate(self, generator, steps):
+        """keras ``evaluate_generator``: ``steps`` batches of ``(images, targets)`` through the test-mode step; returns
+        {name: size-weighted mean of the per-batch values} for ``loss`` and ``get_all_metrics`` (no prefix).  One read."""
+        generator = iter(generator)
+        self._epoch_acc[1].zero_()
+        self._run_steps(generator, steps, 1, train=False)
+        sums = self._read_epoch_sums(slice(1, 2))                   # the validation row alone
+        return keras_metrics.epoch_logs_from_sums(sums[0], self.model.n_classes > 0)
+
+    def fit(self, generator, steps_per_epoch, epochs, validation_data=None, validation_steps=None, callbacks=(), initial_epoch=0):
+        """keras ``fit_generator`` as train.py:176-188 calls it.  ``generator`` / ``validation_data``: endless iterators of
+        ``(images, targets)`` batches (numpy or device tensors; uint8 or float images), never restarted between epochs.  Per epoch:
+        ``steps_per_epoch`` train steps, then ``validation_steps`` test-mode steps with the parameters the epoch ended with, then
+        one read of the two device accumulators, then ``callback.on_epoch_end(epoch, logs)`` with the training means, the
+        ``val_`` means and ``lr`` (a callback may change ``self.opt.lr``: the next ``ubd_adam_step`` takes it).  Within an
+        epoch nothing reads the device or synchronises with it.  Returns a ``History``."""
+        if validation_data is not None and not validation_steps:
+            raise ValueError("validation_data needs validation_steps: the generators are endless")
+        generator = iter(generator)
+        validation_data = iter(validation_data) if validation_data is not None else None
+        cls_mode = self.model.n_classes > 0
+        history = History()
+        callbacks = list(callbacks)
+
+        def notify(method, *args):                               # every callback method is optional: a callback has the ones it needs
+            for cb in callbacks:
+                if hasattr(cb, method):
+                    getattr(cb, method)(*args)
+
+        notify("set_trainer", self)
+        notify("on_train_begin")
+        for epoch in range(int(initial_epoch), int(epochs)):
+            self._epoch_acc.zero_()                              # on the stream, ahead of the epoch's first accumulate
+            self._run_steps(generator, steps_per_epoch, 0, train=True)
+            if validation_data is not None:
+                self._run_steps(validation_data, validation_steps, 1, train=False)
+            sums = self._read_epoch_sums()
+            logs = keras_metrics.epoch_logs_from_sums(sums[0], cls_mode)
+            if validation_data is not None:
+                logs.update(keras_metrics.epoch_logs_from_sums(sums[1], cls_mode, prefix="val_"))
+            for row, what in ((0, "training"), (1, "validation")):
+                if sums[row][1] != 0:
+                    logging.warning("epoch %d: the total loss of %d %s step(s) was not finite", epoch + 1, int(sums[row][1]), what)
+            logs["lr"] = float(self.opt.lr)
+            notify("on_epoch_end", epoch, logs)
+            history.on_epoch_end(epoch, dict(logs))
+        return history
