@@ -28,6 +28,10 @@ pytestmark = pytest.mark.gpu
 # why the same-rounding oracle is no closer than the fp64 one at the large shapes; gates = 2-3 x the observed maxima.
 GATE_SAME_ROUNDING = {"bfloat16": 2e-2, "float16": 4e-3}        # vs the oracle with the same storage roundings
 GATE_FP64 = {"bfloat16": 2.5e-2, "float16": 5e-3}               # vs the plain fp64 oracle (round 1: 8e-2 / 2e-2)
+# Train step (_train_step_16bit_case): relative L2 per gradient tensor (and relative loss) against the same-rounding oracle evaluated in
+# fp64, and -- on shapes other than the fixed ones, which keep 5e-3 -- against the same oracle evaluated in fp32 like the kernels
+TRAIN16_GATE_FP64 = {"bfloat16": 4e-2, "float16": 3e-2}
+TRAIN16_GATE_FP32_SOAK = 2e-2
 
 
 def measure(dtype, cin, ncls, fml, n, hh, ww, seed, thr=0.0):
@@ -116,7 +120,7 @@ def test_bf16_full_batch_property_and_postprocess():
     assert out[4].shape == (4,)
 
 
-@pytest.mark.parametrize("dtype,tol64", [("bfloat16", 4e-2), ("float16", 3e-2)])
+@pytest.mark.parametrize("dtype,tol64", list(TRAIN16_GATE_FP64.items()))
 @pytest.mark.parametrize("cin,ncls,fml,n,hh,ww", [(3, 0, True, 2, 64, 64), (1, 2, True, 2, 64, 96), (3, 2, False, 1, 128, 64),
                                                    (3, 0, True, 3, 72, 104)])
 def test_train_step_16bit(dtype, tol64, cin, ncls, fml, n, hh, ww):
@@ -151,9 +155,9 @@ def test_train_step_bf16_random_shape_soak_with_every_negative_mined():
         mh, mw = hh // 4, ww // 4
         ncls = 2 if case % 3 == 2 else 0                            # every third case with classes (labels 1..2 in vertical bands)
         labels = soak_labels.mostly_positive_maps(rng, n, mh, mw, ncls)
-        for dtype, tol in (("bfloat16", 4e-2), ("float16", 3e-2)):
+        for dtype, tol in TRAIN16_GATE_FP64.items():
             try:
-                _train_step_16bit_case(dtype, tol, cin, ncls, fml, n, hh, ww, labels=labels, seed=500 + case, tol32=2e-2, u8=(case % 4 == 1))
+                _train_step_16bit_case(dtype, tol, cin, ncls, fml, n, hh, ww, labels=labels, seed=500 + case, tol32=TRAIN16_GATE_FP32_SOAK, u8=(case % 4 == 1))
             except AssertionError as e:
                 raise AssertionError(f"case {case} {dtype}: cin {cin} classes {ncls} fml {fml} {n} x {hh} x {ww}: {e}")
 
