@@ -124,6 +124,64 @@ int ubd_forward_postprocess(ubd_handle *h, const float *params, const void *imag
                             float min_area, int32_t *binary_map, int32_t *quads, int32_t *classes, int32_t *counts, int cap,
                             void *pp_workspace, size_t pp_workspace_bytes, void *stream);
 
+/* --- multi-scale inference (net.py:44-59 _create_multiscale_input / UpSampling2D branch, net.py:368-389 _build_multiscale_model) ---
+ * The reference's multi-scale model runs the base net on the batch at full, 1/2, ..., 1/2^P size (P = max_scale_power, 3 at
+ * net.py:368), brings every result back to the full map size with UpSampling2D(2^s) (nearest: y[i >> s, j >> s]) and takes the mean.
+ * Size rule: height and width must be multiples of 4 * 2^P, otherwise the maps of the levels cannot be combined (the reference's
+ * graph fails at its concatenation); every entry point below refuses other sizes and names the multiple.
+ * Pyramid: the reference resizes with tf.image.resize_images (TF1's legacy bilinear, align_corners = False).  Under the size rule
+ * in_size / out_size is exactly 2^s, every sample position is an integer and the interpolation weight is 0, so for finite inputs
+ * level s is exactly images[:, ::2^s, ::2^s, :] (tests/test_multiscale_host.py holds the general formula against the
+ * slice).  The slice commutes with the per-pixel preprocessing: uint8 pixels stay uint8 and each level's pass preprocesses them in
+ * its first layer.
+ * Mean: PER CHANNEL, out (n, height/4, width/4, 1 + n_classes).  The reference takes K.mean over the concatenation of all channels
+ * of all levels, which is this value for a detection-only net (one channel) and meaningless with classes: a stated deviation.
+ * Arithmetic, fixed so that it can be checked bit for bit: fp32, acc = y_0; acc += y_1[...]; ...; acc += y_P[...] in level order,
+ * then acc / (float)(P + 1) as one IEEE division.  Parity with the reduction order of TF's K.mean is unpinned.
+ * Inference only.
+ *
+ * Packed levels: levels first..P of an (n, height, width) array of pixel_bytes-byte pixels, level s being (n, height >> s,
+ * width >> s), lie one after another without padding.  ubd_multiscale_levels_bytes is their total size (0 unless n, height, width,
+ * pixel_bytes >= 1, first_level >= 0, max_scale_power 0..4 and both sides multiples of 2^max_scale_power); level s starts
+ * ubd_multiscale_levels_bytes(..., first_level, s - 1) bytes into the buffer. */
+size_t ubd_multiscale_levels_bytes(int n, int height, int width, int pixel_bytes, int first_level, int max_scale_power);
+
+/* Layer-level entry points, in the spirit of ubd_dilated_layer.
+ * ubd_multiscale_gather: levels 1..max_scale_power (1..4) of a batch, packed into levels_out, in ONE launch.
+ *   images: NHWC (n, height, width, channels), channels 1 or 3, in_dtype UBD_IN_U8 or UBD_IN_F32 (copied bit for bit)
+ *   levels_out: levels_bytes >= ubd_multiscale_levels_bytes(n, height, width, channels * (1 or 4), 1, max_scale_power)
+ * Every even source row is read once, with 16-byte loads (8-byte for uint8 rows whose width is 8 mod 16), and feeds every level it
+ * belongs to; odd rows are not read; nothing outside the rows and the packed levels is touched.  images and levels_out must be
+ * 16-byte aligned, n * height / 2 < 2^31.
+ * ubd_multiscale_fuse: the mean above.
+ *   level_logits: fp32, levels 0..max_scale_power (0..4) of (n, map_h, map_w, k) packed, level 0 first; map_h and map_w multiples of
+ *                 2^max_scale_power, k 1..UBD_MAX_CLASSES + 1
+ *   out: fp32 (n, map_h, map_w, k); may be level 0 itself (level_logits), must not overlap anything else
+ * Level 0 is read once (16-byte accesses where the addresses and map_w * k allow, else 8 or 4); the coarser levels come from cache.
+ * Both: every violation returns non-zero with ubd_last_error() set and launches nothing; one launch, no handle, no host
+ * synchronisation, no allocation, capturable in a HIP graph. */
+int ubd_multiscale_gather(const void *images, int in_dtype, int n, int height, int width, int channels, int max_scale_power,
+                          void *levels_out, size_t levels_bytes, void *stream);
+int ubd_multiscale_fuse(const float *level_logits, int n, int map_h, int map_w, int k, int max_scale_power, float *out, void *stream);
+
+/* Replaces keras Model.predict of the model _build_multiscale_model returns (net.py:368-389).  Arguments as ubd_forward, plus
+ * max_scale_power 0..4.  Enqueues on `stream`, in this order and with nothing between them that waits, allocates or reads on the
+ * host: the gather; ubd_forward of level 0 into `logits` (it packs the weights once, unless UBD_IN_PREPACKED is OR-ed into in_dtype
+ * under ubd_forward's rule); ubd_forward of levels 1..P, which reuse the packed fragments at the head of the same workspace; the
+ * fuse, in place on `logits`.  Each level's pass is the existing path for its shape and dtype (UBD_F32 / UBD_BF16 / UBD_F16
+ * handles alike), so `logits` equal ubd_multiscale_fuse of ubd_forward's outputs on the slices bit for bit.  One stream, a strictly
+ * linear chain: capturable in a HIP graph.  max_scale_power == 0 IS ubd_forward: the same launches, the same bytes, and
+ * ubd_forward_multiscale_workspace_bytes == ubd_forward_workspace_bytes.
+ * Workspace: ubd_forward_multiscale_workspace_bytes (0 for arguments this call refuses): the forward workspace, then the packed
+ * image levels (which is why it depends on in_dtype), then the packed logits of levels 1..P.
+ * Refused (non-zero return, ubd_last_error names the required multiple): max_scale_power outside 0..4, a side that is not a
+ * multiple of 4 * 2^max_scale_power, a workspace that is too small; with max_scale_power >= 1 also images that are not 16-byte
+ * aligned. */
+size_t ubd_forward_multiscale_workspace_bytes(const ubd_handle *h, int in_dtype, int n, int height, int width, int max_scale_power);
+int ubd_forward_multiscale(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
+                           int n, int height, int width, int max_scale_power, float *logits,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* --- training ------------------------------------------------------------ */
 /* Replaces the loss callable losses.get_loss(classification_mode)(y_true, y_pred)
  * (losses.py:20-24, :33-126) together with its autodiff gradient.

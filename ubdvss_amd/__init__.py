@@ -7,7 +7,7 @@ and ``torch.distributed``.  There is no CPU fallback: importing the kernels with
 library, or creating a model without an MI355X, raises.
 """
 from .data_markup import ObjectMarkup, ClassifiedObjectMarkup  # noqa: F401
-from .net import NetConfig, NetManager, PreprocessingType, Model  # noqa: F401
+from .net import NetConfig, NetManager, PreprocessingType, Model, MultiscaleModel  # noqa: F401
 from .model_runner import ModelRunner  # noqa: F401
 from .segmap_manager import SegmapManager  # noqa: F401
 from .augmentation import SegLinksImageAugmentation, AugmentationPlan, Stage, sample_plan, sample_photometric, apply_plan_to_markup  # noqa: F401

@@ -64,6 +64,11 @@ SIGNATURES = {
     "ubd_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ubd_forward_postprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz,
                                      _vp, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "ubd_multiscale_levels_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "ubd_multiscale_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "ubd_multiscale_fuse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_forward_multiscale_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "ubd_forward_multiscale": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ubd_pack_weights": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ubd_dilated_layer": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "ubd_postprocess": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),

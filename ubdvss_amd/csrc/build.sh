@@ -14,7 +14,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale"
 pids=()
 for f in $UNITS; do
   [ -f $f.hip ] || continue
@@ -35,6 +35,8 @@ for f in $UNITS; do
   [ "$f" = "evaluate" ] && extra="-ffp-contract=off"
   # epoch sums acc + value * n with product and sum rounded separately, bit-equal to the host restatement: no FMA contraction
   [ "$f" = "epoch_stats" ] && extra="-ffp-contract=off"
+  # the multi-scale mean: fp32 adds in level order and one IEEE division, bit-equal to the numpy oracle: no FMA contraction
+  [ "$f" = "multiscale" ] && extra="-ffp-contract=off"
   # no SLP packing of adjacent fp32 adds into v_pk_add_f32: beside MFMAs the packed form issues slower than two scalar adds
   [ "$f" = "wino" ] && extra="$extra -fno-slp-vectorize"
   [ "$f" = "wino6" ] && extra="$extra -fno-slp-vectorize"

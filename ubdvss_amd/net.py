@@ -326,20 +326,16 @@ class Model:
             gf = self._graphed[key] = GraphedForward(self, (int(n), int(height), int(width), self.c_in), dtype)
         return gf
 
-    def predict_on_device(self, images, out=None, preprocessing=None, postprocess=None, _prepacked=False):
-        """images: torch tensor (N,H,W,C_in) on this device, float32 (fed as is) or uint8 (the
-        NetConfig preprocessing is fused into the first layer).  Returns fp32 logits (N,H/4,W/4,K).
-        postprocess: None, or the keyword arguments of ``postprocess_on_device`` for ANOTHER batch's logits (with
-        ``outputs`` preallocated): that postprocess is enqueued together with this forward pass
-        (ubd_forward_postprocess: inside the stem kernel's first blocks when the one-kernel stem runs)."""
+    def _input_form(self, images, preprocessing, side_multiple=4):
+        """checks a batch for the forward entry points -> (contiguous images, in_dtype, preprocessing code)"""
         if images.device != self.device:
             raise ValueError("images must live on the model's device")
         if images.dim() != 4 or images.shape[3] != self.c_in:
             raise ValueError(f"expected NHWC images with {self.c_in} channels, got {tuple(images.shape)}")
         images = images.contiguous()
         n, hh, ww, _ = images.shape
-        if hh % 4 or ww % 4:
-            raise ValueError("image height and width must be multiples of 4")
+        if hh % side_multiple or ww % side_multiple:
+            raise ValueError(f"image height and width must be multiples of {side_multiple}")
         if images.dtype == torch.uint8:
             in_dtype = _lib.UBD_IN_U8
             pre = self.net_config.get_preprocessing_type() if preprocessing is None else preprocessing
@@ -348,6 +344,16 @@ class Model:
             in_dtype, pre = _lib.UBD_IN_F32, _lib.UBD_PRE_NONE
         else:
             raise ValueError(f"unsupported image dtype {images.dtype}")
+        return images, in_dtype, pre
+
+    def predict_on_device(self, images, out=None, preprocessing=None, postprocess=None, _prepacked=False):
+        """images: torch tensor (N,H,W,C_in) on this device, float32 (fed as is) or uint8 (the
+        NetConfig preprocessing is fused into the first layer).  Returns fp32 logits (N,H/4,W/4,K).
+        postprocess: None, or the keyword arguments of ``postprocess_on_device`` for ANOTHER batch's logits (with
+        ``outputs`` preallocated): that postprocess is enqueued together with this forward pass
+        (ubd_forward_postprocess: inside the stem kernel's first blocks when the one-kernel stem runs)."""
+        images, in_dtype, pre = self._input_form(images, preprocessing)
+        n, hh, ww, _ = images.shape
         if out is None:
             out = torch.empty((n, hh // 4, ww // 4, self.k_out), dtype=torch.float32, device=self.device)
         nbytes = self._lib.ubd_forward_workspace_bytes(self._h, n, hh, ww)
@@ -474,6 +480,107 @@ class GraphedForward:
         return self.out
 
 
+class MultiscaleModel:
+    """The reference's multi-scale model (net.py:368-389, ``_build_multiscale_model``): the SAME dilated net on the batch at full,
+    1/2, ..., 1/2**max_scale_power size, every result brought back to the full map size by nearest upsampling, and their mean --
+    one ``ubd_forward_multiscale`` call.  Inference only.
+
+    Shares ``base_model``'s parameters and handle: weights, files, ``device``, ``c_in``, ``k_out``, ``n_classes``, ``net_config``,
+    ``dtype`` and the postprocess are the base model's (every attribute not defined here is looked up there), so an instance goes
+    wherever a ``Model`` goes at inference time (``ModelRunner``, the evaluation, the visualisations).
+
+    Image height and width must be multiples of ``4 * 2**max_scale_power`` (32 at the default 3).  The mean is taken PER CHANNEL:
+    with classes the reference's ``K.mean`` over the concatenated channels of all levels is not meaningful."""
+
+    MAX_SCALE_POWER = 4
+
+    def __init__(self, base_model, max_scale_power=3):
+        if isinstance(base_model, MultiscaleModel):
+            raise ValueError("base_model must be a plain Model")
+        if int(max_scale_power) != max_scale_power or not 0 <= max_scale_power <= self.MAX_SCALE_POWER:
+            raise ValueError(f"max_scale_power must be an integer in 0..{self.MAX_SCALE_POWER}, got {max_scale_power}")
+        self.base = base_model
+        self.max_scale_power = int(max_scale_power)
+        self.side_multiple = 4 << self.max_scale_power
+        self._ms_ws = None
+        self._ms_packed_key = None   # as Model._packed_key, for the fragments at the head of THIS model's workspace
+        self._graphed = {}
+
+    def __getattr__(self, name):     # only reached for names this class does not define
+        if name == "base":
+            raise AttributeError(name)
+        return getattr(self.base, name)
+
+    @property
+    def net_config(self):
+        return self.base.net_config
+
+    @net_config.setter
+    def net_config(self, value):
+        self.base.net_config = value
+
+    def invalidate_packed_weights(self):
+        self.base.invalidate_packed_weights()
+        self._ms_packed_key = None
+
+    def _weights_key(self):
+        b = self.base
+        return (self._ms_ws.data_ptr() if self._ms_ws is not None else None, b.params.data_ptr(), b.params._version, b._weights_epoch)
+
+    def graphed_forward(self, n, height, width, dtype=torch.float32):
+        """The whole chain of ONE fixed shape -- the gather, the ``max_scale_power + 1`` passes, the fuse: about 30 launches at
+        ``max_scale_power`` 3, one stream, no forked branch -- as a captured HIP graph (``GraphedForward``).  Cached per shape;
+        bit-identical to ``predict_on_device`` (the same launches)."""
+        key = (int(n), int(height), int(width), dtype)
+        gf = self._graphed.get(key)
+        if gf is None:
+            gf = self._graphed[key] = GraphedForward(self, (int(n), int(height), int(width), self.base.c_in), dtype)
+        return gf
+
+    def predict_on_device(self, images, out=None, preprocessing=None, postprocess=None, _prepacked=False):
+        """``Model.predict_on_device`` for the multi-scale mean: fp32 (N,H/4,W/4,K).  ``postprocess`` (another batch's job, see
+        ``Model.predict_on_device``) cannot ride in a stem kernel of this chain: it is enqueued as a call of its own right after
+        the chain, on the same stream, with identical results."""
+        b = self.base
+        try:
+            images, in_dtype, pre = b._input_form(images, preprocessing, self.side_multiple)
+        except ValueError as e:
+            if "multiples of" in str(e):
+                raise ValueError(f"{e} (4 * 2**max_scale_power, max_scale_power = {self.max_scale_power})") from None
+            raise
+        if images.data_ptr() % 16:                          # an offset view: the pyramid gather loads 16-byte pieces
+            images = images.clone()
+        n, hh, ww, _ = images.shape
+        if out is None:
+            out = torch.empty((n, hh // 4, ww // 4, b.k_out), dtype=torch.float32, device=b.device)
+        if postprocess is not None:
+            pl = postprocess["logits"]
+            if not pl.is_contiguous() or pl.dtype != torch.float32 or pl.shape[3] != b.k_out:
+                raise ValueError("postprocess job: logits must be a contiguous fp32 (N,h,w,K) tensor of this model")
+            if pl.data_ptr() == out.data_ptr():
+                raise ValueError("postprocess job: the logits being postprocessed must not be the buffer this call writes")
+        lib, power = b._lib, self.max_scale_power
+        nbytes = lib.ubd_forward_multiscale_workspace_bytes(b._h, in_dtype, n, hh, ww, power)
+        ws = self._ms_ws
+        if ws is None or ws.numel() < nbytes:
+            ws = self._ms_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=b.device)
+        stream = b._stream()
+        key = (ws.data_ptr(), b.params.data_ptr(), b.params._version, b._weights_epoch, stream.value)
+        if key == self._ms_packed_key or (_prepacked and self._ms_packed_key is not None and key[:4] == self._ms_packed_key[:4]):
+            in_dtype |= _lib.UBD_IN_PREPACKED
+        self._ms_packed_key = None
+        with torch.cuda.device(b.device):
+            _lib.check(lib.ubd_forward_multiscale(b._h, b.params.data_ptr(), images.data_ptr(), in_dtype, pre, n, hh, ww, power,
+                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ubd_forward_multiscale")
+        self._ms_packed_key = key
+        if postprocess is not None:
+            b.postprocess_on_device(postprocess["logits"], postprocess["logit_threshold"], postprocess["scale"], postprocess["min_area"],
+                                    cap=int(postprocess.get("cap", postprocess["outputs"][1].shape[1])), outputs=postprocess["outputs"])
+        return out
+
+    predict = Model.predict             # numpy in, numpy out: the same host code over this class's predict_on_device
+
+
 class NetManager:
     """Builds / saves / loads the model (net.py:255-494) with the reference's method names, arguments and FILES: models are
     written as Keras 2.2 HDF5 (``keras.Model.save`` layout, ubdvss_amd.keras_h5_writer -- the reference's ``load_model`` opens
@@ -497,6 +604,14 @@ class NetManager:
         self._model = Model(self._net_config, dtype=dtype, seed=seed)
         self._net_config._scale = 4                     # net.py:314
         return self._net_config
+
+    def build_multiscale_model(self, max_scale_power=3, dtype="float32", seed=None):
+        """net.py:368-389 (``_build_multiscale_model``): the dilated net, then a ``MultiscaleModel`` around it as the manager's
+        model.  ``save_model`` / ``save_inference`` write the BASE model's files -- a nested Keras graph in the ``.h5`` is out of
+        scope, so a saved multi-scale model is loaded with ``load_model`` and wrapped again."""
+        config = self.build_model(dtype=dtype, seed=seed)
+        self._model = MultiscaleModel(self._model, max_scale_power)
+        return config
 
     def get_keras_model(self):                          # name kept for drop-in use (net.py:415-416)
         return self._model
