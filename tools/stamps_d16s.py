@@ -1,14 +1,11 @@
-"""In-kernel phase timing of dilconv16s_kernel (diagnostic build, tools/build_diag.sh): s_memtime of every wave at the phase boundaries of
+"""In-kernel phase timing of dilconv16s_kernel (diagnostic build): s_memtime of every wave at the phase boundaries of
 its first 8 items; bf16 train step at batch 64 (TRAIN=1, default) or the cfg5 forward (8 x 1024 x 1024 fp16).  Usage: stamps_d16s.py [dilation ...]"""
-import ctypes, os, sys
+import os, sys
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", os.environ.get("DIAG_LIB", "libubd_hip_diag.so"))
+import _diag
 from ubdvss_amd import NetConfig, Model, Trainer, Adam, synthetic
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 if os.environ.get("TRAIN", "1") == "1":
     m = Model(NetConfig(grey=False), dtype="bfloat16", seed=1)
     tr = Trainer(m, Adam())
@@ -23,14 +20,9 @@ else:
     run = lambda: m.predict_on_device(x)
     what = "cfg5 fp16 forward, 8 x 256 x 256 maps"
 for _ in range(100): run()
-lib.ubd_debug_set_stamps_d16s.argtypes = [ctypes.c_void_p, ctypes.c_int]; lib.ubd_debug_set_stamps_d16s.restype = None
 names = ["wait for the tile (vmcnt)", "barrier", "decode + issue the next tile's 4 DMA pieces", "four rows: 28 reads, 56 MFMAs, epilogues, 8 stores"]
 for d in [int(a) for a in sys.argv[1:]] or [2, 4, 8]:
-    st = torch.zeros((768, 4, 8, 8), dtype=torch.int64, device="cuda")
-    lib.ubd_debug_set_stamps_d16s(st.data_ptr(), d)
-    run(); torch.cuda.synchronize()
-    lib.ubd_debug_set_stamps_d16s(None, 0)
-    s = st.cpu().numpy()
+    s = _diag.stamps(lib, "dilconv16s", (768, 4, 8, 8), run, sel=(d,))
     used = s[:, 0, 1, 0] > 0
     s = s[used]
     seg = np.diff(s[:, :, 1:5, :5], axis=-1)

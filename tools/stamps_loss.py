@@ -1,12 +1,10 @@
-"""In-kernel stamps of the one-launch loss (a -DLOSS1_STAMPS build: tools/build_variant.sh loss_stamps loss -DLOSS1_STAMPS): wall-clock stamps
-(100 MHz) of every block at the stage boundaries, read back from the (otherwise unused) ce buffer of the workspace.
-  UBD_LIB_PATH=tools/_ab/loss_stamps.so python tools/stamps_loss.py"""
-import ctypes, os, sys
+"""In-kernel stamps of the one-launch loss (diagnostic build): wall-clock stamps (100 MHz) of every block at the stage boundaries."""
+import ctypes
 import numpy as np, torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import _diag
 from ubdvss_amd import _lib, synthetic
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 n, h, w, k = 64, 128, 128, 1
 lab = torch.from_numpy(synthetic.rectangle_maps(30, n, h, w)).cuda().to(torch.int32)
 g = torch.Generator(device="cuda"); g.manual_seed(1)
@@ -20,12 +18,10 @@ st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 def call(): _lib.check(lib.ubd_loss(hd, logits.data_ptr(), lab.data_ptr(), n, h, w, loss.data_ptr(), grad.data_ptr(), ws.data_ptr(), ws.numel(), st), "loss")
 for _ in range(50): call()
 torch.cuda.synchronize()
-ce_off = nb - ((n * h * w * 4 + 255) // 256 * 256)
 names = ["start", "loads", "lds hist", "flush+records", "barrier 1 passed", "stage 1", "barrier 2 passed", "stage 2", "barrier 3 passed", "gradient", "end"]
 acc = []
 for rep in range(20):
-    call(); torch.cuda.synchronize()
-    s = ws[ce_off:ce_off + 256 * 16 * 8].view(torch.int64).cpu().numpy().reshape(256, 16).astype(np.float64)
+    s = _diag.stamps(lib, "loss", (256, 16), call).astype(np.float64)
     t0 = s[:, 0].min()
     acc.append((s - t0) / 100.0)       # us
 a = np.median(np.stack(acc), axis=0)

@@ -1,14 +1,11 @@
-"""In-kernel phase timing of sep123_16_kernel (diagnostic build, tools/build_diag.sh): s_memtime stamps of every wave at the phase
+"""In-kernel phase timing of sep123_16_kernel (diagnostic build): s_memtime stamps of every wave at the phase
 boundaries of its first 16 tiles, cfg5 shape (8 x 1024 x 1024 fp16) or the bf16 train step (TRAIN=1).  Prints median ticks (100 MHz) per segment."""
-import ctypes, os, sys
+import os
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", os.environ.get("DIAG_LIB", "libubd_hip_diag.so"))
+import _diag
 from ubdvss_amd import NetConfig, Model, Trainer, Adam, synthetic
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 train = os.environ.get("TRAIN") == "1"
 if train:
     m = Model(NetConfig(grey=False), dtype="bfloat16", seed=1)
@@ -22,13 +19,7 @@ else:
     x = torch.from_numpy(synthetic.noise_images(2, 8, 1024, 1024, 3)).cuda()
     run = lambda: m.predict_on_device(x)
 for _ in range(200): run()
-st = torch.zeros((768, 4, 16, 8), dtype=torch.int64, device="cuda")
-lib.ubd_debug_set_stamps_s123.argtypes = [ctypes.c_void_p]; lib.ubd_debug_set_stamps_s123.restype = None
-lib.ubd_debug_set_stamps_s123(st.data_ptr())
-for _ in range(3): run()
-torch.cuda.synchronize()
-lib.ubd_debug_set_stamps_s123(None)
-s = st.cpu().numpy().astype(np.int64)
+s = _diag.stamps(lib, "sep123_16", (768, 4, 16, 8), run, reps=3)
 names = ["wait img+barrier", "L1", "frag req+barrier", "frag wait", "dma issue(+a1 copy) L2", "L3 frag req+barrier", "a2 copy + L3"]
 names = ["wait img + barrier", "L1 units", "L2-frag request + barrier", "L2-frag wait", "dma issue, a1 copy, L2 units", "L3-frag request + barrier", "a2 copy, L3 unit"]
 seg = np.diff(s, axis=-1)                        # (blk, wave, it, 7)

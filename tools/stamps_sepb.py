@@ -1,28 +1,19 @@
 """In-kernel phase timing of sepb16_kernel (diagnostic build): s_memtime of every wave at the phase boundaries of its first
 8 tiles, bf16 train step at batch 64.  Usage: stamps_sepb.py [cin stride]  (24 1 = L2, 3 2 = L1, 24 2 = L3)"""
-import ctypes, os, sys
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", "libubd_hip_diag.so")
+import _diag
 from ubdvss_amd import NetConfig, Model, Trainer, Adam, synthetic
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 m = Model(NetConfig(grey=False), dtype="bfloat16", seed=1)
 tr = Trainer(m, Adam())
 lab = synthetic.rectangle_maps(30, 64, 128, 128)
 x = torch.from_numpy(synthetic.textured_images(31, lab, 4, 3).astype(np.float32) / 127.5 - 1.0).cuda()
 y = torch.from_numpy(lab).cuda()
 for _ in range(100): tr.train_step_on_device(x, y)
-lib.ubd_debug_set_stamps_sepb.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]; lib.ubd_debug_set_stamps_sepb.restype = None
 names = ["top barrier", "stage X / write xf32 / mask loads", "wait DMA + barrier + border fix", "phase 1 (G tile)", "barrier", "next tile: D DMA / x / mask loads", "phase 2a (dDW, depthwise, dpw)", "barrier", "phase 2b (ddw)"]
 for cin, stride in ((24, 1), (3, 2), (24, 2)):
-    st = torch.zeros((1024, 4, 8, 12), dtype=torch.int64, device="cuda")
-    lib.ubd_debug_set_stamps_sepb(st.data_ptr(), cin, stride)
-    tr.train_step_on_device(x, y); torch.cuda.synchronize()
-    lib.ubd_debug_set_stamps_sepb(None, 0, 0)
-    s = st.cpu().numpy()
+    s = _diag.stamps(lib, "sepb16", (1024, 4, 8, 12), lambda: tr.train_step_on_device(x, y), sel=(cin, stride))
     used = s[:, 0, 2, 0] > 0
     s = s[used]
     if not (s[0, 0, 2, 8] > 0): s[:, :, :, 7] = s[:, :, :, 9]; s[:, :, :, 8] = s[:, :, :, 9]   # 1/3-channel kernel: phase 2 in one piece

@@ -1,26 +1,17 @@
-"""In-kernel phase timing of stem123_kernel (diagnostic build, tools/build_diag.sh): s_memtime stamps of every wave at the
+"""In-kernel phase timing of stem123_kernel (diagnostic build): s_memtime stamps of every wave at the
 phase boundaries of its first 16 tiles.  Prints median cycles per segment."""
-import ctypes, os, sys
+import os
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", "libubd_hip_diag.so")
+import _diag
 from ubdvss_amd import NetConfig, Model, synthetic
 os.environ["UBD_STEM"] = "fused123"
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 m = Model(NetConfig(grey=False), seed=1)
 x = torch.from_numpy(synthetic.noise_images(2, 32, 512, 512, 3)).cuda()
 for _ in range(300): m.predict_on_device(x)
 nblk = 256
-st = torch.zeros((nblk, 8, 16, 8), dtype=torch.int64, device="cuda")
-lib.ubd_debug_set_stamps.argtypes = [ctypes.c_void_p]; lib.ubd_debug_set_stamps.restype = None
-lib.ubd_debug_set_stamps(st.data_ptr())
-for _ in range(5): m.predict_on_device(x)
-torch.cuda.synchronize()
-lib.ubd_debug_set_stamps(None)
-s = st.cpu().numpy().astype(np.int64)
+s = _diag.stamps(lib, "stem123", (nblk, 8, 16, 8), lambda: m.predict_on_device(x), reps=5)
 names = ["dma issue + carry", "A (L2)", "wait patch", "barrier", "B (L3, waves 0-3)", "0b (L1 next tile)", "barrier"]
 seg = np.diff(s[..., :8], axis=-1)              # (blk, wave, it, 7)
 its = slice(2, 14)

@@ -1,14 +1,11 @@
-"""Time line of the blocks of stem123_kernel with the postprocess of k earlier maps inside (diagnostic build, tools/build_diag.sh):
+"""Time line of the blocks of stem123_kernel with the postprocess of k earlier maps inside (diagnostic build):
 s_memrealtime (100 MHz, shared by all CUs) at kernel entry, after the postprocess job, at the start of every strip and at the end."""
-import ctypes, os, sys
+import os
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", "libubd_hip_diag.so")
+import _diag
 from ubdvss_amd import NetConfig, Model, synthetic
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 cfg = NetConfig(grey=False)
 m = Model(cfg, seed=1)
 nimg = int(os.environ.get("N", 32))
@@ -17,7 +14,6 @@ x = torch.from_numpy(synthetic.textured_images(4, labs, 4, 3).astype(np.float32)
 out = torch.empty((nimg, 128, 128, 1), device="cuda")
 prev = m.predict_on_device(x).clone()
 nblk = m.num_cus
-lib.ubd_debug_set_stamps.argtypes = [ctypes.c_void_p]; lib.ubd_debug_set_stamps.restype = None
 for k in (0, 1, 32):
     job = None
     if k:
@@ -25,12 +21,8 @@ for k in (0, 1, 32):
         outs = m.alloc_postprocess_outputs(k, 128, 128, 1024)
         job = {"logits": lg, "logit_threshold": 0.0, "scale": 4, "min_area": 5, "cap": 1024, "outputs": outs}
     for _ in range(100): m.predict_on_device(x, out=out, postprocess=job)
-    st = torch.zeros(nblk * 8 * 16 * 8 + nblk * 32, dtype=torch.int64, device="cuda")
-    lib.ubd_debug_set_stamps(st.data_ptr())
-    m.predict_on_device(x, out=out, postprocess=job)
-    torch.cuda.synchronize()
-    lib.ubd_debug_set_stamps(None)
-    b = st.cpu().numpy().astype(np.int64)[nblk * 8 * 16 * 8:].reshape(nblk, 32)
+    st = _diag.stamps(lib, "stem123", (nblk * 8 * 16 * 8 + nblk * 32,), lambda: m.predict_on_device(x, out=out, postprocess=job))
+    b = st[nblk * 8 * 16 * 8:].reshape(nblk, 32)         # the block time lines sit behind the tile stamps
     t0 = b[:, 0].min()
     us = lambda v: (v - t0) / 100.0
     nstr = (b[:, 4:28] > 0).sum(1)

@@ -1,14 +1,12 @@
 """In-kernel timing of dilconv_wino_kernel<0> (diagnostic build): per wave s_memtime at kernel entry, after the U copy +
 barrier, after each group, at exit.  Launch = one dilated layer on 32 x 128 x 128 x 24 (bench shape)."""
-import ctypes, os, sys
+import ctypes, os
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _diag
 from ubdvss_amd import _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_ab", "libubd_hip_diag.so")
 from ubdvss_amd import NetConfig, Model
 torch.cuda.set_device(0)
-lib = _lib.load()
+lib = _diag.load()
 m = Model(NetConfig(grey=False), seed=1)
 n, mh, mw = int(os.environ.get("N", 32)), 128, 128
 a = torch.rand((n, mh, mw, 24), device="cuda") - 0.3
@@ -19,14 +17,9 @@ _lib.check(lib.ubd_pack_weights(m._h, m.params.data_ptr(), ws.data_ptr(), ws.num
 def run(layer):
     _lib.check(lib.ubd_dilated_layer(m._h, m.params.data_ptr(), layer, a.data_ptr(), b.data_ptr(), n, mh, mw, ws.data_ptr(), stream), "dil")
 for _ in range(500): run(2)
-lib.ubd_debug_set_stamps_wino.argtypes = [ctypes.c_void_p]; lib.ubd_debug_set_stamps_wino.restype = None
 for layer in (0, 2, 4):
-    st = torch.zeros((768 * 4, 8), dtype=torch.int64, device="cuda")
     for _ in range(50): run(layer)
-    lib.ubd_debug_set_stamps_wino(st.data_ptr())
-    run(layer); torch.cuda.synchronize()
-    lib.ubd_debug_set_stamps_wino(None)
-    s = st.cpu().numpy().astype(np.int64)
+    s = _diag.stamps(lib, "wino", (768 * 4, 8), lambda: run(layer))
     s = s[s[:, 0] > 0]
     t0 = s[:, 0].min()
     end = s[:, 7]

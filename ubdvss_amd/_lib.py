@@ -3,7 +3,8 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# UBD_LIB_PATH: another build of the same library (diagnostic builds of tools/: stamps, the racy-flatten proof); never a fallback
+# UBD_LIB_PATH: another build of the same library (the variant builds of csrc/build.sh under tools/_ab/; the stamped diagnostic build is
+# loaded by tools/_diag.py, which sets LIB_PATH itself); never a fallback
 LIB_PATH = os.environ.get("UBD_LIB_PATH") or os.path.join(_HERE, "libubd_hip.so")
 
 UBD_F32, UBD_BF16, UBD_F16 = 0, 1, 2

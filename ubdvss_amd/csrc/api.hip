@@ -49,6 +49,29 @@ extern "C" int ubd_host_memcpy_mt(void *dst, const void *src, size_t n, int thre
 }
 extern "C" const char *ubd_build_id(void) { return UBD_BUILD_ID; }   // sha256 over the kernel sources at build time (build.sh); bench.py compares it with the committed profiles' fingerprint
 
+#ifdef UBD_STAMPS   // diagnostic build only (stamps.h): one stamp buffer per kernel family
+// selectors: dilconv16s (d), dil_wgrad16 (d): the dilation; sepb16, sep_bwd (cin, stride): the template variant; the other families have none (0, 0)
+static struct { const char *kernel; ubd_stamp_buf buf; int sel0, sel1; } g_stamps[] = {
+    {"stem23"}, {"stem123"}, {"wino"}, {"wino6"}, {"sep123_16"}, {"dilconv16s"}, {"sepb16"}, {"sep_bwd"}, {"dil_wgrad16"}, {"postprocess"}, {"loss"},
+};
+extern "C" int ubd_debug_set_stamps(const char *kernel, void *buf, size_t capacity_words, int sel0, int sel1)
+{
+    for (auto &e : g_stamps)
+        if (kernel && strcmp(kernel, e.kernel) == 0) {
+            e.buf = {(unsigned long long *)buf, buf ? capacity_words : 0};
+            e.sel0 = sel0; e.sel1 = sel1;
+            return 0;
+        }
+    UBD_REQUIRE(false, "ubd_debug_set_stamps: no kernel family named %s", kernel ? kernel : "(null)");
+}
+ubd_stamp_buf ubd_stamps_for(const char *kernel, int sel0, int sel1)
+{
+    for (const auto &e : g_stamps)
+        if (strcmp(kernel, e.kernel) == 0) return e.sel0 == sel0 && e.sel1 == sel1 ? e.buf : ubd_stamp_buf{nullptr, 0};
+    return {nullptr, 0};
+}
+#endif
+
 // The UBD_* environment switches, read once, when ubd_create builds the handle: NAME=value stores `set` in the int field at `field`; any
 // other value is ignored.  What each field selects is written at the field (common.h).
 static const char ANY[] = "", NUMBER[] = "#";      // in place of a value: set to anything / a positive integer, which is stored itself

@@ -20,12 +20,6 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const rp_batch B)
     rp_reduce_group(B.job[j], (int)blockIdx.x - B.job[j].block0, s);
 }
 
-#ifdef UBD_STAMPS   // diagnostic build only (bwd_common.h)
-unsigned long long *g_sepb_stamps = nullptr;
-int g_sepb_stamps_cin = 0, g_sepb_stamps_stride = 0;
-extern "C" void ubd_debug_set_stamps_sepb(void *p, int cin, int stride) { g_sepb_stamps = (unsigned long long *)p; g_sepb_stamps_cin = cin; g_sepb_stamps_stride = stride; }
-#endif
-
 // Host side of the batched reduction (bwd_common.h)
 void rp_init(rp_queue *q, float *base, size_t cap_floats) { q->b.njobs = 0; q->nblocks = 0; q->base = base; q->used = 0; q->cap = cap_floats; }
 rp_job rp_take_prev(rp_queue *q)

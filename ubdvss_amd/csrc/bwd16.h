@@ -187,17 +187,10 @@ template <typename T, int TW, bool DX, bool MSPLIT = (TW == 8), bool PAIR = fals
 #define W16_OCC(TW, DX) (((TW) == 8) ? 3 : 2)
 __global__ __launch_bounds__(256, W16_OCC(TW, DX)) void dil_wgrad16_kernel(const unsigned short *__restrict__ x, const unsigned short *__restrict__ gz,
                                                              float *__restrict__ partials, int n, int h, int w, int d,
-                                                             const u32x4 *__restrict__ wfrag_t, unsigned short *__restrict__ gout, const rp_job prev, const w16_geom geo
-#ifdef UBD_STAMPS
-                                                             , unsigned long long *__restrict__ stamps
-#endif
-                                                             )
+                                                             const u32x4 *__restrict__ wfrag_t, unsigned short *__restrict__ gout, const rp_job prev, const w16_geom geo UBD_STAMP_PARAM)
 {
-#ifdef UBD_STAMPS   // diagnostic build only: s_memtime of lane 0 of every wave at the phase boundaries of its first 8 items
-#define WGSTAMP(k) do { if (stamps && iter < 8 && (threadIdx.x & 63) == 0) stamps[(((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + iter) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WGSTAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 8 items of the block (tools/stamps_wgrad.py)
+#define WGSTAMP(k) UBD_STAMP(iter < 8, (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + iter) * 8 + (k))
     using C = w16_cfg<TW, DX, PAIR>;
     static_assert(!PAIR || !MSPLIT, "paired sub-grids: accumulators split by k-blocks");
     constexpr int TILES_BYTES = (!MSPLIT && 2 * C::BUF_BYTES < 28672) ? 28672 : 2 * C::BUF_BYTES;   // two tile buffers; the k-split block reduction needs 28 KiB

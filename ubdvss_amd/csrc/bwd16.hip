@@ -23,7 +23,7 @@ static int launch_sepb16(const ubd_handle *h, const void *x, int in_u8, const un
     float *partials = rp_add(rq, grid, C::PART, grads + h->off_sep_dw[s], 9 * CIN, grads + h->off_sep_pw[s], CIN * UBD_C, grads + h->off_sep_b[s], st);
     if (!partials) return -1;
     auto launch = [&](auto xb) {      // 0: fp32 input through registers, 1: uint8, 2: fp32 by LDS-DMA
-        hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, decltype(xb)::value, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev SB_STAMP_ARG);
+        hipLaunchKernelGGL((sepb16_kernel<CIN, STRIDE, decltype(xb)::value, GSRC, T>), dim3(grid), dim3(C::NT), 0, st, x, D, mbits, xbits, dDW, dw_own, pw_own, dw_up, partials, n, H, W, OH, OW, pad_lo, DH, DWd, pad_up, sub, div, prev UBD_STAMP_ARG("sepb16", CIN, STRIDE));
     };
     if constexpr (CIN != UBD_C) {
         if (xdma) { launch(int_c<2>()); return 0; }
@@ -42,7 +42,7 @@ static void launch_dil_wgrad16(int gw, const void *X, const unsigned short *G, f
         constexpr int TW = decltype(tw_c)::value;
         constexpr bool DX = decltype(dx_c)::value, PAIR = decltype(pair_c)::value;
         hipLaunchKernelGGL((dil_wgrad16_kernel<TX, TW, DX, TW == 8, PAIR>), dim3(gw), dim3(256), 0, st, (const unsigned short *)X, G, partials, n, H4, W4, dd,
-                           DX ? (const u32x4 *)wt : nullptr, DX ? g_out : nullptr, prev, w16_geometry<TW, PAIR>(n, H4, W4, dd) WG_STAMP_ARG);
+                           DX ? (const u32x4 *)wt : nullptr, DX ? g_out : nullptr, prev, w16_geometry<TW, PAIR>(n, H4, W4, dd) UBD_STAMP_ARG("dil_wgrad16", dd));
     };
     if (pair) launch(int_c<16>(), std::true_type(), std::true_type());
     else if (tw == 8 && fuse_dx) launch(int_c<8>(), std::true_type(), std::false_type());

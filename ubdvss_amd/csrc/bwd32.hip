@@ -292,20 +292,15 @@ template <int CIN, int STRIDE, int XB, int UPS = 0> struct sepb_cfg {          /
 //     G[p][c] = (A[p][c] > 0) * sum_t dDW_up[(p + up_pad - t) / UPS][c] * dw_up[t][c]        (taps in sep_dx_kernel's order: the same bits)
 // i.e. sep_dx_kernel's arithmetic on the tile, so that kernel's launch -- 403 MB read + 403 MB mask + 403 MB written per separable
 // layer at 64 images -- and the G tensor itself disappear.
-#ifdef UBD_STAMPS   // diagnostic build: s_memtime of every wave at the phase boundaries of its first 8 tiles (tools/stamps_sepb32.py)
-#define SB32_STAMP_PARAM , unsigned long long *stamps = nullptr
-#define SB32STAMP(k) do { if (stamps && stamp_it < 8 && (threadIdx.x & 63) == 0) stamps[(((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + stamp_it) * 12 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SB32_STAMP_PARAM
-#define SB32STAMP(k) do {} while (0)
-#endif
+// diagnostic build only (stamps.h): the phase boundaries, every wave, first 8 tiles of the block, 12 slots per tile (tools/stamps_sepb32.py)
+#define SB32STAMP(k) UBD_STAMP(stamp_it < 8, (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + stamp_it) * 12 + (k))
 template <int CIN, int STRIDE, int IN_U8, typename TX, typename TR, int UPS = 0>
 __global__ __launch_bounds__(256, (CIN != UBD_C && UPS > 0) ? 4 : 2) void sep_bwd_kernel(const void *__restrict__ xin, const float *__restrict__ G,
                                                       float *__restrict__ dDW, const float *__restrict__ fwdfrag,
                                                       const float *__restrict__ bwdfrag, float *__restrict__ partials, int n, int H, int W,
                                                       int OH, int OW, int pad_lo, float pre_sub, float pre_div,
                                                       const float *__restrict__ up_ddw = nullptr, const float *__restrict__ up_dw = nullptr,
-                                                      int up_oh = 0, int up_ow = 0, int up_pad = 0 SB32_STAMP_PARAM)
+                                                      int up_oh = 0, int up_ow = 0, int up_pad = 0 UBD_STAMP_PARAM)
 {
     using C = sepb_cfg<CIN, STRIDE, (int)sizeof(TX), UPS>;
     static_assert(UPS == 0 || sizeof(TX) == 4 || CIN != UBD_C, "the in-block G tile needs an fp32 mask tile of G's size");
@@ -845,7 +840,7 @@ static int launch_sep_bwd(const ubd_handle *h, const void *x, int in_u8, const f
     float *partials = rp_add(rq, grid, part, grads + h->off_sep_dw[s], 9 * CIN, grads + h->off_sep_pw[s], CIN * UBD_C, grads + h->off_sep_b[s], st);
     if (!partials) return -1;
     auto launch = [&](auto u8) {
-        hipLaunchKernelGGL((sep_bwd_kernel<CIN, STRIDE, decltype(u8)::value, TX, TR, UPS>), dim3(grid), dim3(256), 0, st, x, G, dDW, ffrag, bfrag, partials, n, H, W, OH, OW, pad_lo, sub, div, up_ddw, up_dw, up_oh, up_ow, up_pad SB_STAMP_ARG);
+        hipLaunchKernelGGL((sep_bwd_kernel<CIN, STRIDE, decltype(u8)::value, TX, TR, UPS>), dim3(grid), dim3(256), 0, st, x, G, dDW, ffrag, bfrag, partials, n, H, W, OH, OW, pad_lo, sub, div, up_ddw, up_dw, up_oh, up_ow, up_pad UBD_STAMP_ARG("sep_bwd", CIN, STRIDE));
     };
     in_u8 ? launch(int_c<1>()) : launch(int_c<0>());
     return 0;

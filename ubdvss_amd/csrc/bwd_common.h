@@ -344,15 +344,6 @@ __global__ __launch_bounds__(256) void head_wgrad1_kernel(const void *__restrict
         partials[(size_t)blockIdx.x * (UBD_C + 1) + threadIdx.x] = (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
 }
 
-#ifdef UBD_STAMPS   // diagnostic build only: one stamp buffer, for the (CIN, STRIDE) variant of sep_bwd_kernel / sepb16_kernel that ubd_debug_set_stamps_sepb selects (backward.hip)
-extern unsigned long long *g_sepb_stamps;
-extern int g_sepb_stamps_cin, g_sepb_stamps_stride;
-#define SB_STAMP_ARG , ((CIN == g_sepb_stamps_cin && STRIDE == g_sepb_stamps_stride) ? g_sepb_stamps : nullptr)
-#define WG_STAMP_ARG , ((g_sepb_stamps_cin == -1 && g_sepb_stamps_stride == dd) ? g_sepb_stamps : nullptr)      // cin = -1: dil_wgrad16 of dilation `stride`
-#else
-#define SB_STAMP_ARG
-#define WG_STAMP_ARG
-#endif
 
 // Host side of the batched reduction: every producer takes its own partial-sum matrix out of the workspace region and
 // queues a job; rp_flush launches the jobs queued so far (after the dilated loop: those gradients feed the overlapped

@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "../../include/ubd.h"
 #include "stem_plan.h"
+#include "stamps.h"
 
 #define UBD_C 24              // n_filters (net.py:289)
 #define UBD_NUM_DIL 6         // dense dilated layers L4..L9 (net.py:298-304)

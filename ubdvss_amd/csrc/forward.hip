@@ -439,13 +439,6 @@ __global__ __launch_bounds__(256, (CIN == UBD_C) ? (STRIDE == 1 ? 3 : 2) : 5) vo
     }
 }
 
-#ifdef UBD_STAMPS   // diagnostic build only: device buffer that receives in-kernel s_memtime stamps
-static unsigned long long *g_ubd_stamps = nullptr;
-extern "C" void ubd_debug_set_stamps(void *p) { g_ubd_stamps = (unsigned long long *)p; }
-#define UBD_STAMP_ARG(p) , p       // the stem kernels' last parameter exists in the diagnostic build only
-#else
-#define UBD_STAMP_ARG(p)
-#endif
 #include "pp_lds.h"
 #include "stem23.h"
 #include "stem123.h"
@@ -763,7 +756,7 @@ static void launch_stem123(const ubd_handle *h, const float *params, const void 
         auto launch = [&](auto pl) {
             hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD>), dim3(grid), dim3(s23_cfg::NT), 0, st,
                                images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p
-                               UBD_STAMP_ARG(COLD ? (unsigned long long *)nullptr : g_ubd_stamps));
+                               UBD_STAMP_ARG(COLD ? "" : "stem123"));      // the stamp indices are the strip walk's
         };
         if constexpr (decltype(in_u8)::value == 0) { if (plain) return launch(ubd_int<1>{}); }
         launch(ubd_int<0>{});
@@ -830,7 +823,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
         const int grid = plan.strips < h->num_cus ? (int)plan.strips : h->num_cus;   // one 8-wave block per CU (120 KB of LDS) walks whole row strips of tiles
         ubd_dispatch_bool(pad_s2 != 0, [&](auto pad) {
             hipLaunchKernelGGL(stem23_kernel<decltype(pad)::value>, dim3(grid), dim3(s23_cfg::NT), 0, st, a1, cur, sf1, params + h->off_sep_b[1], sf2,
-                               params + h->off_sep_b[2], n, H2, W2, H4, W4, pad_s2 UBD_STAMP_ARG(g_ubd_stamps));
+                               params + h->off_sep_b[2], n, H2, W2, H4, W4, pad_s2 UBD_STAMP_ARG("stem23"));
         });
     } else if (plan.form == UBD_STEM_FORM_SEPARATE) {
         launch_sep<UBD_C, 1>(h, a1, 0, a2, sf1, params + h->off_sep_b[1], n, H2, W2, H2, W2, 1, 0.f, 1.f, st);

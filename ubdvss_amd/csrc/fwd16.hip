@@ -691,18 +691,6 @@ __global__ __launch_bounds__(256, XB == 1 ? 4 : 3) void sep12_16_kernel(const vo
 }
 
 #include "sep123_16.h"
-#ifdef UBD_STAMPS
-static unsigned long long *g_d16s_stamps = nullptr;
-static int g_d16s_stamps_d = 0;
-extern "C" void ubd_debug_set_stamps_d16s(void *p, int d) { g_d16s_stamps = (unsigned long long *)p; g_d16s_stamps_d = d; }
-#define D16S_STAMP_ARG , (d == g_d16s_stamps_d ? g_d16s_stamps : nullptr)
-static unsigned long long *g_s123_stamps = nullptr;
-extern "C" void ubd_debug_set_stamps_s123(void *p) { g_s123_stamps = (unsigned long long *)p; }
-#define S123_16_STAMP_ARG , g_s123_stamps
-#else
-#define S123_16_STAMP_ARG
-#define D16S_STAMP_ARG
-#endif
 
 // ------------------------------------------------------------------------------------ dilated layers
 struct a16_frags { u32x4 v[7]; u32x2 m0, m1; };
@@ -869,20 +857,12 @@ template <typename T, int EPI = 0>
 #endif
 __global__ __launch_bounds__(256, D16S_OCC) void dilconv16s_kernel(const unsigned short *__restrict__ x, unsigned short *__restrict__ y,
                                                             const u32x4 *__restrict__ wfrag, const float *__restrict__ bias, int n, int h,
-                                                            int w, int d, const float *__restrict__ head, float *__restrict__ logits, const d16s_geom geo
-#ifdef UBD_STAMPS
-                                                            , unsigned long long *__restrict__ stamps
-#endif
-                                                            )
+                                                            int w, int d, const float *__restrict__ head, float *__restrict__ logits, const d16s_geom geo UBD_STAMP_PARAM)
 {
-#ifdef UBD_STAMPS   // diagnostic build only: s_memtime of lane 0 of every wave at the phase boundaries of its first 8 items (tools/stamps_d16s.py)
-#define D16STAMP(k) do { if (stamps && iter < 8 && (threadIdx.x & 63) == 0 && blockIdx.x < 768) stamps[(((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + iter) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-    // block time line: [5] entry, [6] in front of the item loop, [7] behind it (s_memtime), [5..7] of item slot 1: the same three points on the 100-MHz clock all CUs share
-#define D16BLK(k) do { if (stamps && (threadIdx.x & 63) == 0 && blockIdx.x < 768) { const size_t b_ = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 * 8; stamps[b_ + (k)] = __builtin_amdgcn_s_memtime(); stamps[b_ + 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define D16STAMP(k) do {} while (0)
-#define D16BLK(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 8 items of the block (tools/stamps_d16s.py)
+#define D16STAMP(k) UBD_STAMP(iter < 8, (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + iter) * 8 + (k))
+    // block time line: [5] entry, [6] in front of the item loop, [7] behind it (shader clock), [5..7] of item slot 1: the same three points on the 100-MHz clock all CUs share
+#define D16BLK(k) do { UBD_STAMP(true, ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + (k)); UBD_STAMP_RT(true, ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + 8 + (k)); } while (0)
     D16BLK(5);
     // EPI 0: y = relu(conv + bias).  EPI 2 / 3 (last hidden layer with ONE output channel, round 4: the staged kernel takes L9 too): the
     // 1 x 1 head (24 fp32 weights + bias at `head`, net.py:308-311) is applied in the epilogue, fp32 logits to `logits`; EPI 2 (inference)
@@ -1129,7 +1109,7 @@ static void launch_sep123(const ubd_handle *h, const void *x, unsigned short *a1
     auto launch = [&](auto pl) {
         ubd_dispatch_bool(write_a12, [&](auto wr) {
             hipLaunchKernelGGL((sep123_16_kernel<CIN, IN_MODE, decltype(pl)::value, decltype(wr)::value, T>), dim3(grid), dim3(256), 0, st, x, a1, a2, a3, frag1,
-                               bias1, (const u32x4 *)ready23, bias2, bias3, n, H, W, H2, W2, H4, W4, pad_lo, sub, div S123_16_STAMP_ARG);
+                               bias1, (const u32x4 *)ready23, bias2, bias3, n, H, W, H2, W2, H4, W4, pad_lo, sub, div UBD_STAMP_ARG("sep123_16"));
         });
     };
     if constexpr (IN_MODE == 0) {                                  // offsets inside one image below 2^31
@@ -1164,7 +1144,7 @@ static void launch_dil16(const ubd_handle *h, int epi, const unsigned *frag, con
         float *lg = epi == 0 ? nullptr : epi == 2 ? (float *)out : logits3;
         auto launch = [&](auto e) {
             hipLaunchKernelGGL((dilconv16s_kernel<T, decltype(e)::value>), dim3(g2), dim3(256), 0, st, in16, act, (const u32x4 *)frag, bias, n, H4, W4, d, head, lg,
-                               geo D16S_STAMP_ARG);
+                               geo UBD_STAMP_ARG("dilconv16s", d));
         };
         if (epi == 0) launch(ubd_int<0>{}); else if (epi == 2) launch(ubd_int<2>{}); else launch(ubd_int<3>{});
         return;

@@ -684,13 +684,11 @@ __device__ __forceinline__ void loss1_refine(const unsigned (&bits)[R], int matc
 template <int R>
 __global__ __launch_bounds__(LOSS1_BLOCK) void loss_one_kernel(const float *__restrict__ logits, int k_out, const int *__restrict__ y_true, long npix,
                                                                loss_hdr *hdr, unsigned *hist, unsigned *blockties,
-                                                               loss1_rec *rec, float *__restrict__ dlogits, float *__restrict__ loss4, unsigned long long *dbg)
+                                                               loss1_rec *rec, float *__restrict__ dlogits, float *__restrict__ loss4, unsigned long long *dbg UBD_STAMP_PARAM)
 {
-#ifdef LOSS1_STAMPS
-#define STAMP(i) do { if (threadIdx.x == 0) dbg[blockIdx.x * 16 + (i)] = wall_clock64(); } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
+    // diagnostic build only (stamps.h): thread 0 of every block at the stage boundaries on the 100-MHz clock all CUs share, 16 slots per block
+    // (tools/stamps_loss.py).  dbg: the same buffer (nullptr in the product build)
+#define STAMP(i) UBD_STAMP_RT(threadIdx.x == 0, blockIdx.x * 16 + (i))
     STAMP(0);
     __shared__ unsigned s_h[2048];
     __shared__ double s_red[LOSS1_BLOCK / 64 * 6];
@@ -964,15 +962,17 @@ static loss1_dev_state g_loss1_dev[16];          // by device ordinal
 
 // the one-launch form applies when every block can be resident (grid <= CUs) with its chunk in registers (<= 4 pixels per thread: 1 M pixels on 256 CUs)
 static bool loss_one_launch(const float *logits, int k_out, const int32_t *y_true, long npix, float *loss, float *dlogits, loss_hdr *hdr,
-                            unsigned *hist, unsigned *blockties, loss1_rec *rec, int max_grid, hipStream_t st, void *dbg)
+                            unsigned *hist, unsigned *blockties, loss1_rec *rec, int max_grid, hipStream_t st)
 {
+    unsigned long long *dbg = nullptr;
+    UBD_STAMPS_ONLY(dbg = ubd_stamps_for("loss").p;)
     if (max_grid > LOSS_MAX_BLOCKS) max_grid = LOSS_MAX_BLOCKS;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }   // a graph replays anywhere: the chain has no barrier
     for (int r = 1; r <= LOSS1_MAX_R; r *= 2) {
         const long g = (npix + (long)r * LOSS1_BLOCK - 1) / ((long)r * LOSS1_BLOCK);
         if (g > max_grid) continue;
-#define LOSS1_LAUNCH(RR) hipLaunchKernelGGL((loss_one_kernel<RR>), dim3((int)g), dim3(LOSS1_BLOCK), 0, st, logits, k_out, y_true, npix, hdr, hist, blockties, rec, dlogits, loss, (unsigned long long *)dbg)
+#define LOSS1_LAUNCH(RR) hipLaunchKernelGGL((loss_one_kernel<RR>), dim3((int)g), dim3(LOSS1_BLOCK), 0, st, logits, k_out, y_true, npix, hdr, hist, blockties, rec, dlogits, loss, dbg UBD_STAMP_ARG("loss"))
         // Two of these kernels on two streams could each hold a part of the CUs and wait for the rest for ever (every block spins at the
         // barriers until all of its grid is resident; the spin limit would end it with a NaN loss after seconds).  Launches on ONE stream are
         // ordered anyway (the train step, bench.py: no cost); the first launch from a second stream of this process drains the device once,
@@ -1032,7 +1032,7 @@ int ubd_loss_impl(const float *logits, int k_out, const int32_t *y_true, long np
     const int cgrid = (int)((npix + chunk - 1) / chunk);
     int rc;
     if (!glob && !(h && h->loss_chain) &&
-        loss_one_launch(logits, k_out, y_true, npix, loss, dlogits, hdr, (unsigned *)(ws + L.off_histk), blockties, (loss1_rec *)(ws + L.off_rec), h ? h->num_cus : LOSS_MAX_BLOCKS, st, ce)) {    // ce: unused by this form (stamps of a -DLOSS1_STAMPS build)
+        loss_one_launch(logits, k_out, y_true, npix, loss, dlogits, hdr, (unsigned *)(ws + L.off_histk), blockties, (loss1_rec *)(ws + L.off_rec), h ? h->num_cus : LOSS_MAX_BLOCKS, st)) {
         UBD_CHECK_HIP(hipGetLastError());
         return 0;
     }

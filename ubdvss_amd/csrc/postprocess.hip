@@ -495,10 +495,6 @@ __global__ __launch_bounds__(256) void pp_emit_kernel(int n, const int *__restri
 
 
 // ------------------------------------------------------------------------------------ one-launch front end (pp_lds.h)
-#ifdef UBD_STAMPS   // diagnostic build only (tools/build_diag.sh)
-static unsigned long long *g_pp_stamps = nullptr;
-extern "C" void ubd_debug_set_stamps_pp(void *p) { g_pp_stamps = (unsigned long long *)p; }
-#endif
 template <bool TAIL, int NT = PP_LDS_THREADS>
 __global__ __launch_bounds__(NT) void pp_front_lds_kernel(pp_lds_args a)
 {
@@ -586,11 +582,8 @@ extern "C" int ubd_postprocess(ubd_handle *hd, const float *logits, int n, int m
         a.vote = vote; a.quads = quads; a.classes = classes; a.counts = counts;
         a.g_owner = (!fused_tail && n_cls > 0) ? owner : nullptr;
         a.g_kept = (!fused_tail && n_cls > 0) ? kept : nullptr;
-#ifdef UBD_STAMPS
-        a.stamps = g_pp_stamps;
-#else
         a.stamps = nullptr;
-#endif
+        UBD_STAMPS_ONLY(a.stamps = ubd_stamps_for("postprocess").p; a.stamps_cap = ubd_stamps_for("postprocess").cap;)
         if (fused_tail && hd->pp_threads_512) {        // diagnostics: the block shape the job has inside the stem kernel (512 threads)
             static bool attr512 = false;
             if (!attr512) { UBD_CHECK_HIP(hipFuncSetAttribute((const void *)pp_front_lds_kernel<true, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS_MAX_BYTES)); attr512 = true; }

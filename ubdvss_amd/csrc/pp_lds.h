@@ -578,7 +578,8 @@ struct pp_lds_args {
     int *binary_map, *g_nroots, *g_nkept, *g_owner, *g_roots, *g_kept, *stage, *ymax, *rows;
     float *vote;
     int *quads, *classes, *counts;
-    unsigned long long *stamps;                                // diagnostic build only (nullptr otherwise)
+    unsigned long long *stamps;                                // diagnostic build only (nullptr otherwise), with its capacity (stamps.h)
+    UBD_STAMPS_ONLY(size_t stamps_cap;)
 };
 
 // NT threads (a multiple of 64, <= 1024) work on image `img`; `smem`: pp_front_lds_bytes(h * w, root_cap) bytes of LDS, 16-byte aligned.
@@ -597,13 +598,8 @@ __device__ __forceinline__ void pp_image_lds(int *__restrict__ smem, const pp_ld
     int *__restrict__ stage = A.stage, *__restrict__ ymax = A.ymax, *__restrict__ rows = A.rows;
     float *__restrict__ vote = A.vote;
     int *__restrict__ quads = A.quads, *__restrict__ classes = A.classes, *__restrict__ counts = A.counts;
-#ifdef UBD_STAMPS
-    unsigned long long *__restrict__ stamps = A.stamps;
-    int stamp_k = 0;
-#define PPSTAMP() do { if (stamps && threadIdx.x == 0) stamps[img * 16 + stamp_k] = __builtin_amdgcn_s_memtime(); ++stamp_k; } while (0)
-#else
-#define PPSTAMP() do {} while (0)
-#endif
+    UBD_STAMPS_ONLY(const ubd_stamp_buf stamps = {A.stamps, A.stamps_cap}; int stamp_k = 0;)      // thread 0 after every block barrier, 16 slots per image
+#define PPSTAMP() UBD_STAMP(threadIdx.x == 0, img * 16 + stamp_k++)       // the index is evaluated by the storing thread only: it alone counts
     PPSTAMP();
     const int hw = h * w;
     int *lab = smem;

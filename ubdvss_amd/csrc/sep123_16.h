@@ -138,17 +138,10 @@ __global__ __launch_bounds__(256, S123_OCC) void sep123_16_kernel(
     const void *__restrict__ xin, unsigned short *__restrict__ a1out, unsigned short *__restrict__ a2out, unsigned short *__restrict__ y,
     const float *__restrict__ frag1, const float *__restrict__ bias1, const u32x4 *__restrict__ ready23, const float *__restrict__ bias2,
     const float *__restrict__ bias3, int n, int H, int W, int H2, int W2, int H4, int W4, int pad_lo,
-    float pre_sub, float pre_div
-#ifdef UBD_STAMPS
-    , unsigned long long *__restrict__ stamps
-#endif
-    )
+    float pre_sub, float pre_div UBD_STAMP_PARAM)
 {
-#ifdef UBD_STAMPS   // diagnostic build only: s_memtime of lane 0 of every wave at the phase boundaries of its first 16 tiles
-#define S3STAMP(k) do { if (stamps && it < 16 && (threadIdx.x & 63) == 0 && blockIdx.x < 768) stamps[(((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + it) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define S3STAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 16 tiles of the block (tools/stamps_s123.py)
+#define S3STAMP(k) UBD_STAMP(it < 16, (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + it) * 8 + (k))
     using C = sep123_cfg<CIN>;
     constexpr int AP = C::AP, TP = C::TP;
     static_assert(!PLAIN || IN_MODE == 0, "LDS-DMA moves fp32 pixels only");

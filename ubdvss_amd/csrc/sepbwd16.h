@@ -192,18 +192,11 @@ __global__ __launch_bounds__(256, (sepb16_cfg<CIN, STRIDE, GSRC, IN_MODE == 2>::
                                                         const float *__restrict__ dw_own, const float *__restrict__ pw_own,
                                                         const float *__restrict__ dw_up, float *__restrict__ partials, int n, int H,
                                                         int W, int OH, int OW, int pad_lo, int DH, int DW_, int pad_up, float pre_sub,
-                                                        float pre_div, const rp_job prev
-#ifdef UBD_STAMPS
-                                                        , unsigned long long *__restrict__ stamps
-#endif
-                                                        )
+                                                        float pre_div, const rp_job prev UBD_STAMP_PARAM)
 {
-#ifdef UBD_STAMPS   // diagnostic build only: s_memtime of lane 0 of every wave at the phase boundaries of its first 8 tiles
-    int stamp_it = 0;
-#define SBSTAMP(k) do { if (stamps && stamp_it < 8 && (threadIdx.x & 63) == 0) stamps[(((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + stamp_it) * 12 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SBSTAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 8 tiles of the block, 12 slots per tile (tools/stamps_sepb.py)
+    UBD_STAMPS_ONLY(int stamp_it = 0;)
+#define SBSTAMP(k) UBD_STAMP(stamp_it < 8, (((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + stamp_it) * 12 + (k))
     constexpr bool XDMA = (IN_MODE == 2);
     constexpr int IN_U8 = (IN_MODE == 1);
     static_assert(!XDMA || CIN != UBD_C, "the 24-channel patch is a 16-bit tensor");
@@ -800,9 +793,7 @@ __global__ __launch_bounds__(256, (sepb16_cfg<CIN, STRIDE, GSRC, IN_MODE == 2>::
             }
         }
         SBSTAMP(9);
-#ifdef UBD_STAMPS
-        ++stamp_it;
-#endif
+        UBD_STAMPS_ONLY(++stamp_it;)
         if constexpr (X_AHEAD || XDMA) xb ^= 1;
     }
 #undef SBSTAMP

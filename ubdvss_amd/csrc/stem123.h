@@ -76,10 +76,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                                                                 int n, int H, int W, int H2, int W2, int H4, int W4,
                                                                 float pre_sub, float pre_div, int *__restrict__ ticket, pp_lds_args pj,
                                                                 int a3_l2p /* L3's output rows in column layout P_(2^a3_l2p) (wino6.hip) */
-#ifdef UBD_STAMPS
-                                                                , unsigned long long *__restrict__ stamps
-#endif
-                                                                )
+                                                                UBD_STAMP_PARAM)
 {
     using C = s23_cfg;
     using X = s123_cfg<CIN>;
@@ -89,11 +86,8 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     // queue below, where the blocks that had no image have meanwhile taken its share (tickets).  One launch instead of a second
     // stream with two events per step: round 3 measured 10 us of idle forward stream behind every event record and a placement
     // race between the postprocess blocks and this kernel's whole-CU blocks.
-#ifdef UBD_STAMPS   // diagnostic build only: the block's time line on the 100-MHz clock all CUs share (tools/stamps_stem_blocks.py)
-#define S123_BLOCK_STAMP(k) do { if (stamps && threadIdx.x == 0 && (k) < 32) stamps[(size_t)gridDim.x * 8 * 16 * 8 + (size_t)blockIdx.x * 32 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define S123_BLOCK_STAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the block's time line on the 100-MHz clock all CUs share, 32 slots per block behind the tile stamps (tools/stamps_stem_blocks.py)
+#define S123_BLOCK_STAMP(k) UBD_STAMP_RT(threadIdx.x == 0 && (k) < 32, (size_t)gridDim.x * 8 * 16 * 8 + (size_t)blockIdx.x * 32 + (k))
     S123_BLOCK_STAMP(0);
     if (pj.n > 0) {
         for (int im = (int)blockIdx.x; im < pj.n; im += (int)gridDim.x) {
@@ -309,8 +303,9 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
         for (int j = 0; j < 3; ++j) ring[j] = had_job ? ticket_ls(t0_early + j) : (int)blockIdx.x * D + j;   // only the first D are this block's: the rest are overwritten before use
     }
     __syncthreads();
-    S123_BLOCK_STAMP(3);
     tpos cur = strip_pos(0, 0);
+    S123_BLOCK_STAMP(3);         // behind the strip's decoding (a few scalar instructions), not in front of it: with thread 0's store between the barrier and the decoding
+                                 // hipcc hands dma_x's buffer descriptor to ubd_blds16 in vector registers, which the instruction does not take
     // The counter resets itself: every block checks out through a second counter, and the last one out -- by then nobody draws
     // tickets any more -- zeroes both for the next launch on this workspace (stream order; the host zeroes them only before
     // the first launch on a workspace: the per-pass memset was a 5 us kernel of its own between two forward passes).
@@ -328,11 +323,8 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     if (cur.ls >= strips) { S123_BLOCK_STAMP(2); check_out(); return; }              // block-uniform: nothing left
     tpos nx1 = advance(cur);
     int pending = 0;                                                                 // ticket in flight (thread 0)
-#ifdef UBD_STAMPS   // diagnostic build only: s_memtime at the phase boundaries, lane 0 of every wave, first 16 tiles of the block
-#define S123_STAMP(k) do { if (stamps && it < 16 && lane == 0) stamps[(((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define S123_STAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 16 tiles of the block
+#define S123_STAMP(k) UBD_STAMP(it < 16, (((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k))
     // ---- phase 0a of tile p (non-PLAIN): the patch, requested a phase ago into registers, goes to LDS (preprocessed)
     auto convert_x = [&](tpos p) {
         const bool plain = !IN_U8 && pre_sub == 0.f && pre_div == 1.f;              // already preprocessed fp32 input: a copy

@@ -48,17 +48,10 @@ template <bool CARRY>
 __global__ __launch_bounds__(s23_cfg::NT, 1) void stem23_kernel(const float *__restrict__ a1, float *__restrict__ y,
                                                         const float *__restrict__ frag2, const float *__restrict__ bias2,
                                                         const float *__restrict__ frag3, const float *__restrict__ bias3,
-                                                        int n, int H2, int W2, int H4, int W4, int pad_lo
-#ifdef UBD_STAMPS
-                                                        , unsigned long long *__restrict__ stamps
-#endif
-                                                        )
+                                                        int n, int H2, int W2, int H4, int W4, int pad_lo UBD_STAMP_PARAM)
 {
-#ifdef UBD_STAMPS   // diagnostic build only (tools/build_diag.sh): s_memtime at the phase boundaries, lane 0 of every wave, 16 tiles
-#define UBD_STAMP(k) do { if (stamps && it < 16 && lane == 0) stamps[(((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define UBD_STAMP(k) do {} while (0)
-#endif
+    // diagnostic build only (stamps.h): the phase boundaries, every wave, first 16 tiles of the block
+#define S23_STAMP(k) UBD_STAMP(it < 16, (((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k))
     using C = s23_cfg;
     __shared__ __attribute__((aligned(16))) float smem[C::SMEM_FLOATS];                    // ONE LDS object
     float *l2 = smem + 2 * C::BUF_FLOATS;
@@ -202,13 +195,13 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem23_kernel(const float *__r
         // writes of phase A nor waits for it anywhere -- these counted waits are the only ones.  Outstanding on waves 4-7,
         // oldest first: [DMA of this tile: k pieces] [DMA of the next tile: k pieces, issued during the previous phase B];
         // k = 10 (wave 4) or 9.  Waves 0-3 only have their L3 stores outstanding, which nobody waits for.
-        UBD_STAMP(0);
+        S23_STAMP(0);
         if (it < 2 || !has_next) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // prologue DMAs / nothing issued behind this patch
         else if (wid == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
         else if (wid > 4) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        UBD_STAMP(1);
+        S23_STAMP(1);
         __builtin_amdgcn_s_barrier();                                               // ... for everyone; the L2 image is free again
-        UBD_STAMP(2);
+        S23_STAMP(2);
         const int iy0 = R0 - 1, ix0 = C0 - 1;
         const bool border = (iy0 < 0) || (ix0 < 0) || (iy0 + C::PH > H2) || (ix0 + C::PW > W2);
         if (border) {                                                               // block-uniform: L2's 'same' zero padding
@@ -227,7 +220,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem23_kernel(const float *__r
         }
         // L3's zero padding: L2 positions outside L2's map must read as 0 (block-uniform: does this tile have any?)
         const bool mask_needed = (R0 < 0) || (C0 < 0) || (R0 + C::LR > H2) || (C0 + C::LC > W2);
-        UBD_STAMP(3);
+        S23_STAMP(3);
 
         // ---- phase A: L2 on the 9 x 33 positions; wave = (column half, rows {0-2, 3-4, 5-6, 7-8})
         {
@@ -329,9 +322,9 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem23_kernel(const float *__r
             }
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);                                         // lgkmcnt(0): the L2 image is written
-        UBD_STAMP(4);
+        S23_STAMP(4);
         __builtin_amdgcn_s_barrier();                                               // ... by everyone; this tile's patch buffer is free
-        UBD_STAMP(5);
+        S23_STAMP(5);
 
         if (wid < 4) {
             // ---- phase B, waves 0-3: L3 output row oy0 + wid
@@ -361,13 +354,13 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem23_kernel(const float *__r
             }
             store_tile_relu_t(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, z4, z4);   // bias already in
         }
-        UBD_STAMP(6);
+        S23_STAMP(6);
         // ---- waves 4-7: the patch of tile t + 2, into the buffer phase A has just released
         if (wid >= 4 && has_next2) dma_tile(nx2, smem + (it & 1) * C::BUF_FLOATS, true);
-        UBD_STAMP(7);
+        S23_STAMP(7);
         if (!has_next) break;
         cur = nx1;
         nx1 = nx2;
     }
-#undef UBD_STAMP
+#undef S23_STAMP
 }

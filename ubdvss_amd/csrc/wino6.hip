@@ -80,13 +80,8 @@ void ubd_launch_pack_wino6(const ubd_handle *h, const float *params, unsigned *o
 //   instruction with an SGPR source ~1.95 ns, v_and_b32 with a literal 1.05 ns, s_nop and scalar ALU ~1.9 ns of the wave's time.
 // resid / pack_hi / pack6 / mfma16: split3.h
 
-#ifdef UBD_STAMPS   // diagnostic build only (tools/build_diag.sh)
-static unsigned long long *g_wino6_stamps = nullptr;
-extern "C" void ubd_debug_set_stamps_wino6(void *p) { g_wino6_stamps = (unsigned long long *)p; }
-#define WSTAMP(k) do { if (stamps && lane == 0) stamps[((size_t)blockIdx.x * W6_WAVES + wave_in_block) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WSTAMP(k) do {} while (0)
-#endif
+// diagnostic build only (stamps.h): eight slots per wave, no tile index (tools/stamps_wino6.py)
+#define WSTAMP(cond, k) UBD_STAMP(cond, ((size_t)blockIdx.x * W6_WAVES + wave_in_block) * 8 + (k))
 
 #ifndef W6_WAVES
 #define W6_WAVES 8
@@ -127,11 +122,7 @@ struct w6addr {
 template <int EPI, bool LAY>
 __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const float *__restrict__ x, float *__restrict__ y,
                                                                      const unsigned *__restrict__ ufrag,
-                                                                     const float *__restrict__ bias, w6geom G, const float *__restrict__ head
-#ifdef UBD_STAMPS
-                                                                     , unsigned long long *__restrict__ stamps
-#endif
-                                                                     )
+                                                                     const float *__restrict__ bias, w6geom G, const float *__restrict__ head UBD_STAMP_PARAM)
 {
     __shared__ __attribute__((aligned(16))) unsigned s_u[UBD_WINO6_FRAG_U32];       // 96 KiB
     const int lane = threadIdx.x & 63;
@@ -227,7 +218,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
     // block copies U into LDS: their latency hides behind the copy.
     w6samples D;
     w6addr A, An;
-    WSTAMP(0);
+    WSTAMP(true, 0);
     set_addr(A, g < g_last ? g : g_last);
     load_row(D, A, 0);
     load_row(D, A, 2);
@@ -251,7 +242,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
     }
     asm volatile("s_waitcnt vmcnt(9)" ::: "memory");          // the sample rows (older) and this wave's rounds 0..2 have landed
     __builtin_amdgcn_s_barrier();                             // A: points 0..3 of the weights are in LDS
-    WSTAMP(1);
+    WSTAMP(true, 1);
     if (g >= g_end || wave_in_block >= G.wpb) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                         // B
@@ -360,9 +351,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
             }
             if (xi < 15) { const int bn = (b + 1) & 3; P1 = pack6(V4[bn], V2[bn]); P2 = pack6(r4, r2); P3 = pack6(t4, t2); }
             consume(a, b, m);
-#ifdef UBD_STAMPS
-            if (gcount == 1 && (xi & 3) == 3) WSTAMP(2 + (xi >> 2));
-#endif
+            WSTAMP(gcount == 1 && (xi & 3) == 3, 2 + (xi >> 2));
         }
         // Row 1 of the NEXT group is requested here, BEFORE this group's stores: the vector-memory counter retires in issue order, so a
         // load issued after the stores is only known to have landed once the stores have been acknowledged -- the wait for row 1 (three
@@ -402,23 +391,16 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                     }
                 }
         }
-#ifdef UBD_STAMPS
-        if (gcount == 1) WSTAMP(6);
-        if (gcount == 0) WSTAMP(1);                          // re-stamped: start of the second group
-#endif
+        WSTAMP(gcount == 1, 6);
+        WSTAMP(gcount == 0, 1);                              // re-stamped: start of the second group
         ++gcount;
         g += stride;
         if (g >= g_end) break;
         A = An;
     }
-    WSTAMP(7);
+    WSTAMP(true, 7);
 }
 
-#ifdef UBD_STAMPS
-#define WSTAMP_ARG , g_wino6_stamps
-#else
-#define WSTAMP_ARG
-#endif
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // frag: this layer's UBD_WINO6_FRAG_U32 packed dwords; epi 0 / 2 as in ubd_launch_dilconv_wino
@@ -452,11 +434,11 @@ void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag
     grid = (grid + 7) / 8 * 8;
     const bool lay = lay_in != 1 || lay_out != 1;
     if (epi == 2 && lay)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<2, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head WSTAMP_ARG);
+        hipLaunchKernelGGL((dilconv_wino6_kernel<2, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
     else if (epi == 2)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<2, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head WSTAMP_ARG);
+        hipLaunchKernelGGL((dilconv_wino6_kernel<2, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
     else if (lay)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<0, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr WSTAMP_ARG);
+        hipLaunchKernelGGL((dilconv_wino6_kernel<0, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
     else
-        hipLaunchKernelGGL((dilconv_wino6_kernel<0, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr WSTAMP_ARG);
+        hipLaunchKernelGGL((dilconv_wino6_kernel<0, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
 }
