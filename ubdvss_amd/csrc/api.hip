@@ -119,6 +119,7 @@ extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
     h->num_cus = prop.multiProcessorCount;
     h->use_wino = h->wino_x6 = h->chain_reduce = 1;             // the defaults that are not 0
     h->fuse_stem = cfg->fml_compatible != 0 ? UBD_STEM_FUSED123 : UBD_STEM_SEPARATE;
+    h->stem_cold_tail = -1;
     for (const env_switch &sw : ENV_SWITCHES) {
         const char *e = getenv(sw.name);
         if (!e) continue;
@@ -126,6 +127,7 @@ extern "C" int ubd_create(const ubd_config *cfg, ubd_handle **out)
         if (sw.value == NUMBER) { if (atoi(e) > 0) *field = atoi(e); }
         else if (sw.value == ANY || strcmp(e, sw.value) == 0) *field = sw.set;
     }
+    { const char *s = getenv("UBD_STEM_COLD_TAIL"); if (s && *s >= '0' && *s <= '9') h->stem_cold_tail = atoi(s); }      // 0 is a value: not a table row
     { const char *s = getenv("UBD_STEM"); if (s && strcmp(s, "cold123") == 0 && cfg->fml_compatible != 0) { h->fuse_stem = UBD_STEM_COLD123; h->fuse_force = 1; } }      // fml padding only: not a table row
     // Keras model.get_weights() order
     size_t off = 0;

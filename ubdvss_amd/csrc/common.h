@@ -24,9 +24,11 @@ struct ubd_handle {
     size_t n_params;
     int num_cus;              // CUs of the device; UBD_TEST_NUM_CUS=n (test hook): pretend it has n, so that every persistent kernel walks many tiles per block even on
                               // the small shapes the CPU oracle can check (tests/test_gpu_persistent.py; ubd_num_cus reports what was taken)
-    // The UBD_* environment switches below are the definition of each switch (api.hip holds only the table that parses them).  They are read
+    // The UBD_* environment switches below are the definition of each switch (api.hip holds only the table that parses them, and two lines
+    // beside it for UBD_STEM=cold123 and UBD_STEM_COLD_TAIL, which the table's kinds do not express).  They are read
     // ONCE, in ubd_create, never in a launch path; a value that is not named here is ignored.
     int pp_lds_attr_set;      // pp_front_lds_kernel's dynamic-LDS limit has been raised on this handle's device
+    int stem_cold_tail;       // UBD_STEM_COLD_TAIL=rows: tail rows of a job pass of the strip-walking stem (ubd_plan_stem clips it; 0: none -- the reference side of tests/test_gpu_stem_cold_tail.py); -1 (unset): the plan's default
     int fuse_force;           // UBD_STEM named a fused variant explicitly: use it at any launch size
     int split_headbwd;        // UBD_HEADBWD=split: bf16 train step with classes: head data gradient and head weight gradient as two kernels (diagnostics / tests)
     int no_pair_dilbwd;       // UBD_DILBWD=pair8: narrow sub-grids (dilation 16 on 128-wide maps) keep the 8-wide tiles instead of pairs in 16-wide ones (diagnostics / tests)

@@ -739,11 +739,12 @@ static int check_forward_input(int n, int H, int W, int in_dtype)
 }
 
 // L1 -> L2 -> L3 in one kernel (stem123.h): neither a1 nor a2 is touched.  COLD: one cold-started tile per work unit, tiles of a row 15 L3
-// columns apart, no tickets, no job; else every block walks whole strips and `job` (may be null) rides along
+// columns apart, no tickets, no job; else every block walks whole strips and `job` (may be null) rides along, with the last
+// tail_rows strips handed out as ticketed cold tiles (the plan gives 0 without a job)
 template <bool COLD>
 static void launch_stem123(const ubd_handle *h, const float *params, const void *images, bool u8, float *a3, const float *sf0, const float *sf1,
                            const float *sf2, int n, int H, int W, float sc, float sh, long units, int *ticket, const pp_lds_args *job, int a3_l2p,
-                           hipStream_t st)
+                           int tail_rows, hipStream_t st)
 {
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
     const int grid = units < h->num_cus ? (int)units : h->num_cus;       // one 8-wave block per CU (LDS)
@@ -754,13 +755,29 @@ static void launch_stem123(const ubd_handle *h, const float *params, const void 
     const bool plain = ubd_pixels_by_lds_dma(!u8, sc, sh, H, W, h->cfg.c_in, 1ull << 30, images);   // offsets of one image in 30 bits
     ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
         auto launch = [&](auto pl) {
-            hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD>), dim3(grid), dim3(s23_cfg::NT), 0, st,
-                               images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p
-                               UBD_STAMP_ARG(COLD ? "" : "stem123"));      // the stamp indices are the strip walk's
+            ubd_dispatch_bool(!COLD && tail_rows > 0, [&](auto tail) {       // a pass without a tail runs the instance that has the strip walk alone
+                if constexpr (COLD && decltype(tail)::value) return;
+                else hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD, decltype(tail)::value>),
+                                        dim3(grid), dim3(s23_cfg::NT), 0, st,
+                                        images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p, tail_rows
+                                        UBD_STAMP_ARG(COLD ? "" : "stem123"));      // the stamp indices are the strip walk's
+            });
         };
         if constexpr (decltype(in_u8)::value == 0) { if (plain) return launch(ubd_int<1>{}); }
         launch(ubd_int<0>{});
     });
+}
+
+// the stem plan of one launch from the handle's settings; job_maps < 0: no postprocess job
+static ubd_stem_plan plan_stem_of(const ubd_handle *h, int n, int H, int W, bool inference, int job_maps)
+{
+    return ubd_plan_stem(h->fuse_stem, h->fuse_force != 0, h->cfg.fml_compatible != 0, h->num_cus, n, H, inference, job_maps >= 0, W,
+                         job_maps > 0 ? job_maps : 0, h->stem_cold_tail);
+}
+extern "C" int ubd_stem_tail_rows(const ubd_handle *h, int n, int height, int width, int job_maps)
+{
+    if (!h || h->cfg.dtype != UBD_F32 || n <= 0 || height <= 0 || width <= 0) return 0;
+    return plan_stem_of(h, n, height, width, true, job_maps).tail_rows;
 }
 
 // Runs L1..L9 + head.  acts[0..8] receive the hidden activations (L1..L9 outputs).
@@ -797,7 +814,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     const int u8 = in_dtype == UBD_IN_U8;
     float *cur = (float *)(ws + L.off_acts[0]);
     static_assert(UBD_STEM_STRIP_ROWS == s23_cfg::TH3, "stem_plan.h counts the strips the stem kernels walk");
-    const ubd_stem_plan plan = ubd_plan_stem(h->fuse_stem, h->fuse_force != 0, h->cfg.fml_compatible != 0, h->num_cus, n, H, inference, pp_job != nullptr);
+    const ubd_stem_plan plan = plan_stem_of(h, n, H, W, inference, pp_job ? pp_job->n : -1);
     UBD_REQUIRE(!plan.job_without_strips, "ubd_forward: a postprocess job needs the fused stem kernel (internal error)");
     const bool one_kernel = plan.form == UBD_STEM_FORM_STRIPS || plan.form == UBD_STEM_FORM_COLD;
     // Column layouts of a3 and L4..L8's outputs (wino6.hip, P_p): L4, L5 and L9 (dilation d = 1, 2, 1) read P_2d, where one sample load
@@ -808,12 +825,12 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
     static const int phase_lay[UBD_NUM_DIL + 1] = {2, 4, 1, 1, 1, 2, 1};
     const bool phase_major = h->wino_x6 && !h->wino6_natural && one_kernel;
     const int a3_l2p = phase_major ? 1 : 0;
-    int *ticket = (int *)(ws + L.off_tickets);                   // zeroed with the weight pack above; the strip walk resets them itself, the cold form does not touch them
+    int *ticket = (int *)(ws + L.off_tickets);                   // zeroed with the weight pack above; the strip walk resets them itself (strip tickets [0], check-out [16], tile tickets of a job pass's tail [32]), the cold form does not touch them
     if (plan.form == UBD_STEM_FORM_COLD)
         launch_stem123<true>(h, params, images, u8, cur, sf0, sf1, sf2, n, H, W, sc, sh, plan.strips * (W4 <= 16 ? 1 : 1 + (W4 - 16 + 14) / 15),
-                             ticket, nullptr, a3_l2p, st);
+                             ticket, nullptr, a3_l2p, 0, st);
     else if (plan.form == UBD_STEM_FORM_STRIPS)
-        launch_stem123<false>(h, params, images, u8, cur, sf0, sf1, sf2, n, H, W, sc, sh, plan.strips, ticket, pp_job, a3_l2p, st);
+        launch_stem123<false>(h, params, images, u8, cur, sf0, sf1, sf2, n, H, W, sc, sh, plan.strips, ticket, pp_job, a3_l2p, plan.tail_rows, st);
     else if (h->cfg.c_in == 1)
         launch_sep<1, 2>(h, images, u8, a1, sf0, params + h->off_sep_b[0], n, H, W, H2, W2, pad_s2, sc, sh, st);
     else

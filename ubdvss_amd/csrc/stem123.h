@@ -21,6 +21,9 @@
 // fp32 MFMAs: the reference side of tests/test_gpu_forward.py::test_fused_stem_path.
 // Two block barriers per tile, one 8-wave block per CU: phase B of tile t shares its barrier interval with phase 0b of tile
 // t + 1 (waves 4-7, which have no L3 row, take twice the L1 units).  Training keeps the separate kernels (it needs a1 and a2).
+// Work units: whole row strips of tiles handed out by tickets (the walk below); single cold-started tiles dealt out statically (COLD, small
+// launches); and, when a postprocess job rides along and the plan gives tail_rows > 0, both in one launch: the last tail_rows strips are
+// walked as ticketed cold tiles by whichever block runs out of strips (the tile loop is instantiated twice from one body).
 #pragma once
 #include "split3.h"
 
@@ -66,16 +69,25 @@ template <int CIN> struct s123_cfg {
 // columns apart (tile k > 0 at column 15 k covers columns 15 k + 1 .. 15 k + 15; tile 0 covers 0 .. 15 -- the image edge is its
 // padding), nine tiles for 128 columns instead of eight.  Everything else -- patch, L1, L2, L3 of a tile -- is the code of the strip
 // walk, so every output is computed by the same instructions on the same values: bit-identical (tests/test_gpu_forward.py).  Tiles
-// are dealt out statically (block b takes b, b + grid, ...): no tickets, no ring.  One 512 x 512 image: 288 tiles on 256 CUs, one
+// are dealt out statically (block b takes b, b + grid, ...): no tickets, no ring (the tail of a job pass hands the same tiles out by
+// tickets, inside the strip form: strip_pos below).  One 512 x 512 image: 288 tiles on 256 CUs, one
 // launch of ~8 us instead of three of 5.6 + 6.6 + 7.2 us.
-template <int CIN, int IN_U8, int PLAIN, bool COLD = false>
+// A tile's position; `cold`: the tile is walked cold-started (15 columns apart, no inherited column) -- a property of the TYPE, so the
+// strip walk and the cold walk are two instances of one tile loop and neither carries the other's state.
+template <bool CW> struct s123_tpos { static constexpr bool cold = CW; int tx, ty, img, ord, ls; };   // ord: ordinal of the strip in this block's sequence
+
+// TAIL: the instance a job pass with tail_rows > 0 launches.  The second instance of the tile loop costs the strip loop registers (spilled
+// VGPRs of the RGB instances: 17 -> 22 fp32 by LDS-DMA, 29 register-fed fp32, 30 uint8; grey: 17 as before; +3.8 us per pass at
+// 32 x 512 x 512 with both loops in every instance), so passes without a tail keep the kernel that has the strip walk alone.
+template <int CIN, int IN_U8, int PLAIN, bool COLD = false, bool TAIL = false>
 __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__restrict__ xin, float *__restrict__ y,
                                                                 const float *__restrict__ frag1, const float *__restrict__ bias1,
                                                                 const float *__restrict__ frag2, const float *__restrict__ bias2,
                                                                 const float *__restrict__ frag3, const float *__restrict__ bias3,
                                                                 int n, int H, int W, int H2, int W2, int H4, int W4,
                                                                 float pre_sub, float pre_div, int *__restrict__ ticket, pp_lds_args pj,
-                                                                int a3_l2p /* L3's output rows in column layout P_(2^a3_l2p) (wino6.hip) */
+                                                                int a3_l2p /* L3's output rows in column layout P_(2^a3_l2p) (wino6.hip) */,
+                                                                int tail_rows /* strip form with a job: the last tail_rows strips are walked as ticketed cold tiles (stem_plan.h) */
                                                                 UBD_STAMP_PARAM)
 {
     using C = s23_cfg;
@@ -167,9 +179,17 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     const int D = tiles_x >= 3 ? 1 : 4 - tiles_x;                                   // strips claimed ahead of the current one
     int *ring = (int *)(bt + 64);                                                   // logical strip id of the block's strip ordinal j at [j & 3]
     float *lut = bt + 64 + 4;                                                       // uint8 input: ((float)b - pre_sub) / pre_div for b = 0 .. 255, filled with the weight tables
-    struct tpos { int tx, ty, img, ord, ls; };                                      // ord: ordinal of the strip in this block's sequence
-    auto strip_pos = [&](int ord, int tx) {
-        tpos p;
+    // The tail of a job pass (tail_rows > 0): logical strips strips_end .. strips - 1 -- the last in ticket order -- are not handed out
+    // as strips.  A block whose strip tickets have run out draws TILE tickets from a second counter (ticket[32]) and walks those rows
+    // as cold tiles: ticket k is tile k % cold_kx of logical row strips_end + k / cold_kx.  The blocks that ran a postprocess job come up
+    // when everybody else is ~3 strips in, and whole strips of ~28 us then end up to a strip apart; tiles of ~3.4 us end a tile apart.
+    const int strips_end = TAIL ? strips - tail_rows : strips;                      // the strip walk's share (the host clips tail_rows: every block's D own strips are in it)
+    static_assert(!(COLD && TAIL), "the tail belongs to the strip form");
+    const int tail_tiles = TAIL ? tail_rows * cold_kx : 0;
+    using cold_c = std::bool_constant<true>;
+    auto pos_limit = [&](auto cw) { return COLD ? strips : (decltype(cw)::value ? tail_tiles : strips_end); };   // first id that is no work of that walk
+    auto strip_pos = [&](auto cw, int ord, int tx) {
+        s123_tpos<decltype(cw)::value> p;
         if constexpr (COLD) {                                                        // tile b, b + grid, ...: (image, tile row, tile of the row)
             const int ls = (int)blockIdx.x + ord * (int)gridDim.x;
             const int sidx = ubd_xcd_tile(ls < strips ? ls : strips - 1, strips);
@@ -179,19 +199,30 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
             p.img = (int)((unsigned)rowi / (unsigned)tiles_y);
             p.ord = ord; p.ls = ls;
             return p;
+        } else if constexpr (decltype(cw)::value) {                                  // ticketed cold tile of the tail: the ring holds tile tickets
+            const int tk = __builtin_amdgcn_readfirstlane(ring[ord & 3]);
+            const int tc = tk < tail_tiles ? tk : tail_tiles - 1;
+            const int rel = (int)((unsigned)tc / (unsigned)cold_kx);
+            const int sidx = ubd_xcd_tile(strips_end + rel, strips);
+            p.tx = tc - rel * cold_kx;
+            p.ty = (int)((unsigned)sidx % (unsigned)tiles_y);
+            p.img = (int)((unsigned)sidx / (unsigned)tiles_y);
+            p.ord = ord; p.ls = tk;
+            return p;
+        } else {
+            const int ls = __builtin_amdgcn_readfirstlane(ring[ord & 3]);
+            const int sidx = ubd_xcd_tile(ls < strips ? ls : strips - 1, strips);
+            p.ty = (int)((unsigned)sidx % (unsigned)tiles_y);
+            p.img = (int)((unsigned)sidx / (unsigned)tiles_y);
+            p.tx = tx; p.ord = ord; p.ls = ls;
+            return p;
         }
-        const int ls = __builtin_amdgcn_readfirstlane(ring[ord & 3]);
-        const int sidx = ubd_xcd_tile(ls < strips ? ls : strips - 1, strips);
-        p.ty = (int)((unsigned)sidx % (unsigned)tiles_y);
-        p.img = (int)((unsigned)sidx / (unsigned)tiles_y);
-        p.tx = tx; p.ord = ord; p.ls = ls;
-        return p;
     };
-    auto advance = [&](tpos p) {
-        if (!COLD && p.tx + 1 < tiles_x) { ++p.tx; return p; }
-        return strip_pos(p.ord + 1, 0);
+    auto advance = [&](auto p) {
+        if (!decltype(p)::cold && p.tx + 1 < tiles_x) { ++p.tx; return p; }
+        return strip_pos(std::bool_constant<decltype(p)::cold>{}, p.ord + 1, 0);
     };
-    auto xo3 = [&](const tpos &p) { return (COLD ? 15 : 16) * p.tx; };              // first L3 column of the tile
+    auto xo3 = [&](auto p) { return (decltype(p)::cold ? 15 : 16) * p.tx; };        // first L3 column of the tile
 
     // ---- input patch of a tile: rows 4*oy0 - 5 .. + 22, columns 4*ox0 - 3 .. + 68, raw bits into registers (fp32 pattern
     //      or zero-extended byte; 0x100 / pre_sub bits = "outside the image", exactly 0 after the preprocessing)
@@ -204,11 +235,11 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     // ~20 vector instructions per element: phase 0a was 2.5 k of the tile's 11.5 k cycles in the stamps).  Interior tiles
     // (block-uniform) load unconditionally; border tiles load from the clamped position and the elements outside the image
     // are replaced where the registers are consumed (a select next to the load would wait for it).
-    auto tile_interior = [&](tpos p) {
+    auto tile_interior = [&](auto p) {
         const int iy0 = 4 * p.ty * C::TH3 - 5, ix0 = 4 * xo3(p) - 3;
         return (iy0 >= 0) && (ix0 >= 0) && (iy0 + X::XH <= H) && (ix0 + X::XW <= W);
     };
-    auto load_x = [&](tpos p) {
+    auto load_x = [&](auto p) {
         const int iy0 = 4 * p.ty * C::TH3 - 5, fx0 = (4 * xo3(p) - 3) * CIN, WC = W * CIN;
         const unsigned char *img8 = (const unsigned char *)xin + (size_t)p.img * H * WC * (IN_U8 ? 1 : 4);   // wave-uniform
         const bool interior = tile_interior(p);                                      // block-uniform
@@ -225,7 +256,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
             if (pcf >= RWF) { pcf -= RWF; ++pr; }
         }
     };
-    auto fix_border = [&](tpos p) {                                                  // outside the image = exactly 0 after the preprocessing
+    auto fix_border = [&](auto p) {                                                  // outside the image = exactly 0 after the preprocessing
         const int iy0 = 4 * p.ty * C::TH3 - 5, fx0 = (4 * xo3(p) - 3) * CIN, WC = W * CIN;
         int pr = e0_row, pcf = e0_col;
 #pragma unroll
@@ -238,7 +269,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     };
 
     const unsigned lds_xp = ubd_lds_addr(xp);
-    auto dma_x = [&](tpos p) {                                                       // PLAIN: the patch of tile p, one 16-byte LDS-DMA piece per patch row
+    auto dma_x = [&](auto p) {                                                       // PLAIN: the patch of tile p, one 16-byte LDS-DMA piece per patch row
         const int iy0 = 4 * p.ty * C::TH3 - 5, fx0 = (4 * xo3(p) - 4) * CIN, WC = W * CIN;   // one column left of the patch: 16-byte aligned (COLD: 60 k - 4 columns)
         __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)xin + (size_t)p.img * H * WC * 4), 0,
                                                                         (int)((unsigned)H * WC * 4u), 0x00020000);
@@ -303,30 +334,35 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
         for (int j = 0; j < 3; ++j) ring[j] = had_job ? ticket_ls(t0_early + j) : (int)blockIdx.x * D + j;   // only the first D are this block's: the rest are overwritten before use
     }
     __syncthreads();
-    tpos cur = strip_pos(0, 0);
+    const auto first = strip_pos(std::bool_constant<COLD>{}, 0, 0);
     S123_BLOCK_STAMP(3);         // behind the strip's decoding (a few scalar instructions), not in front of it: with thread 0's store between the barrier and the decoding
                                  // hipcc hands dma_x's buffer descriptor to ubd_blds16 in vector registers, which the instruction does not take
-    // The counter resets itself: every block checks out through a second counter, and the last one out -- by then nobody draws
-    // tickets any more -- zeroes both for the next launch on this workspace (stream order; the host zeroes them only before
+    // The counters reset themselves: every block checks out through another counter, and the last one out -- by then nobody draws
+    // tickets any more, strips or tiles -- zeroes all three for the next launch on this workspace (stream order; the host zeroes them only before
     // the first launch on a workspace: the per-pass memset was a 5 us kernel of its own between two forward passes).
+    // A block leaves its walk with one ticket still requested (the last tile of either walk draws one and breaks out): that add must have
+    // been performed before the block's check-out add is issued, or it could land on a counter the last block out has already zeroed and
+    // the next pass would skip a strip or a tile.  Consuming its return value (the empty asm: a wait for the value, no instruction) makes
+    // that hold by construction, whatever the path of the two adds to the L2.
+    int pending = 0;                                                                 // ticket in flight (thread 0)
     auto check_out = [&]() {
         if constexpr (COLD) return;                                                  // no tickets drawn
+        asm volatile("" :: "v"(pending) : "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
             const int left = __hip_atomic_fetch_add(ticket + 16, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (left == (int)gridDim.x - 1) {
                 __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(ticket + 16, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(ticket + 32, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     };
-    if (cur.ls >= strips) { S123_BLOCK_STAMP(2); check_out(); return; }              // block-uniform: nothing left
-    tpos nx1 = advance(cur);
-    int pending = 0;                                                                 // ticket in flight (thread 0)
+    if (first.ls >= pos_limit(std::bool_constant<COLD>{}) && tail_tiles == 0) { S123_BLOCK_STAMP(2); check_out(); return; }   // block-uniform: nothing left
     // diagnostic build only (stamps.h): the phase boundaries, every wave, first 16 tiles of the block
-#define S123_STAMP(k) UBD_STAMP(it < 16, (((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k))
+#define S123_STAMP(k) UBD_STAMP(tile_stamps && it < 16, (((size_t)blockIdx.x * 8 + wid) * 16 + it) * 8 + (k))
     // ---- phase 0a of tile p (non-PLAIN): the patch, requested a phase ago into registers, goes to LDS (preprocessed)
-    auto convert_x = [&](tpos p) {
+    auto convert_x = [&](auto p) {
         const bool plain = !IN_U8 && pre_sub == 0.f && pre_div == 1.f;              // already preprocessed fp32 input: a copy
         if (!tile_interior(p)) fix_border(p);                                        // block-uniform
         int pr = e0_row, pcf = e0_col;
@@ -357,7 +393,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) tap[ky * 3 + kx] = xp[u_rd + ky * X::XS + kx * CIN];
     };
-    auto l1_finish = [&](tpos p, auto nunits, auto &tap, int k0) {                  // units k0 .. k0 + NU - 1 of the wave
+    auto l1_finish = [&](auto p, auto nunits, auto &tap, int k0) {                  // units k0 .. k0 + NU - 1 of the wave
         constexpr int NU = decltype(nunits)::value;
         const int A0y = 2 * p.ty * C::TH3 - 2, A0x = 2 * xo3(p) - 2;                 // a1 pixel of patch (0, 0)
         float dwk1[9], pwf1[2];
@@ -397,7 +433,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
             }
         }
     };
-    auto phase0b = [&](tpos p) {                                                     // the whole phase at once (first tile of a block)
+    auto phase0b = [&](auto p) {                                                     // the whole phase at once (first tile of a block)
         if (wid < 4) {                                                               // wave-uniform: waves 0-3 own two units, waves 4-7 four
             float tap[2][9];
             l1_taps(0, tap[0]); l1_taps(1, tap[1]);
@@ -414,8 +450,7 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     // ---- first tile: patch -> LDS, L1.  The LDS weight tables are filled while the patch is on its way (and not at all by a block
     // that found no strip left; after the postprocess job, which uses the same LDS).  L1's eleven per-lane values, the biases of
     // L1 / L3, the pointwise pieces of L2 / L3 and L3's depthwise table:
-    if constexpr (PLAIN) dma_x(cur); else load_x(cur);
-    {   // every thread's (up to) six table entries: all loads first, then the stores -- one memory round trip (as loops of
+    auto fill_tables = [&]() {   // every thread's (up to) six table entries: all loads first, then the stores -- one memory round trip (as loops of
         // load -> store the fills took 1.8 us of the prologue)
         static_assert(64 * 12 <= 2 * C::NT && 2 * X::PWS_U32 / 3 == 2 * C::NT && C::W3DW_FLOATS <= C::NT, "table entries per thread");
         auto w1_entry = [&](int e) {
@@ -450,145 +485,174 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
         pw_store(t, p0, p1); pw_store(t + C::NT, p2, p3);
         if (t < 64) bt[t] = v5;
         if constexpr (IN_U8) { if (t < 256) lut[t] = ((float)t - pre_sub) / pre_div; }     // the expression the conversion applied per element: same bits
-    }
-    if constexpr (PLAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else {
-        if constexpr (IN_U8) __syncthreads();                                        // the lookup table is complete
-        convert_x(cur);
-    }
-    __syncthreads();
-    S123_BLOCK_STAMP(29);
-    phase0b(cur);
-    __syncthreads();
-    S123_BLOCK_STAMP(30);
-    // Per tile t (two block barriers): [request the input patch of t + 1] -> phase A(t) -> [patch of t + 1 complete in LDS] -> barrier
-    // -> phase B(t) on waves 0-3 beside phase 0b(t + 1) (waves 4-7 take twice the units) -> barrier.  Phase 0b of the next tile
-    // touches nothing phase B reads (the inherited L2 column is moved at the start of phase A instead), so the four waves that
-    // have no L3 row do not idle through phase B.
-    for (int it = 0;; ++it) {
-        S123_STAMP(0);
-        const bool new_strip = !COLD && cur.tx == 0;                                 // block-uniform
-        if (new_strip) S123_BLOCK_STAMP(4 + cur.ord);
-        if (new_strip && threadIdx.x == 0) pending = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the raw ticket: arithmetic on it here would wait for the round trip
-        const int img = cur.img, oy0 = cur.ty * C::TH3, ox0 = xo3(cur);
-        const bool has_next = nx1.ls < strips;                                       // block-uniform
-        const int R0 = 2 * oy0 - 1, C0 = 2 * ox0 - 1;                                // L2 pixel of position (0, 0)
-        if (has_next) { if constexpr (PLAIN) dma_x(nx1); else load_x(nx1); }        // phase 0b(t) has read the patch: the next tile's may land
-        if (wid == C::NW - 1 && lane < C::LR * 6) {
-            // L2 position 0 (column 2*ox0 - 1): the previous tile's position 32, or L3's zero padding at the left image edge
-            const int row = lane / 6, ch4 = lane - row * 6;
-            f32x4 v = z4;
-            if (!COLD && cur.tx > 0) v = *(const f32x4 *)(carry_buf + (((it + 1) & 1) * C::LR + row) * C::LP + 4 * ch4);   // COLD: nobody to inherit from -- the tile's first L3 column is not stored
-            *(f32x4 *)(l2 + (row * C::LC) * C::LP + 4 * ch4) = v;
+    };
+    // The tile loop, instantiated as the strip walk and as the cold walk of the tail (CW: compile time, from the position's type).  A ticketed
+    // cold tile is a strip of one tile: it draws the ticket of the tile three ahead (as the strips of one-tile rows do), so the next
+    // tile is known -- and its patch requested -- a phase A ahead through the same four-entry ring.
+    auto walk = [&](auto cur, bool tables_needed) {
+        constexpr bool CW = decltype(cur)::cold;
+        constexpr bool tile_stamps = COLD || !CW;                                    // the tile stamps are the first walk's
+        (void)tile_stamps;
+        const int limit = pos_limit(std::bool_constant<CW>{});
+        auto nx1 = advance(cur);
+        if constexpr (PLAIN) dma_x(cur); else load_x(cur);
+        if (tables_needed) fill_tables();
+        if constexpr (PLAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else {
+            if constexpr (IN_U8) __syncthreads();                                        // the lookup table is complete
+            convert_x(cur);
         }
-        S123_STAMP(1);
+        __syncthreads();
+        if constexpr (tile_stamps) S123_BLOCK_STAMP(29);
+        phase0b(cur);
+        __syncthreads();
+        if constexpr (tile_stamps) S123_BLOCK_STAMP(30);
+        // Per tile t (two block barriers): [request the input patch of t + 1] -> phase A(t) -> [patch of t + 1 complete in LDS] -> barrier
+        // -> phase B(t) on waves 0-3 beside phase 0b(t + 1) (waves 4-7 take twice the units) -> barrier.  Phase 0b of the next tile
+        // touches nothing phase B reads (the inherited L2 column is moved at the start of phase A instead), so the four waves that
+        // have no L3 row do not idle through phase B.
+        for (int it = 0;; ++it) {
+            S123_STAMP(0);
+            const bool new_strip = COLD ? false : (CW || cur.tx == 0);                   // block-uniform; a ticketed cold tile is a strip of one
+            if (new_strip && !CW) S123_BLOCK_STAMP(4 + cur.ord);
+            if (new_strip && threadIdx.x == 0) pending = __hip_atomic_fetch_add(ticket + (CW ? 32 : 0), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the raw ticket: arithmetic on it here would wait for the round trip
+            const int img = cur.img, oy0 = cur.ty * C::TH3, ox0 = xo3(cur);
+            const bool has_next = nx1.ls < limit;                                       // block-uniform
+            const int R0 = 2 * oy0 - 1, C0 = 2 * ox0 - 1;                                // L2 pixel of position (0, 0)
+            if (has_next) { if constexpr (PLAIN) dma_x(nx1); else load_x(nx1); }        // phase 0b(t) has read the patch: the next tile's may land
+            if (wid == C::NW - 1 && lane < C::LR * 6) {
+                // L2 position 0 (column 2*ox0 - 1): the previous tile's position 32, or L3's zero padding at the left image edge
+                const int row = lane / 6, ch4 = lane - row * 6;
+                f32x4 v = z4;
+                if (!CW && cur.tx > 0) v = *(const f32x4 *)(carry_buf + (((it + 1) & 1) * C::LR + row) * C::LP + 4 * ch4);   // COLD: nobody to inherit from -- the tile's first L3 column is not stored
+                *(f32x4 *)(l2 + (row * C::LC) * C::LP + 4 * ch4) = v;
+            }
+            S123_STAMP(1);
 
-        // ---- phase A: L2 on positions (0..8, 1..32)
-        const bool mask_needed = (R0 < 0) || (R0 + C::LR > H2) || (C0 + C::LC > W2);
-        {
-            float dwv[3][6];
+            // ---- phase A: L2 on positions (0..8, 1..32)
+            const bool mask_needed = (R0 < 0) || (R0 + C::LR > H2) || (C0 + C::LC > W2);
+            {
+                float dwv[3][6];
 #pragma unroll
-            for (int o = 0; o < 3; ++o)
+                for (int o = 0; o < 3; ++o)
 #pragma unroll
-                for (int s = 0; s < 6; ++s) dwv[o][s] = 0.f;
+                    for (int s = 0; s < 6; ++s) dwv[o][s] = 0.f;
 #pragma unroll
-            for (int yy = 0; yy < 5; ++yy) {
-                if (yy < rw + 2) {                                                   // wave-uniform
-                    f32x4 v4[3];
-                    f32x2 v2[3];
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        v4[kx] = *(const f32x4 *)(a1p + ro4[kx] + yy * (C::PW * UBD_C));
-                        v2[kx] = *(const f32x2 *)(a1p + ro2[kx] + yy * (C::PW * UBD_C));
-                    }
-#pragma unroll
-                    for (int o = 0; o < 3; ++o) {
-                        const int ky = yy - o;
-                        if (ky < 0 || ky > 2) continue;
+                for (int yy = 0; yy < 5; ++yy) {
+                    if (yy < rw + 2) {                                                   // wave-uniform
+                        f32x4 v4[3];
+                        f32x2 v2[3];
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx) {
-                            const int t = ky * 3 + kx;
-                            dwv[o][0] = fmaf(v4[kx][0], dwk2[t][0], dwv[o][0]);
-                            dwv[o][1] = fmaf(v4[kx][1], dwk2[t][1], dwv[o][1]);
-                            dwv[o][2] = fmaf(v4[kx][2], dwk2[t][2], dwv[o][2]);
-                            dwv[o][3] = fmaf(v4[kx][3], dwk2[t][3], dwv[o][3]);
-                            dwv[o][4] = fmaf(v2[kx][0], dwk2[t][4], dwv[o][4]);
-                            dwv[o][5] = fmaf(v2[kx][1], dwk2[t][5], dwv[o][5]);
-                        }
-                    }
-                    if (yy >= 2) {
-                        const int o = yy - 2;
-                        f32x4 acc0 = b2A, acc1 = b2B;
-                        pw_split(pws, (f32x4){dwv[o][0], dwv[o][1], dwv[o][2], dwv[o][3]}, (f32x2){dwv[o][4], dwv[o][5]}, acc0, acc1);
-                        float cap = __builtin_inff();
-                        if (mask_needed) {
-                            const bool ok = (unsigned)(C0 + pos) < (unsigned)W2 && (unsigned)(R0 + rb + o) < (unsigned)H2;
-                            cap = ok ? cap : 0.f;                                    // L3's zero padding
+                            v4[kx] = *(const f32x4 *)(a1p + ro4[kx] + yy * (C::PW * UBD_C));
+                            v2[kx] = *(const f32x2 *)(a1p + ro2[kx] + yy * (C::PW * UBD_C));
                         }
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) { acc0[r] = ubd_relu_cap(acc0[r], cap); acc1[r] = ubd_relu_cap(acc1[r], cap); }
-                        float *dst = l2 + l2w + o * (C::LC * C::LP);
-                        *(f32x4 *)dst = acc0;
-                        if (q < 2) *(f32x4 *)(dst + 16) = acc1;
-                        if (half == 1 && i == 15) {                                  // position 32: the next tile's position 0
-                            float *cd = carry_buf + ((it & 1) * C::LR + rb + o) * C::LP + 4 * q;
-                            *(f32x4 *)cd = acc0;
-                            if (q < 2) *(f32x4 *)(cd + 16) = acc1;
+                        for (int o = 0; o < 3; ++o) {
+                            const int ky = yy - o;
+                            if (ky < 0 || ky > 2) continue;
+#pragma unroll
+                            for (int kx = 0; kx < 3; ++kx) {
+                                const int t = ky * 3 + kx;
+                                dwv[o][0] = fmaf(v4[kx][0], dwk2[t][0], dwv[o][0]);
+                                dwv[o][1] = fmaf(v4[kx][1], dwk2[t][1], dwv[o][1]);
+                                dwv[o][2] = fmaf(v4[kx][2], dwk2[t][2], dwv[o][2]);
+                                dwv[o][3] = fmaf(v4[kx][3], dwk2[t][3], dwv[o][3]);
+                                dwv[o][4] = fmaf(v2[kx][0], dwk2[t][4], dwv[o][4]);
+                                dwv[o][5] = fmaf(v2[kx][1], dwk2[t][5], dwv[o][5]);
+                            }
+                        }
+                        if (yy >= 2) {
+                            const int o = yy - 2;
+                            f32x4 acc0 = b2A, acc1 = b2B;
+                            pw_split(pws, (f32x4){dwv[o][0], dwv[o][1], dwv[o][2], dwv[o][3]}, (f32x2){dwv[o][4], dwv[o][5]}, acc0, acc1);
+                            float cap = __builtin_inff();
+                            if (mask_needed) {
+                                const bool ok = (unsigned)(C0 + pos) < (unsigned)W2 && (unsigned)(R0 + rb + o) < (unsigned)H2;
+                                cap = ok ? cap : 0.f;                                    // L3's zero padding
+                            }
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) { acc0[r] = ubd_relu_cap(acc0[r], cap); acc1[r] = ubd_relu_cap(acc1[r], cap); }
+                            float *dst = l2 + l2w + o * (C::LC * C::LP);
+                            *(f32x4 *)dst = acc0;
+                            if (q < 2) *(f32x4 *)(dst + 16) = acc1;
+                            if (half == 1 && i == 15) {                                  // position 32: the next tile's position 0
+                                float *cd = carry_buf + ((it & 1) * C::LR + rb + o) * C::LP + 4 * q;
+                                *(f32x4 *)cd = acc0;
+                                if (q < 2) *(f32x4 *)(cd + 16) = acc1;
+                            }
                         }
                     }
                 }
             }
-        }
-        S123_STAMP(2);
-        if (has_next) {
-            if constexpr (PLAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next patch has landed (requested a whole phase A ago)
-            else convert_x(nx1);
-        }
-        S123_STAMP(3);
-        __syncthreads();                                                             // L2 tile and the next input patch are complete
-        S123_STAMP(4);
+            S123_STAMP(2);
+            if (has_next) {
+                if constexpr (PLAIN) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next patch has landed (requested a whole phase A ago)
+                else convert_x(nx1);
+            }
+            S123_STAMP(3);
+            __syncthreads();                                                             // L2 tile and the next input patch are complete
+            S123_STAMP(4);
 
-        // ---- phase B (waves 0-3: L3 output row oy0 + wid) beside phase 0b of the next tile (all waves)
-        if (wid < 4) {
-            const int oy = oy0 + wid;
-            float dv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            // ---- phase B (waves 0-3: L3 output row oy0 + wid) beside phase 0b of the next tile (all waves)
+            if (wid < 4) {
+                const int oy = oy0 + wid;
+                float dv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
+                for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float *p = l2 + l2r + (ky * C::LC + kx) * C::LP;
-                    const f32x4 v4 = *(const f32x4 *)(p + 4 * q);
-                    const f32x2 v2 = *(const f32x2 *)(p + 16 + 2 * q);
-                    const float *wt = w3dw + (q * 9 + ky * 3 + kx) * 8;
-                    const f32x4 w4 = *(const f32x4 *)wt;
-                    const f32x2 w2 = *(const f32x2 *)(wt + 4);
-                    dv[0] = fmaf(v4[0], w4[0], dv[0]); dv[1] = fmaf(v4[1], w4[1], dv[1]);
-                    dv[2] = fmaf(v4[2], w4[2], dv[2]); dv[3] = fmaf(v4[3], w4[3], dv[3]);
-                    dv[4] = fmaf(v2[0], w2[0], dv[4]); dv[5] = fmaf(v2[1], w2[1], dv[5]);
-                }
-            f32x4 acc0 = *(const f32x4 *)(bt + 32 + 4 * q), acc1 = *(const f32x4 *)(bt + 48 + 4 * q);
-            pw_split(pws + X::PWS_U32, (f32x4){dv[0], dv[1], dv[2], dv[3]}, (f32x2){dv[4], dv[5]}, acc0, acc1);
-            store_tile_relu_nb(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, COLD && cur.tx > 0 && i == 0, a3_l2p);   // bias already in
-            S123_STAMP(5);
-            if (!has_next) break;
-            float tap[2][9];
-            l1_taps(0, tap[0]); l1_taps(1, tap[1]);
-            l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 0);
-        } else {
-            S123_STAMP(5);
-            if (!has_next) break;
-            float tap[2][9];
-            l1_taps(0, tap[0]); l1_taps(1, tap[1]);
-            l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 0);
-            l1_taps(2, tap[0]); l1_taps(3, tap[1]);
-            l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 2);
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const float *p = l2 + l2r + (ky * C::LC + kx) * C::LP;
+                        const f32x4 v4 = *(const f32x4 *)(p + 4 * q);
+                        const f32x2 v2 = *(const f32x2 *)(p + 16 + 2 * q);
+                        const float *wt = w3dw + (q * 9 + ky * 3 + kx) * 8;
+                        const f32x4 w4 = *(const f32x4 *)wt;
+                        const f32x2 w2 = *(const f32x2 *)(wt + 4);
+                        dv[0] = fmaf(v4[0], w4[0], dv[0]); dv[1] = fmaf(v4[1], w4[1], dv[1]);
+                        dv[2] = fmaf(v4[2], w4[2], dv[2]); dv[3] = fmaf(v4[3], w4[3], dv[3]);
+                        dv[4] = fmaf(v2[0], w2[0], dv[4]); dv[5] = fmaf(v2[1], w2[1], dv[5]);
+                    }
+                f32x4 acc0 = *(const f32x4 *)(bt + 32 + 4 * q), acc1 = *(const f32x4 *)(bt + 48 + 4 * q);
+                pw_split(pws + X::PWS_U32, (f32x4){dv[0], dv[1], dv[2], dv[3]}, (f32x2){dv[4], dv[5]}, acc0, acc1);
+                store_tile_relu_nb(y, ((size_t)img * H4 + oy) * W4, ox0, oy < H4 ? W4 : 0, lane, acc0, acc1, CW && cur.tx > 0 && i == 0, a3_l2p);   // bias already in
+                S123_STAMP(5);
+                if (!has_next) break;
+                float tap[2][9];
+                l1_taps(0, tap[0]); l1_taps(1, tap[1]);
+                l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 0);
+            } else {
+                S123_STAMP(5);
+                if (!has_next) break;
+                float tap[2][9];
+                l1_taps(0, tap[0]); l1_taps(1, tap[1]);
+                l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 0);
+                l1_taps(2, tap[0]); l1_taps(3, tap[1]);
+                l1_finish(nx1, std::integral_constant<int, 2>{}, tap, 2);
+            }
+            S123_STAMP(6);
+            if (new_strip && threadIdx.x == 0) ring[(cur.ord + (CW ? 3 : D)) & 3] = CW ? pending : ticket_ls(pending);      // visible after the barrier below and the next tile's
+            __syncthreads();                                                             // a1 patch of the next tile complete; phase B is over
+            S123_STAMP(7);
+            cur = nx1;
+            nx1 = advance(nx1);
         }
-        S123_STAMP(6);
-        if (new_strip && threadIdx.x == 0) ring[(cur.ord + D) & 3] = ticket_ls(pending);       // visible after the barrier below and the next tile's
-        __syncthreads();                                                             // a1 patch of the next tile complete; phase B is over
-        S123_STAMP(7);
-        cur = nx1;
-        nx1 = advance(nx1);
+    };
+    if (first.ls < pos_limit(std::bool_constant<COLD>{})) walk(first, true);
+    else if constexpr (TAIL) fill_tables();                                          // a block that comes up after the last strip: the tables of its cold tiles.  Here, not in the
+                                                                                     // cold walk: the weight pointers would stay live through the strip loop
+    if constexpr (TAIL) {
+        if (tail_tiles > 0) {                                                        // block-uniform: the tail of a job pass
+            __syncthreads();                                                         // every wave has decoded `first` and left phase B
+            S123_BLOCK_STAMP(31);
+            if (threadIdx.x == 0) {
+                const int t0 = __hip_atomic_fetch_add(ticket + 32, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // drawn here: drawn a tile earlier, in the last strip tile, it measured the same
+#pragma unroll
+                for (int j = 0; j < 3; ++j) ring[j] = t0 + j;
+            }
+            __syncthreads();
+            const auto ct = strip_pos(cold_c{}, 0, 0);
+            if (ct.ls < tail_tiles) walk(ct, false);
+        }
     }
     S123_BLOCK_STAMP(2);
     check_out();
