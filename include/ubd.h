@@ -138,7 +138,7 @@ int ubd_forward_postprocess(ubd_handle *h, const float *params, const void *imag
  * of all levels, which is this value for a detection-only net (one channel) and meaningless with classes: a stated deviation.
  * Arithmetic, fixed so that it can be checked bit for bit: fp32, acc = y_0; acc += y_1[...]; ...; acc += y_P[...] in level order,
  * then acc / (float)(P + 1) as one IEEE division.  Parity with the reduction order of TF's K.mean is unpinned.
- * Inference only.
+ * The same graph is trained by ubd_train_step_multiscale (training section below).
  *
  * Packed levels: levels first..P of an (n, height, width) array of pixel_bytes-byte pixels, level s being (n, height >> s,
  * width >> s), lie one after another without padding.  ubd_multiscale_levels_bytes is their total size (0 unless n, height, width,
@@ -158,11 +158,23 @@ size_t ubd_multiscale_levels_bytes(int n, int height, int width, int pixel_bytes
  *                 2^max_scale_power, k 1..UBD_MAX_CLASSES + 1
  *   out: fp32 (n, map_h, map_w, k); may be level 0 itself (level_logits), must not overlap anything else
  * Level 0 is read once (16-byte accesses where the addresses and map_w * k allow, else 8 or 4); the coarser levels come from cache.
- * Both: every violation returns non-zero with ubd_last_error() set and launches nothing; one launch, no handle, no host
+ * ubd_multiscale_fuse_backward: the adjoint of that mean -- what each level's logits receive of d loss / d mean.
+ *   dmean: fp32 (n, map_h, map_w, k)
+ *   level_dlogits: fp32, levels 0..max_scale_power packed exactly as level_logits of ubd_multiscale_fuse (level s is (n, map_h >> s,
+ *                  map_w >> s, k), ubd_multiscale_levels_bytes(n, map_h, map_w, 4 * k, 0, s - 1) bytes into the buffer); must not
+ *                  overlap dmean.  The same limits and refusals as ubd_multiscale_fuse.
+ * Arithmetic, fixed so that it can be checked bit for bit, per channel in fp32:  S_0 = dmean;
+ *   S_s[i, j] = (S_(s-1)[2i, 2j] + S_(s-1)[2i, 2j+1]) + (S_(s-1)[2i+1, 2j] + S_(s-1)[2i+1, 2j+1])   (three additions, this association);
+ *   level_dlogits_s = S_s / (float)(P + 1), one IEEE division per element; no FMA contraction, no reciprocal multiply.
+ * dmean is read exactly once (16-byte accesses where the addresses and map_w * k allow, else 8 or 4); the sums pass from level to level
+ * in LDS; no atomics, every output element is written once by one lane; nothing outside the packed levels is written.
+ * All three: every violation returns non-zero with ubd_last_error() set and launches nothing; one launch, no handle, no host
  * synchronisation, no allocation, capturable in a HIP graph. */
 int ubd_multiscale_gather(const void *images, int in_dtype, int n, int height, int width, int channels, int max_scale_power,
                           void *levels_out, size_t levels_bytes, void *stream);
 int ubd_multiscale_fuse(const float *level_logits, int n, int map_h, int map_w, int k, int max_scale_power, float *out, void *stream);
+int ubd_multiscale_fuse_backward(const float *dmean, int n, int map_h, int map_w, int k, int max_scale_power,
+                                 float *level_dlogits, void *stream);
 
 /* Replaces keras Model.predict of the model _build_multiscale_model returns (net.py:368-389).  Arguments as ubd_forward, plus
  * max_scale_power 0..4.  Enqueues on `stream`, in this order and with nothing between them that waits, allocates or reads on the
@@ -203,6 +215,26 @@ int ubd_loss(ubd_handle *h, const float *logits, const int32_t *y_true, int n, i
 int ubd_train_step(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
                    const int32_t *y_true, int n, int height, int width,
                    float *grads, float *loss, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ubd_train_step through the multi-scale graph (net.py:368-389; train.py compiles and fits whichever model build_model returns).
+ * Arguments, `grads` and `loss` as ubd_train_step, plus max_scale_power 0..4; y_true is (n, height/4, width/4) and the loss is taken
+ * on the mean map.  Enqueues on `stream`, with nothing that waits, allocates or reads on the host: the pyramid gather; for every
+ * level s = 0..P the handle's training forward (all activations kept) on level s, in the level's own region of the workspace; the
+ * fuse into a mean map; the loss once, on the mean map (`loss`, d loss / d mean); ubd_multiscale_fuse_backward; for every level the
+ * handle's backward pass for that level's shape from its own share of the gradient, into a gradient vector of its own; one kernel
+ * grads = ((g_0 + g_1) + g_2) + ... + g_P, fp32, in level order.  Forward, loss and backward are ubd_train_step's kernels for each
+ * shape and handle precision (UBD_F32 / UBD_BF16 / UBD_F16); every level packs its own weight fragments, as ubd_train_step does.
+ * max_scale_power == 0 IS ubd_train_step: the same launches, the same bytes in `grads` and `loss`, and
+ * ubd_train_multiscale_workspace_bytes == ubd_train_workspace_bytes.
+ * Refused (non-zero return, ubd_last_error names the required multiple): max_scale_power outside 0..4, a side that is not a
+ * multiple of 4 * 2^max_scale_power, a workspace smaller than ubd_train_multiscale_workspace_bytes (0 for arguments this call
+ * refuses); with max_scale_power >= 1 also images or a workspace that are not 16-byte aligned, UBD_IN_PREPACKED, and a handle whose
+ * communicator was made with UBD_COMM_FUSED: the exchange is never skipped silently -- use the explicit mode (ubd_comm_init without
+ * UBD_COMM_FUSED, ubd_allreduce_grads on `grads` after this call). */
+size_t ubd_train_multiscale_workspace_bytes(const ubd_handle *h, int in_dtype, int n, int height, int width, int max_scale_power);
+int ubd_train_step_multiscale(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
+                              const int32_t *y_true, int n, int height, int width, int max_scale_power,
+                              float *grads, float *loss, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Keras 2.2 Adam (train.py:110): lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v updated in place;
  * p -= lr_t*m/(sqrt(v)+eps); grads are multiplied by grad_scale first (1/world for DP mean). */

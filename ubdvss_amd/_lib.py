@@ -68,6 +68,7 @@ SIGNATURES = {
     "ubd_multiscale_levels_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "ubd_multiscale_gather": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "ubd_multiscale_fuse": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_multiscale_fuse_backward": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ubd_forward_multiscale_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "ubd_forward_multiscale": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ubd_pack_weights": (_i, [_vp, _vp, _vp, _sz, _vp]),
@@ -75,6 +76,8 @@ SIGNATURES = {
     "ubd_postprocess": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "ubd_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_train_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ubd_train_multiscale_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "ubd_train_step_multiscale": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ubd_adam_step": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _f, _f, _f, _f, _f, _vp]),
     "ubd_epoch_accumulator_bytes": (_sz, []),
     "ubd_epoch_accumulate": (_i, [_vp, _i, _vp, _vp]),

@@ -1,5 +1,5 @@
-// Train-step orchestration of the ubdvss hot path on gfx950: the workspace layout, ubd_train_step, and the stand-alone reduction of
-// the weight gradients' partial sums.
+// Train-step orchestration of the ubdvss hot path on gfx950: the workspace layout, ubd_train_step (and the two halves of a step that
+// the multi-scale step runs per level), and the stand-alone reduction of the weight gradients' partial sums.
 //
 // The reference gets its gradients from TensorFlow autodiff of the Keras graph
 // (model.compile / fit_generator, train.py:110-112, :176-188); here every gradient kernel is
@@ -52,7 +52,7 @@ float *rp_add(rp_queue *q, int rows, int count, float *out0, int n0, float *out1
     return part;
 }
 
-static void train_layout_compute(const ubd_handle *h, int n, int H, int W, train_layout *T)
+void ubd_train_layout_compute(const ubd_handle *h, int n, int H, int W, train_layout *T)
 {
     size_t off;
     if (h->cfg.dtype == UBD_F32) { ubd_fwd_layout_compute(h, n, H, W, 1, &T->fwd); off = T->fwd.total; }
@@ -78,8 +78,38 @@ extern "C" size_t ubd_train_workspace_bytes(const ubd_handle *h, int n, int heig
 {
     if (!h) return 0;
     train_layout T;
-    train_layout_compute(h, n, height, width, &T);
+    ubd_train_layout_compute(h, n, height, width, &T);
     return T.total;
+}
+
+// The forward half of a step over p's workspace, keeping every activation: on bf16 handles the one-launch prologue first, then the
+// handle's training forward into `logits`; fills in what the backward pass reads of it.  ubd_train_step and every level of
+// ubd_train_step_multiscale (multiscale.hip) run this and ubd_train_backward.
+int ubd_train_forward(bwd_pass &p, float *logits)
+{
+    ubd_handle *h = p.h;
+    char *ws = p.ws;
+    const train_layout &T = p.T;
+    const bool f32 = h->cfg.dtype == UBD_F32, bf16 = h->cfg.dtype == UBD_BF16;
+    int rc;
+    if (f32) {
+        rc = ubd_forward_impl(h, p.params, p.images, p.in_dtype, p.preprocessing, p.n, p.H, p.W, logits, ws, T.fwd, p.st);
+        p.a1 = ws + T.fwd.off_a1; p.a2 = ws + T.fwd.off_a2; p.wfrag = (const float *)(ws + T.fwd.off_wfrag);
+        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd.off_acts[k];
+    } else {
+        UBD_REQUIRE(p.in_dtype == UBD_IN_F32 || p.in_dtype == UBD_IN_U8, "ubd_train_step: bad in_dtype %d", p.in_dtype);
+        if (bf16) p.prologue_bf16();                               // the one-launch prologue: everything packed, gradients and loss scratch zeroed
+        rc = ubd_forward16_layout(h, p.params, p.images, bf16 ? (p.in_dtype | UBD_IN_PREPACKED) : p.in_dtype, p.preprocessing, p.n, p.H, p.W, logits, ws, T.fwd16, p.st);
+        p.a1 = ws + T.fwd16.off_a1; p.a2 = ws + T.fwd16.off_a2; p.wfrag = (const float *)(ws + T.fwd16.off_wfrag32);
+        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd16.off_acts[k];
+    }
+    return rc;
+}
+
+int ubd_train_backward(bwd_pass &p)
+{
+    const int dt = p.h->cfg.dtype;
+    return dt == UBD_BF16 ? p.backward_bf16() : dt == UBD_F32 ? p.backward_f32<float>() : p.backward_f32<_Float16>();
 }
 
 extern "C" int ubd_train_step(ubd_handle *h, const float *params, const void *images, int in_dtype, int preprocessing,
@@ -90,27 +120,15 @@ extern "C" int ubd_train_step(ubd_handle *h, const float *params, const void *im
     UBD_REQUIRE(n > 0 && height > 0 && width > 0 && (height % 4) == 0 && (width % 4) == 0, "ubd_train_step: height and width must be positive multiples of 4");
     UBD_REQUIRE(h->cfg.dtype == UBD_F32 || h->use_wino, "ubd_train_step: 16-bit activations need the Winograd data-gradient kernel (unset UBD_DILCONV=direct)");
     train_layout T;
-    train_layout_compute(h, n, height, width, &T);
+    ubd_train_layout_compute(h, n, height, width, &T);
     UBD_REQUIRE(workspace_bytes >= T.total, "ubd_train_step: workspace too small (%zu < %zu)", workspace_bytes, T.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     float *logits = (float *)(ws + T.off_logits), *dlogits = (float *)(ws + T.off_dlogits);
-    const bool f32 = h->cfg.dtype == UBD_F32, bf16 = h->cfg.dtype == UBD_BF16;
     bwd_pass p = {h, params, images, in_dtype, preprocessing, n, height, width, dlogits, grads, ws, T, st};
-    int rc;
-    if (f32) {
-        rc = ubd_forward_impl(h, params, images, in_dtype, preprocessing, n, height, width, logits, ws, T.fwd, st);
-        p.a1 = ws + T.fwd.off_a1; p.a2 = ws + T.fwd.off_a2; p.wfrag = (const float *)(ws + T.fwd.off_wfrag);
-        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd.off_acts[k];
-    } else {
-        UBD_REQUIRE(in_dtype == UBD_IN_F32 || in_dtype == UBD_IN_U8, "ubd_train_step: bad in_dtype %d", in_dtype);
-        if (bf16) p.prologue_bf16();                               // the one-launch prologue: everything packed, gradients and loss scratch zeroed
-        rc = ubd_forward16_layout(h, params, images, bf16 ? (in_dtype | UBD_IN_PREPACKED) : in_dtype, preprocessing, n, height, width, logits, ws, T.fwd16, st);
-        p.a1 = ws + T.fwd16.off_a1; p.a2 = ws + T.fwd16.off_a2; p.wfrag = (const float *)(ws + T.fwd16.off_wfrag32);
-        for (int k = 0; k < 7; ++k) p.acts[k] = ws + T.fwd16.off_acts[k];
-    }
+    int rc = ubd_train_forward(p, logits);
     if (rc) return rc;
-    rc = ubd_loss_impl(logits, h->k_out, y_true, (long)n * (height / 4) * (width / 4), loss, dlogits, ws + T.off_loss, st, h, bf16);
+    rc = ubd_loss_impl(logits, h->k_out, y_true, (long)n * (height / 4) * (width / 4), loss, dlogits, ws + T.off_loss, st, h, h->cfg.dtype == UBD_BF16);
     if (rc) return rc;
-    return bf16 ? p.backward_bf16() : f32 ? p.backward_f32<float>() : p.backward_f32<_Float16>();
+    return ubd_train_backward(p);
 }

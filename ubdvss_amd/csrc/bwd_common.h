@@ -447,3 +447,8 @@ struct bwd_pass {
     void prologue_bf16();      // in front of the forward pass
     int backward_bf16();
 };
+
+// backward.hip: the workspace layout of a step, and its two halves around the loss (forward with kept activations; backward pass)
+void ubd_train_layout_compute(const ubd_handle *h, int n, int H, int W, train_layout *T);
+int ubd_train_forward(bwd_pass &p, float *logits);
+int ubd_train_backward(bwd_pass &p);

@@ -483,11 +483,13 @@ class GraphedForward:
 class MultiscaleModel:
     """The reference's multi-scale model (net.py:368-389, ``_build_multiscale_model``): the SAME dilated net on the batch at full,
     1/2, ..., 1/2**max_scale_power size, every result brought back to the full map size by nearest upsampling, and their mean --
-    one ``ubd_forward_multiscale`` call.  Inference only.
+    one ``ubd_forward_multiscale`` call.  ``Trainer`` trains it through the same graph (``ubd_train_step_multiscale``: the loss of the
+    mean map, every level back-propagated from its share of the gradient, the weight gradients summed).
 
     Shares ``base_model``'s parameters and handle: weights, files, ``device``, ``c_in``, ``k_out``, ``n_classes``, ``net_config``,
     ``dtype`` and the postprocess are the base model's (every attribute not defined here is looked up there), so an instance goes
-    wherever a ``Model`` goes at inference time (``ModelRunner``, the evaluation, the visualisations).
+    wherever a ``Model`` goes (``ModelRunner``, the evaluation, the visualisations, ``Trainer``); ``NetManager.save_model`` /
+    ``save_inference`` write the base net's files.
 
     Image height and width must be multiples of ``4 * 2**max_scale_power`` (32 at the default 3).  The mean is taken PER CHANNEL:
     with classes the reference's ``K.mean`` over the concatenated channels of all levels is not meaningful."""

@@ -10,6 +10,10 @@ evaluated per replica (option 1).
 ``Trainer.fit`` / ``Trainer.evaluate`` are the loop itself (``fit_generator`` / ``evaluate_generator`` as train.py:176-188 uses
 them): every step adds its loss vector to a device accumulator (``ubd_epoch_accumulate``) and the host reads the two
 accumulators -- training and validation -- ONCE per epoch; nothing inside an epoch waits for the device.
+
+A ``MultiscaleModel`` is trained through the multi-scale graph (train.py fits whichever model ``build_model`` returns): its train
+steps are ``ubd_train_step_multiscale``, its validation steps the multi-scale forward, so ``loss`` and ``val_loss`` belong to one model.
+With a native communicator the multi-scale step needs the explicit mode (``attach_native_comm(model, fused=False)``).
 """
 import ctypes
 import logging
@@ -18,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, distributed, keras_metrics
-from .net import PreprocessingType
+from .net import MultiscaleModel, PreprocessingType
 
 
 class History:
@@ -73,24 +77,42 @@ class Trainer:
 
     def backward_on_device(self, images, targets):
         """images: device tensor (N,H,W,C) float32 or uint8; targets: device int32 (N,H/4,W/4[,1]).
-        Leaves gradients in self.grads and [total, det, cls, k] in self.loss."""
+        Leaves gradients in self.grads and [total, det, cls, k] in self.loss.  A ``MultiscaleModel`` is trained through its own
+        graph (``ubd_train_step_multiscale``: the loss of the mean map, the gradients of every level summed); height and width must
+        then be multiples of ``model.side_multiple``."""
         mdl = self.model
+        power = mdl.max_scale_power if isinstance(mdl, MultiscaleModel) else None
         images = images.contiguous()
         n, hh, ww, _ = images.shape
+        if power is not None:
+            if hh % mdl.side_multiple or ww % mdl.side_multiple:      # Model._input_form's wording with MultiscaleModel.predict_on_device's suffix
+                raise ValueError(f"image height and width must be multiples of {mdl.side_multiple} "
+                                 f"(4 * 2**max_scale_power, max_scale_power = {power})")
+            if images.data_ptr() % 16:                              # an offset view: the pyramid gather loads 16-byte pieces
+                images = images.clone()
         targets = targets.reshape(n, hh // 4, ww // 4).to(torch.int32).contiguous()
         if images.dtype == torch.uint8:
             in_dtype = _lib.UBD_IN_U8
             pre = _lib.UBD_PRE_MOBILENET if mdl.net_config.get_preprocessing_type() == PreprocessingType.MOBILENET_LIKE else _lib.UBD_PRE_NONE
         else:
             in_dtype, pre = _lib.UBD_IN_F32, _lib.UBD_PRE_NONE
-        nbytes = self._lib.ubd_train_workspace_bytes(mdl._h, n, hh, ww)
+        if power is None:
+            nbytes = self._lib.ubd_train_workspace_bytes(mdl._h, n, hh, ww)
+        else:
+            nbytes = self._lib.ubd_train_multiscale_workspace_bytes(mdl._h, in_dtype, n, hh, ww, power)
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=mdl.device)
         with torch.cuda.device(mdl.device):
-            _lib.check(self._lib.ubd_train_step(mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
-                                                targets.data_ptr(), n, hh, ww, self.grads.data_ptr(),
-                                                self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                mdl._stream()), "ubd_train_step")
+            if power is None:
+                _lib.check(self._lib.ubd_train_step(mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
+                                                    targets.data_ptr(), n, hh, ww, self.grads.data_ptr(),
+                                                    self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                    mdl._stream()), "ubd_train_step")
+            else:
+                _lib.check(self._lib.ubd_train_step_multiscale(mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
+                                                               targets.data_ptr(), n, hh, ww, power, self.grads.data_ptr(),
+                                                               self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                               mdl._stream()), "ubd_train_step_multiscale")
 
     def apply_gradients(self):
         native = getattr(self.model, "_native_comm", None)
