@@ -355,6 +355,40 @@ typedef struct ubd_warp_desc {
 int ubd_warp_images(const uint8_t *src, size_t src_bytes, uint8_t *dst, size_t dst_bytes, const ubd_warp_desc *descs,
                     int channels, int n, void *stream);
 
+/* --- rectified patches of the found objects ---------------------------------------
+ * The hand-over to a decoder: one upright uint8 patch of patch_h x patch_w per found object, cut out of the ORIGINAL frames
+ * where the outputs of ubd_postprocess lie.  The engine restated is Pillow's Image.transform((patch_w, patch_h), Image.QUAD,
+ * data, Image.BILINEAR), bit for bit (QUAD data as Image.__transformer forms it, quad_transform, and the bilinear filter that
+ * ubd_warp_images uses), which a host would call once per object on frames copied back first.
+ * ALL POINTERS ARE DEVICE POINTERS, the descriptors included: the call is one launch for any n and reads nothing on the host.
+ *   src + src_offsets[i] (int64 byte offsets) = image i, packed uint8 rows of src_hw[2i] x src_hw[2i+1] (rows x cols) pixels of
+ *     `channels` (1 or 3); src_bytes: size of the buffer behind src.  An image that does not lie inside [0, src_bytes) cannot be
+ *     refused on the host, because its descriptor is device memory: the kernel treats it as EMPTY, reads nothing of it, and its
+ *     patches come out all zero.
+ *   quads (n, cap, 8) int32, counts (n) int32: exactly as ubd_postprocess writes them; slots j >= min(counts[i], cap) are not read.
+ *   scales: (n, 2) doubles, xscale then yscale of image i (original / network size, ModelRunner.rescale's), or NULL: no rescale.
+ *     Corners are rescaled as utils.rescale_bbox does: X = trunc(clamp(x * xscale, -2^30, 2^30)), toward zero.
+ *   expand: > 0; 1.0 takes the corners as they are, otherwise every corner P becomes c + (P - c) * expand about the mean c of
+ *     the four (a quiet zone around the code).
+ *   patches: uint8 (n, cap, patch_h, patch_w, channels).  patch_quads: int32 (n, cap, 8) or NULL: the rescaled corners of every
+ *     object in the order NW, NE, SE, SW of its patch, before expansion.  Patches and patch_quads rows of slots that hold no
+ *     object are NOT written; nothing outside the two outputs is written.
+ * Orientation (exact, in int64): corners in clockwise order on the screen (the order is reversed when the signed area says
+ * counter-clockwise; a degenerate quad counts as clockwise), NW = corner 0 if side 0-1 is at least as long as side 1-2, else
+ * corner 1.  The patch's width therefore runs along a long side and the patch is a rotation of the object, never a mirror
+ * image; which of the two long sides is on top stays open (a half turn), decoders read both directions.  The order in which a
+ * quad's vertices are listed does not change its patch.
+ * The QUAD map sends the patch's corners to the four corners and interpolates bilinearly between them: for a rectangle (what
+ * the postprocess' minAreaRect finds) it is affine and the patch is an exact rectification; for any other quad it is Pillow's
+ * bilinear corner map, not a perspective one.  Positions outside the image give 0, as in ubd_warp_images.
+ * Limits (non-zero return, ubd_last_error, nothing launched): n >= 1, cap >= 1, patch_h and patch_w 1..1024, channels 1 or 3,
+ * expand finite and > 0, no null pointer except scales and patch_quads, n * cap * ceil(patch_h * patch_w / 1024) < 2^31.
+ * |x * xscale| beyond 2^30 is clamped; without scales the orientation is exact for |coordinates| <= 2^30.
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
+int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src_offsets, const int32_t *src_hw, int channels,
+                        const int32_t *quads, const int32_t *counts, int n, int cap, const double *scales, double expand,
+                        uint8_t *patches, int patch_h, int patch_w, int32_t *patch_quads, void *stream);
+
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one
  * operation ("stage") per image per call, for n

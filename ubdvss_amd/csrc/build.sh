@@ -23,7 +23,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp extract photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale"
 unit_flags() {   # the flags a unit needs beside $FLAGS, in every mode
   case $1 in
     api) echo "-DUBD_BUILD_ID=\"$BUILD_ID\"" ;;           # carries the fingerprint of ALL kernel sources
@@ -32,6 +32,7 @@ unit_flags() {   # the flags a unit needs beside $FLAGS, in every mode
     visualize) echo "-ffp-contract=off" ;;                # the same scan-line arithmetic (raster_fill.h) and the fp32 denorm x * 127.5 + 127.5 as numpy rounds it: no FMA contraction
     resize) echo "-ffp-contract=off" ;;                   # Pillow-exact double coefficient arithmetic of the bicubic resampler: no FMA contraction
     warp) echo "-ffp-contract=off" ;;                     # Pillow-exact double arithmetic of the generic transform and its bilinear filter: no FMA contraction
+    extract) echo "-ffp-contract=off" ;;                  # Pillow-exact double arithmetic of the QUAD transform and the bilinear filter it shares with warp: no FMA contraction
     photometric) echo "-ffp-contract=off" ;;              # fp32 Box-Muller of the noise mode, product and sum rounded separately as the numpy oracle does: no FMA contraction
     evaluate) echo "-ffp-contract=off" ;;                 # exact fp64 cross products of the evaluation geometry (collinearity tests compare them with 0): no FMA contraction
     epoch_stats) echo "-ffp-contract=off" ;;              # epoch sums acc + value * n with product and sum rounded separately, bit-equal to the host restatement: no FMA contraction

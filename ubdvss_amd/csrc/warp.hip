@@ -15,6 +15,7 @@
 //     [0, w - 1], row y clamped to [0, h - 1]; v1 = p00 + (p01 - p00) dx (the difference is an integer); on row y + 1, if
 //     0 <= y + 1 < h, v2 = p10 + (p11 - p10) dx, else v2 = v1; the result v1 + (v2 - v1) dy is truncated to uint8.
 // build.sh compiles this file with -ffp-contract=off: no product above may be fused into the following sum.
+// The second half (from the outside test on) is ubd_bilinear_sample of bilinear_sample.h, which extract.hip samples with too.
 //
 // Crops and quarter turns: EVERY mode reads its source through a signed strided view (byte offset of the view's pixel
 // (0, 0), signed byte pitch per view column and per view row, view width and height).  A crop moves the offset and shrinks
@@ -30,6 +31,7 @@
 // consecutive pixels of one image; the grid is the concatenation of the images' blocks (descriptors in the kernel
 // arguments, at most WP_MAX_IMGS per launch, the block finds its image by the first-block table).
 #include "common.h"
+#include "bilinear_sample.h"
 #include <algorithm>
 #include <cmath>
 
@@ -68,34 +70,7 @@ __device__ __forceinline__ void wp_pixel(const uint8_t *__restrict__ s, const wp
         sx = sx / q;
         sy = sy / q;
     }
-    if (!(sx >= 0.0 && sx < d.sw && sy >= 0.0 && sy < d.sh)) {
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) out[ch] = 0;
-        return;
-    }
-    sx -= 0.5;
-    sy -= 0.5;
-    const int xi = sx < 0.0 ? (int)floor(sx) : (int)sx;
-    const int yi = sy < 0.0 ? (int)floor(sy) : (int)sy;
-    const double dx = sx - xi, dy = sy - yi;
-    const int x0 = xi < 0 ? 0 : (xi < d.sw ? xi : d.sw - 1);
-    const int x1 = xi + 1 < 0 ? 0 : (xi + 1 < d.sw ? xi + 1 : d.sw - 1);
-    const int yc = yi < 0 ? 0 : (yi < d.sh ? yi : d.sh - 1);
-    const bool second = yi + 1 >= 0 && yi + 1 < d.sh;
-    const uint8_t *r0 = s + (int64_t)yc * d.yp;
-    const uint8_t *r1 = s + (int64_t)(second ? yi + 1 : yc) * d.yp;      // never dereferenced outside the view
-    const int64_t o0 = (int64_t)x0 * d.xp, o1 = (int64_t)x1 * d.xp;
-#pragma unroll
-    for (int ch = 0; ch < C; ++ch) {
-        const int p00 = r0[o0 + ch], p01 = r0[o1 + ch];
-        double v1 = p00 + (p01 - p00) * dx, v2 = v1;
-        if (second) {
-            const int p10 = r1[o0 + ch], p11 = r1[o1 + ch];
-            v2 = p10 + (p11 - p10) * dx;
-        }
-        v1 = v1 + (v2 - v1) * dy;
-        out[ch] = (uint8_t)(int)v1;
-    }
+    ubd_bilinear_sample<C>(s, d.xp, d.yp, d.sw, d.sh, sx, sy, out);      // the outside test and the filter: bilinear_sample.h
 }
 
 template <int C>

@@ -231,9 +231,26 @@ class ModelRunner:
         data_generators.py:133-140); per group (and per ``batch_size`` images of it) they are resized on the device
         (ubd_resize_images, Pillow's BICUBIC bit for bit) and fed as uint8 to ``predict_on_device`` (the NetConfig
         preprocessing fused into the first layer); the boxes are scaled back by the MetaInfo scales (``rescale``)."""
-        from .segmap_manager import SegmapManager
         if not torch.cuda.is_available():
             raise RuntimeError("ModelRunner.predict_images needs an MI355X; there is no CPU fallback")
+        return self._predict_images(model, images, batch_size, None)[0]
+
+    def predict_patches(self, model, images, patch_size=(64, 256), expand=1.0, batch_size=None):
+        """``predict_images`` plus what a decoder wants of every found object: one upright uint8 patch of ``patch_size`` =
+        (patch_h, patch_w), sampled from the ORIGINAL frame (``ubd_extract_objects``: Pillow's Image.transform(size, QUAD, data,
+        BILINEAR) bit for bit; the orientation rule and ``expand`` as in ``object_patches.extract_objects_on_device``).
+        Grouping and chain of ``predict_images``; the raw sources of a group are staged ONCE and the same device bytes feed the
+        resize and then the extraction, with the group's ``ResizeMeta`` scales.  Returns (found, patches): ``found`` is exactly
+        ``predict_images``' result, ``patches[k]`` a uint8 host array (len(found[k]), patch_h, patch_w, c) in the order of
+        ``found[k]`` (c = 3 unless every image of the group is grey).  One device-to-host copy of the patches per group."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelRunner.predict_patches needs an MI355X; there is no CPU fallback")
+        return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)))
+
+    def _predict_images(self, model, images, batch_size, patch):
+        """The loop of ``predict_images``; patch = (patch_h, patch_w, expand): also the patches of ``predict_patches``, else None."""
+        from .object_patches import _extract_staged
+        from .segmap_manager import SegmapManager, ResizeMeta
         groups = {}
         for k, im in enumerate(images):
             if isinstance(im, torch.Tensor) or isinstance(im, np.ndarray):
@@ -242,11 +259,14 @@ class ModelRunner:
                 w, h = im.size
             groups.setdefault(SegmapManager.target_size(w, h, self._net_config), []).append(k)
         found = [None] * len(images)
+        patches = [None] * len(images) if patch else None
         for idx in groups.values():
             step = len(idx) if not batch_size else int(batch_size)
             for b0 in range(0, len(idx), step):
                 part = idx[b0:b0 + step]
-                x, metas = SegmapManager.rescale_images_on_device([images[k] for k in part], self._net_config, device=model.device)
+                # the staged raw sources stay: the extraction reads the same device bytes the resize read
+                x, sizes, stage = SegmapManager._rescale_images_staged([images[k] for k in part], self._net_config, model.device)
+                metas = [ResizeMeta(w / int(x.shape[2]), h / int(x.shape[1])) for w, h in sizes]
                 _, _, quads, classes, counts = self.predict_on_device(model, x)
                 self.flush()                            # pipelined runner: this batch's postprocess now, the copies below wait for it
                 counts_h = counts.cpu().numpy()
@@ -256,7 +276,16 @@ class ModelRunner:
                 objs = self._object_lists(counts_h, quads.cpu().numpy(), classes.cpu().numpy() if classes is not None else None)
                 for k, o in zip(part, self.rescale(objs, metas)):
                     found[k] = o
-        return found
+                if patch:
+                    ph, pw, expand = patch
+                    most = int(counts_h.max())
+                    host = np.zeros((len(part), 0, ph, pw, stage[3]), np.uint8)
+                    if most:                            # the patch tensor holds the fullest list of the group, not the capacity
+                        host = _extract_staged(stage, quads[:, :most].contiguous(), counts, metas, (ph, pw), expand, False, model.device,
+                                               zero=False).cpu().numpy()
+                    for j, k in enumerate(part):
+                        patches[k] = np.array(host[j, :len(found[k])])
+        return found, patches
 
     def predict_stream(self, model, batches, rescale=False, meta_infos=None, copy_threads=8):
         """The loop of the reference's ``ModelRunner.run`` (model_runner.py:60-67: ``predict`` batch after batch) as ONE pipeline:

@@ -95,29 +95,43 @@ def _stage_host(arrays, device):
     return buf, offsets[:-1]
 
 
-def _resize_sources(srcs, new_h, new_w, dst_c, device):
-    """ubd_resize_images of every source (host arrays and device tensors alike) into one (N, new_h, new_w, dst_c) tensor."""
-    lib = _lib.load()
+def _stage_sources(srcs, device):
+    """The sources of ``_image_source`` as ONE descriptor set over device memory: host arrays are staged (``_stage_host``),
+    device tensors are read in place.  Returns (base address, int64 byte offsets from it, int32 (rows, cols) per image,
+    channels, the tensors that hold the bytes -- keep them while the descriptors are in use)."""
     src_c = 3 if any(s.shape[2] == 3 for s in srcs) else 1
     if src_c == 3:                                       # a grey source among RGB ones: convert('RGB') replicates it
         srcs = [s if s.shape[2] == 3 else (s.expand(-1, -1, 3).contiguous() if isinstance(s, torch.Tensor) else np.repeat(s, 3, axis=2))
                 for s in srcs]
     host = [k for k, s in enumerate(srcs) if not isinstance(s, torch.Tensor)]
     ptrs = [s.data_ptr() if isinstance(s, torch.Tensor) else 0 for s in srcs]
-    staged = None
+    keep = [s for s in srcs if isinstance(s, torch.Tensor)]
     if host:
         staged, offs = _stage_host([srcs[k] for k in host], device)
+        keep.append(staged)
         for k, off in zip(host, offs):
             ptrs[k] = staged.data_ptr() + int(off)
     base = min(ptrs)
     offsets = np.array([p - base for p in ptrs], np.int64)
     hw = np.array([[s.shape[0], s.shape[1]] for s in srcs], np.int32)
-    out = torch.empty((len(srcs), new_h, new_w, dst_c), dtype=torch.uint8, device=device)
+    return base, offsets, hw, src_c, keep
+
+
+def _resize_staged(stage, new_h, new_w, dst_c, device):
+    """ubd_resize_images of every staged source into one (N, new_h, new_w, dst_c) tensor."""
+    lib = _lib.load()
+    base, offsets, hw, src_c, _ = stage
+    out = torch.empty((len(offsets), new_h, new_w, dst_c), dtype=torch.uint8, device=device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     with torch.cuda.device(device):
-        _lib.check(lib.ubd_resize_images(ctypes.c_void_p(base), offsets.ctypes.data, hw.ctypes.data, src_c, len(srcs),
+        _lib.check(lib.ubd_resize_images(ctypes.c_void_p(base), offsets.ctypes.data, hw.ctypes.data, src_c, len(offsets),
                                          out.data_ptr(), new_h, new_w, dst_c, stream), "ubd_resize_images")
     return out
+
+
+def _resize_sources(srcs, new_h, new_w, dst_c, device):
+    """ubd_resize_images of every source (host arrays and device tensors alike) into one (N, new_h, new_w, dst_c) tensor."""
+    return _resize_staged(_stage_sources(srcs, device), new_h, new_w, dst_c, device)
 
 
 class SegmapManager:
@@ -335,6 +349,12 @@ class SegmapManager:
     @staticmethod
     def _rescale_images(images, net_config, device, max_side=None):
         """rescale_images_on_device -> (device tensor, [(w, h) of every source image])"""
+        return SegmapManager._rescale_images_staged(images, net_config, device, max_side)[:2]
+
+    @staticmethod
+    def _rescale_images_staged(images, net_config, device, max_side=None):
+        """_rescale_images that also hands back the staged sources (``_stage_sources``) it resized: the raw frames as they lie
+        in device memory, for a second reader (ModelRunner.predict_patches cuts the found objects out of them)."""
         if not torch.cuda.is_available():
             raise RuntimeError("SegmapManager.rescale_images_on_device needs an MI355X; there is no CPU fallback")
         device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -347,7 +367,8 @@ class SegmapManager:
             raise ValueError(f"the images do not share one target size ({sorted(targets)}); group them by "
                              "SegmapManager.target_size first (ModelRunner.predict_images does)")
         new_w, new_h = targets.pop()
-        return _resize_sources(srcs, new_h, new_w, 1 if net_config.is_grey() else 3, device), sizes
+        stage = _stage_sources(srcs, device)
+        return _resize_staged(stage, new_h, new_w, 1 if net_config.is_grey() else 3, device), sizes, stage
 
     @staticmethod
     def prepare_batch_on_device(images, markups, net_config, device=None):
