@@ -30,7 +30,7 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("cin,ncls,fml,n,hh,ww", [(3, 0, True, 2, 64, 64), (1, 3, True, 2, 64, 96), (3, 2, False, 1, 128, 64), (3, 0, True, 3, 72, 104)])
-def test_gradients_vs_autograd(cin, ncls, fml, n, hh, ww, labels=None):
+def test_gradients_vs_autograd(cin, ncls, fml, n, hh, ww, labels=None, per_tap=False):
     model, w, x, labels = _setup(cin, ncls, fml, n, hh, ww, 7 + cin + ncls, labels)
     tr = Trainer(model, Adam())
     tr.backward_on_device(torch.from_numpy(x).cuda(), torch.from_numpy(labels).cuda())
@@ -46,11 +46,17 @@ def test_gradients_vs_autograd(cin, ncls, fml, n, hh, ww, labels=None):
         assert err <= 1e-3, (nm, err)
         off += k
     assert off == g.size
+    if per_tap:      # every tap of every 3 x 3 kernel and every output-channel column of l4.k .. l9.k that exists at this shape, on its own
+        import dilated_tap_cases as taps
+        figures = taps.tap_figures(taps.Case("soak", cin, ncls, fml, n, hh, ww), l4[0], g.astype(np.float64), loss_ref, grads_ref, live_only=True)
+        bad = {nm: v for nm, v in figures.items() if nm != "loss" and not v <= 1e-3}
+        assert not bad, taps.worst(bad)
 
 
 def test_gradients_random_shape_soak():
     """fp32 train step on random small shapes (sides multiples of 4 from 32 to 128, 1-3 images, grey / RGB, with / without classes, both
-    padding rules) against the fp64 autograd oracle, same gates as above.  UBD_TRAIN_SOAK_CASES scales it (default 4)."""
+    padding rules) against the fp64 autograd oracle, same gates as above, and the same 1e-3 on every tap and output-channel column whose
+    reference is not zero (tests/dilated_tap_cases.py).  UBD_TRAIN_SOAK_CASES scales it (default 4)."""
     import os
     import soak_labels
     rng = np.random.default_rng(123)
@@ -62,7 +68,7 @@ def test_gradients_random_shape_soak():
         # big maps: labels with k = n_neg (tests/soak_labels.py): thousands of negatives make near-ties at the k-th value likely even in fp32
         lab = soak_labels.mostly_positive_maps(rng, n, hh // 4, ww // 4, ncls) if top > 33 else None
         try:
-            test_gradients_vs_autograd(cin, ncls, fml, n, hh, ww, lab)
+            test_gradients_vs_autograd(cin, ncls, fml, n, hh, ww, lab, per_tap=True)
         except AssertionError as e:
             raise AssertionError(f"case {case}: cin {cin} classes {ncls} fml {fml} {n} x {hh} x {ww}: {e}")
 
