@@ -639,6 +639,53 @@ int ubd_evaluate_pixels(const float *class_logits, int pixel_stride, int n_class
                         int8_t *mask, ubd_pixel_record *per_image,
                         void *accumulator, void *workspace, size_t workspace_bytes, void *stream);
 
+/* --- detection scores and ranked records for average precision (NO reference counterpart: the reference has no confidence of a
+ * found object and reports P / R / F1 at one operating point only) -------------------------------------------------------------
+ * ubd_score_objects: scores[i][o] = mean detection probability over the REGION of found object o of image i.
+ *   logits       : device; pixel p's detection logit is logits[p * pixel_stride] (the net's (n, h, w, K) output: pixel_stride = K)
+ *   quads, counts: device, as ubd_postprocess writes them (image coordinates)
+ *   scores       : device fp32 (n, cap); slots o >= min(counts[i], cap) are written 0.0f, an image with counts[i] > cap scores
+ *                  its first cap entries
+ * Region: exactly the map pixels ubd_build_label_maps would paint for the quad at `scale` -- the corners divided by scale and
+ * snapped outward (_proper_round, segmap_manager.py:106-133), the polygon filled by ImageDraw.polygon's rule (csrc/raster_fill.h),
+ * clipped to the map.  Stated deviation: the region is the found BOX, not the component's filled contour, so a thin diagonal
+ * object scores lower than its own pixels alone would.
+ * Arithmetic, fixed so that every parallelisation gives the same bits: p = 1.0f / (1.0f + expf(-x)) in fp32, a NaN p counts as 0;
+ * q = (uint32_t)rintf(p * 16777216.0f); the q are summed in 64-bit integers; score = (float)((double)sum / (16777216.0 *
+ * (double)count)).  An empty region (a box wholly outside the map) scores 0.0f.
+ * Non-zero return, ubd_last_error set and nothing launched (all checked before the first HIP call): a null pointer; n, map_h, map_w,
+ * cap, scale or pixel_stride below 1; map_h or map_w >= 32768; n * map_h * map_w or n * cap >= 2^31.
+ * No handle, no workspace; one launch, no host synchronisation, capturable in a HIP graph.
+ *
+ * ubd_rank_detections: COCO's greedy matching of every image at every IoU threshold at once, appended to an epoch buffer that is
+ * read once per epoch.  NOT the reference's 1-1 / 1-many / many-1 analysis (ubd_evaluate_objects): the average precision formed from
+ * these records at a threshold and the precision / recall of ubd_evaluate_objects at the same threshold need not lie on one curve.
+ *   scores, counts : device (n, cap) fp32 and (n) int32: ubd_score_objects' output and ubd_postprocess' counts
+ *   iou            : device; IoU of ground truth g and found f of image i = iou[i * image_stride_doubles + g * cap + f]: the IoU table
+ *                    ubd_evaluate_tables_layout / ubd_evaluate_polygons_tables_layout locate in the workspace of the evaluate call
+ *                    just made on the same stream (image start + (max_gt + cap + max_gt * cap) doubles, stride as reported)
+ *   gt_counts      : device (n) int32 ground-truth objects per image (rows of the image's table)
+ *   thresholds     : HOST (n_thresholds) doubles, compared as they are: a match needs iou >= t
+ * Per image: the detections 0 .. counts[i]-1 are taken in descending score, ties to the lower index, a NaN score last.  For every
+ * threshold j independently a detection takes the not-yet-taken ground truth with the largest IoU (ties to the lowest g, a NaN IoU
+ * never matches); if that IoU is >= t_j the detection is a true positive at j and the ground truth is taken, otherwise it is a false
+ * positive and nothing is taken.
+ * rank_buffer: device, ubd_rank_buffer_bytes(capacity) bytes, zeroed by the caller once.  Eight int64 slots -- [0] records written,
+ * [1] records dropped for lack of capacity, [2] ground-truth objects of the scored images, [3] images scored, [4] images flagged,
+ * [5..7] unused -- then `capacity` records {float score; uint32_t tp_mask}, bit j = true positive at threshold j.  An image with
+ * counts[i] > cap or gt_counts[i] > UBD_EVAL_MAX_GT is flagged: it writes no record and adds nothing to [2].  Records are appended in
+ * image order and inside an image in the ranked order; no atomics on global memory: the same calls give the same bytes.
+ * Limits (non-zero return, nothing launched, checked before the first HIP call): non-null pointers, n >= 1, cap 1..UBD_EVAL_MAX_FOUND,
+ * n_thresholds 1..UBD_EVAL_MAX_THRESHOLDS, image_stride_doubles >= 1, capacity >= 1.  Two launches, no host synchronisation,
+ * capturable in a HIP graph. */
+int ubd_score_objects(const float *logits, int pixel_stride, const int32_t *quads, const int32_t *counts,
+                      int n, int map_h, int map_w, int cap, int scale, float *scores, void *stream);
+size_t ubd_rank_buffer_bytes(int64_t capacity);          /* 0 for capacity < 1 */
+int ubd_rank_detections(const float *scores, const int32_t *counts, int n, int cap,
+                        const double *iou, int64_t image_stride_doubles, const int32_t *gt_counts,
+                        const double *thresholds, int n_thresholds,
+                        void *rank_buffer, int64_t capacity, void *stream);
+
 /* --- visualisations (semantic_segmentation/visualizations.py:20-151, Visualizer.compute_visualizations) -------------------
  * The four overlays of a batch in one pass over the image pixels, from what the forward pass, the postprocess and the
  * evaluation left in device memory.  Every overlay is draw_segmentation_map (:138-151), Image.composite(Image.blend(image,

@@ -100,6 +100,9 @@ SIGNATURES = {
     "ubd_evaluate_pixels_accumulator_bytes": (_sz, []),
     "ubd_evaluate_pixels_workspace_bytes": (_sz, [_i, _i, _i]),
     "ubd_evaluate_pixels": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ubd_score_objects": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ubd_rank_buffer_bytes": (_sz, [ctypes.c_int64]),
+    "ubd_rank_detections": (_i, [_vp, _vp, _i, _i, _vp, ctypes.c_int64, _vp, _vp, _i, _vp, ctypes.c_int64, _vp]),
     "ubd_visualize_images": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ubd_comm_unique_id": (_i, [_vp]),
     "ubd_comm_init": (_i, [_vp, _vp, _i, _i, _i]),

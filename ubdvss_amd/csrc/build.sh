@@ -23,7 +23,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp extract photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp extract photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale score"
 unit_flags() {   # the flags a unit needs beside $FLAGS, in every mode
   case $1 in
     api) echo "-DUBD_BUILD_ID=\"$BUILD_ID\"" ;;           # carries the fingerprint of ALL kernel sources
@@ -37,6 +37,7 @@ unit_flags() {   # the flags a unit needs beside $FLAGS, in every mode
     evaluate) echo "-ffp-contract=off" ;;                 # exact fp64 cross products of the evaluation geometry (collinearity tests compare them with 0): no FMA contraction
     epoch_stats) echo "-ffp-contract=off" ;;              # epoch sums acc + value * n with product and sum rounded separately, bit-equal to the host restatement: no FMA contraction
     multiscale) echo "-ffp-contract=off" ;;               # the multi-scale mean: fp32 adds in level order and one IEEE division, bit-equal to the numpy oracle: no FMA contraction
+    score) echo "-ffp-contract=off" ;;                    # the scan-line arithmetic of raster_fill.h and the fixed fp32 sigmoid of the object scores (add, divide, product rounded separately): no FMA contraction
     wino|wino6) echo "-fno-slp-vectorize" ;;              # no SLP packing of adjacent fp32 adds into v_pk_add_f32: beside MFMAs the packed form issues slower than two scalar adds
   esac
 }

@@ -17,22 +17,7 @@
 // One thread per map pixel; objects are tested in order and the last one that covers the pixel wins (painter's order).
 #include "common.h"
 #include "raster_fill.h"       // rq_covers: the scan-line rule, shared with visualize.hip
-
-// segmap_manager.py:96 + :106-133 on float64 markup: bbox / scale (IEEE double division, what numpy does for the reference),
-// then floor a coordinate when at least two of the four coordinates on the same axis are strictly larger, else ceil
-__device__ void rq_proper_round(const double *bbox, int scale, int *out)
-{
-    double v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = __ddiv_rn(bbox[k], (double)scale);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        int larger = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) larger += v[2 * j + (k & 1)] > v[k] ? 1 : 0;
-        out[k] = (int)(larger > 1 ? floor(v[k]) : ceil(v[k]));
-    }
-}
+#include "raster_round.h"      // rq_proper_round: the corner snapping, shared with score.hip
 
 __global__ __launch_bounds__(256) void build_label_maps_kernel(const double *__restrict__ quads, const int *__restrict__ values,
                                                                const int *__restrict__ counts, int n, int cap, int map_h,

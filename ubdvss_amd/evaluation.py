@@ -8,6 +8,10 @@ device accumulator: a validation epoch is any number of ``evaluate_batch`` calls
 The pixel classification accuracies of ``_calc_pixel_classification_correctness_mask`` (:546-575) come from
 ``ubd_evaluate_pixels`` in the same way: the class logits of the forward pass and the label maps stay on the device, the
 sums go to a second small accumulator and the correctness mask comes back as a device tensor.
+Beyond the reference (it has no counterpart): with ``average_precision=True`` every batch is also ranked by
+``ubd_rank_detections`` -- COCO's greedy matching of the detections in descending score (``Model.score_objects_on_device``) at every
+threshold, not the reference's 1-1 / 1-many / many-1 analysis -- into a device record buffer, and ``average_precision`` forms
+``ap_iou*`` and ``map`` from the one read of that buffer.
 There is no CPU path: without a GPU the entry points raise ``RuntimeError``.
 
 ``ImageResultCategories`` (:579-628) sorts an image's result into the folders the result saver writes; the overlays themselves
@@ -393,6 +397,79 @@ def unpack_accumulator(acc_host, n_thresholds, n_classes):
                 confusion=f64[8 + 10 * T:8 + 10 * T + T * C * C].reshape(T, C, C).copy())
 
 
+# ---- ranked detections and average precision (ubd_rank_detections; no reference counterpart) -----------------------------------------
+_RANK_HEADER_BYTES = 64
+_RANK_DTYPE = np.dtype([("score", np.float32), ("tp_mask", np.uint32)])
+assert _RANK_DTYPE.itemsize == 8
+
+
+def rank_buffer_bytes(capacity):
+    """bytes of an epoch's rank buffer for ``capacity`` records (0 for capacity < 1); the caller zeroes it once"""
+    return int(_lib.load().ubd_rank_buffer_bytes(int(capacity)))
+
+
+def rank_detections(scores, counts, gt_polygons, tables, thresholds, rank_buffer):
+    """One ubd_rank_detections call on the current stream, behind the ``evaluate_objects(..., return_tables=True)`` call whose
+    second result is ``tables``: COCO's greedy matching of every image's detections, in descending score, against its ground truth
+    at every threshold at once, appended to ``rank_buffer`` (device uint8 tensor of rank_buffer_bytes(capacity), zeroed once per
+    epoch).  scores (n, cap) float32 and counts (n) int32: device tensors (``Model.score_objects_on_device`` and the postprocess);
+    gt_polygons: the per-image lists the evaluate call was given (only their lengths are used), or the lengths themselves.
+    The rule is not the reference's 1-1 / 1-many / many-1 analysis.  Nothing is copied to the host."""
+    torch = _require_gpu()
+    lib = _lib.load()
+    ws, off, stride, max_gt = tables
+    n, cap = int(scores.shape[0]), int(scores.shape[1])
+    if scores.dtype != torch.float32 or counts.dtype != torch.int32 or int(counts.numel()) != n:
+        raise ValueError(f"scores must be float32 (n, cap) and counts int32 (n), got {tuple(scores.shape)} {scores.dtype}, "
+                         f"{tuple(counts.shape)} {counts.dtype}")
+    if len(gt_polygons) != n:
+        raise ValueError(f"{len(gt_polygons)} ground-truth lists for {n} images")
+    gt_counts = np.asarray([g if isinstance(g, (int, np.integer)) else len(g) for g in gt_polygons], dtype=np.int32)
+    if gt_counts.max(initial=0) > max_gt:
+        raise ValueError(f"an image has {int(gt_counts.max())} ground-truth objects, the tables hold {max_gt}")
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64))
+    capacity = (int(rank_buffer.numel()) - _RANK_HEADER_BYTES) // _RANK_DTYPE.itemsize
+    dev = scores.device
+    gt_d = torch.from_numpy(gt_counts).to(dev)
+    scores, counts = scores.contiguous(), counts.contiguous()
+    iou_ptr = ws.data_ptr() + int(off) + (max_gt + cap + max_gt * cap) * 8          # the IoU table follows the areas and the intersections
+    _lib.check(lib.ubd_rank_detections(scores.data_ptr(), counts.data_ptr(), n, cap, iou_ptr, int(stride), gt_d.data_ptr(),
+                                       thr.ctypes.data, len(thr), rank_buffer.data_ptr(), capacity,
+                                       torch.cuda.current_stream(dev).cuda_stream), "ubd_rank_detections")
+    # gt_d was allocated on this stream: the caching allocator reuses it in stream order
+
+
+def unpack_rank_buffer(host_bytes):
+    """host bytes of a rank buffer -> dict(written, dropped, n_gt, images, flagged, scores float32 (written), tp_mask uint32 (written)):
+    the records in the order they were appended; bit j of tp_mask = true positive at threshold j"""
+    raw = np.ascontiguousarray(host_bytes).view(np.uint8).reshape(-1)
+    head = raw[:_RANK_HEADER_BYTES].view(np.int64)
+    written = int(head[0])
+    rec = raw[_RANK_HEADER_BYTES:_RANK_HEADER_BYTES + written * _RANK_DTYPE.itemsize].view(_RANK_DTYPE)
+    return dict(written=written, dropped=int(head[1]), n_gt=int(head[2]), images=int(head[3]), flagged=int(head[4]),
+                scores=rec["score"].copy(), tp_mask=rec["tp_mask"].copy())
+
+
+def average_precision(scores, tp_flags, n_gt):
+    """Area under the precision envelope of a ranked detection list, in fp64: stable sort by descending score (record order on
+    ties, NaN last), cumulative true positives, recall = ctp / n_gt, precision = ctp / rank, precision made non-increasing from the
+    right, AP = sum over the ranks of (recall_k - recall_{k-1}) * precision_k.  An empty list gives 0.  n_gt < 1: ValueError."""
+    if int(n_gt) < 1:
+        raise ValueError(f"average precision needs at least one ground-truth object, got {n_gt}")
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    tp = np.asarray(tp_flags).reshape(-1).astype(bool)
+    if s.shape != tp.shape:
+        raise ValueError(f"{s.size} scores for {tp.size} flags")
+    if s.size == 0:
+        return 0.0
+    order = np.argsort(-s, kind="stable")
+    ctp = np.cumsum(tp[order].astype(np.float64))
+    recall = ctp / float(int(n_gt))
+    precision = ctp / np.arange(1, s.size + 1, dtype=np.float64)
+    envelope = np.maximum.accumulate(precision[::-1])[::-1]
+    return float(np.sum(np.diff(recall, prepend=0.0) * envelope))
+
+
 def pack_found_objects(found_boxes_per_image, found_classes_per_image=None, n_classes=0, image_offset=0):
     """host lists of integer quads -> host arrays (quads (n, cap, 8), classes (n, cap), counts (n)) int32 in the layout of the
     ubd_postprocess outputs.  ValueError for a found object that is not a convex quadrilateral with integer coordinates, or
@@ -485,13 +562,20 @@ class DatasetMetricCalculator:
     IOU_THRESHOLDS = np.arange(0.4, 1, 0.05)
     ERROR_IOU_THRESHOLD = 0.5
 
-    def __init__(self, net_config):
+    def __init__(self, net_config, average_precision=False, rank_capacity=1 << 20):
+        """average_precision: every batch is also ranked (``ubd_rank_detections``) into a device buffer of ``rank_capacity``
+        records, ``evaluate_batch`` then needs the objects' scores, and ``get_metrics`` adds the keys of ``get_average_precision``."""
         self._net_config = net_config
         self._with_cls = bool(net_config.is_classification_supported())
         self._n_classes = net_config.get_n_classes() if self._with_cls else 0
         self._acc = None
         self._pix_acc = None
         self._images = 0
+        self._with_ap = bool(average_precision)
+        self._rank_capacity = int(rank_capacity)
+        if self._with_ap and self._rank_capacity < 1:
+            raise ValueError(f"rank_capacity must be positive, got {rank_capacity}")
+        self._rank_buf = None
 
     def _accumulator(self, device):
         torch = _require_gpu()
@@ -504,7 +588,8 @@ class DatasetMetricCalculator:
         cls = [[int(o.object_type) for o in objs] for objs in gt_objects] if self._with_cls else None
         return polys, cls
 
-    def evaluate_batch(self, gt_objects, found_objects, gt_segmap=None, classification_logits=None, meta_infos=None, scales=None):
+    def evaluate_batch(self, gt_objects, found_objects, gt_segmap=None, classification_logits=None, meta_infos=None, scales=None,
+                       scores=None):
         """gt_objects: per image a list of markup records (``bbox``, ``object_type`` id).  found_objects: the same kind of
         lists (integer quads), or the device triple (quads, classes, counts) of ``ModelRunner.predict_on_device``.  scales:
         (n, 2) xscale, yscale applied to the found quads on the device (model_runner.py:140-148), or None.  Adds the batch
@@ -512,7 +597,12 @@ class DatasetMetricCalculator:
         host copy is made here -- and the pixel classification correctness mask.  With a classification config and both
         gt_segmap (the label maps, (N, h, w) or (N, h, w, 1) int32) and classification_logits (the net's output or its class
         slice, see ``evaluate_pixels``) the pixel accuracies of evaluation.py:546-575 are added to their device sums too and
-        mask is an int8 device tensor (N, h, w) of -1 / 0 / 1; in every other case mask is None."""
+        mask is an int8 device tensor (N, h, w) of -1 / 0 / 1; in every other case mask is None.  scores: with
+        ``average_precision=True`` required (ValueError without), the objects' confidences as a float32 device tensor (n, cap)
+        (``Model.score_objects_on_device``) or per image a sequence in the order of ``found_objects[i]``; the batch is then
+        ranked on the device behind its evaluation.  Without the flag ``scores`` is not looked at."""
+        if self._with_ap and scores is None:
+            raise ValueError("this calculator was made with average_precision=True: evaluate_batch needs the objects' scores")
         torch = _require_gpu()
         for i, objs in enumerate(gt_objects):
             if len(objs) == 0:
@@ -527,8 +617,15 @@ class DatasetMetricCalculator:
             quads, classes, counts = _found_to_device(boxes, fcls, dev, self._n_classes, self._images)
         if len(gt_objects) != int(quads.shape[0]):
             raise ValueError(f"{len(gt_objects)} ground-truth lists for {int(quads.shape[0])} images")
-        rec = evaluate_objects(quads, classes, counts, polys, cls, self.IOU_THRESHOLDS, self._n_classes,
-                               self._accumulator(quads.device), scales=scales, image_offset=self._images)
+        if not self._with_ap:
+            rec = evaluate_objects(quads, classes, counts, polys, cls, self.IOU_THRESHOLDS, self._n_classes,
+                                   self._accumulator(quads.device), scales=scales, image_offset=self._images)
+        else:                                           # the same call, keeping the workspace with the IoU tables for the ranking
+            rec, tables = evaluate_objects(quads, classes, counts, polys, cls, self.IOU_THRESHOLDS, self._n_classes,
+                                           self._accumulator(quads.device), scales=scales, image_offset=self._images, return_tables=True)
+            if self._rank_buf is None:
+                self._rank_buf = torch.zeros(rank_buffer_bytes(self._rank_capacity), dtype=torch.uint8, device=quads.device)
+            rank_detections(self._scores_to_device(scores, quads), counts, polys, tables, self.IOU_THRESHOLDS, self._rank_buf)
         mask = None
         if self._with_cls and gt_segmap is not None and classification_logits is not None:
             if self._pix_acc is None:
@@ -537,6 +634,47 @@ class DatasetMetricCalculator:
                                       per_image=False)
         self._images += len(gt_objects)
         return rec, mask
+
+    @staticmethod
+    def _scores_to_device(scores, quads):
+        """scores as evaluate_batch takes them -> float32 device tensor (n, cap) beside ``quads``"""
+        torch = _require_gpu()
+        n, cap = int(quads.shape[0]), int(quads.shape[1])
+        if not hasattr(scores, "data_ptr"):
+            if len(scores) != n:
+                raise ValueError(f"{len(scores)} score lists for {n} images")
+            packed = np.zeros((n, cap), dtype=np.float32)
+            for i, row in enumerate(scores):
+                row = np.asarray(row, dtype=np.float32).reshape(-1)
+                if len(row) > cap:
+                    raise ValueError(f"image {i}: {len(row)} scores for at most {cap} found objects")
+                packed[i, :len(row)] = row
+            scores = torch.from_numpy(packed)
+        if tuple(scores.shape) != (n, cap) or scores.dtype != torch.float32:
+            raise ValueError(f"scores must be float32 {(n, cap)}, got {tuple(scores.shape)} {scores.dtype}")
+        return scores.to(quads.device)
+
+    def get_average_precision(self):
+        """{"ap_iou0.40": ..., ..., "map": their mean over IOU_THRESHOLDS} after ONE read of the rank buffer.  COCO's greedy
+        matching in descending score (``ubd_rank_detections``), not the reference's analysis: an ``ap_*`` and the ``pr_*`` /
+        ``recall_*`` at the same threshold need not lie on one curve.  RuntimeError when records were dropped for lack of
+        ``rank_capacity`` or an image was not ranked."""
+        if not self._with_ap:
+            raise RuntimeError("this calculator was made without average_precision=True")
+        if self._rank_buf is None:
+            raise RuntimeError("no batch has been evaluated")
+        r = unpack_rank_buffer(self._rank_buf.cpu().numpy())
+        if r["dropped"]:
+            raise RuntimeError(f"{r['dropped']} detection record(s) were dropped: more than rank_capacity={self._rank_capacity} "
+                               "detections in the epoch; raise the capacity")
+        if r["flagged"]:
+            raise RuntimeError(f"{r['flagged']} image(s) were not ranked: more found objects than max_objects_per_image "
+                               f"(or more than {_lib.UBD_EVAL_MAX_GT} ground-truth objects); raise the capacity")
+        out = {}
+        for j, thr in enumerate(self.IOU_THRESHOLDS):
+            out["ap_iou{:.2f}".format(thr)] = average_precision(r["scores"], (r["tp_mask"] >> np.uint32(j)) & np.uint32(1), r["n_gt"])
+        out["map"] = float(np.mean([out["ap_iou{:.2f}".format(thr)] for thr in self.IOU_THRESHOLDS]))
+        return out
 
     def get_per_threshold_metrics(self):
         """The one read of the epoch: {threshold: FtMetrics} from the device sums.  Raises RuntimeError when an image was
@@ -572,6 +710,8 @@ class DatasetMetricCalculator:
             p = unpack_pixel_accumulator(self._pix_acc.cpu().numpy())
             if p["images"] > 0:
                 logs.update(pixel_logs_from_sums(p["n_correct"], p["n_total"], p["n_objects"], p["object_acc_sum"]))
+        if self._with_ap:
+            logs.update(self.get_average_precision())
         return logs
 
     @classmethod

@@ -181,12 +181,13 @@ class EvaluationCallback(SingleSplitLogCallback):
     MAX_SAVED_IMAGES = 10
 
     def __init__(self, log_dir, net_config, batch_generator, max_evaluated_images=-1,
-                 mode=SingleSplitLogCallback.ONLY_TRAIN_LOGS_MODE, save_images=False):
+                 mode=SingleSplitLogCallback.ONLY_TRAIN_LOGS_MODE, save_images=False, average_precision=False):
         SingleSplitLogCallback.__init__(self, log_dir, mode)
         available = batch_generator.get_images_per_epoch()
         self._n_evaluated_images = available if max_evaluated_images < 0 else min(available, max_evaluated_images)
         self._runner = ModelRunner(net_config, pixel_threshold=0.5)
         self._save_images = bool(save_images)
+        self._average_precision = bool(average_precision)       # opt-in: the epoch's logs gain ap_iou* and map (ModelRunner.run)
         self._batches = self._run_batches(batch_generator.generate(add_metainfo=True))
 
     @staticmethod
@@ -199,7 +200,8 @@ class EvaluationCallback(SingleSplitLogCallback):
     def on_epoch_end(self, epoch, logs=None):
         measured, pictures = {}, {}
         if self._n_evaluated_images > 0:
-            measured, pictures = self._runner.run(self.model, self._batches, self._n_evaluated_images)   # no save_dir: nothing is written there
+            measured, pictures = self._runner.run(self.model, self._batches, self._n_evaluated_images,   # no save_dir: nothing is written there
+                                                  average_precision=self._average_precision)
         # a validation callback files its own metrics under val_ so that the split rule keeps them and drops the training logs
         prefix = "" if self.is_train_log_mode() else "val_"
         merged = {prefix + name: value for name, value in measured.items()}

@@ -82,7 +82,7 @@ class ModelRunner:
         bmap, quads, classes, counts = slot["out"]
         return logits, bmap, quads, classes, counts
 
-    def evaluate_batches(self, model, batches):
+    def evaluate_batches(self, model, batches, average_precision=False):
         """The device form of the evaluation loop of ModelRunner.run (model_runner.py:60-75, :102): for every
         (images, gt_objects, meta_infos) batch the forward pass, the postprocess and the object-level evaluation
         (ubd_evaluate_objects) are enqueued on the current stream -- the found objects never leave the device; the quads are
@@ -91,9 +91,12 @@ class ModelRunner:
         images: (N,H,W,C) numpy array or device tensor; gt_objects: per image a list of markup records.
         A batch may also be (images, gt_objects, meta_infos, gt_segmap), gt_segmap the label maps (N,h,w) or (N,h,w,1) int32
         (device tensor or numpy, e.g. of ``prepare_batch_on_device``): on a classification config the logits the forward pass
-        just wrote are then scored in place (ubd_evaluate_pixels) and the two pixel accuracies join the result."""
+        just wrote are then scored in place (ubd_evaluate_pixels) and the two pixel accuracies join the result.
+        average_precision=True: every found object is also given its confidence (ubd_score_objects) and every batch is ranked
+        behind its evaluation (ubd_rank_detections), all on the device; the result gains ``ap_iou*`` and ``map``
+        (DatasetMetricCalculator.get_average_precision) and keeps every other key and value."""
         from .evaluation import DatasetMetricCalculator
-        evaluator = DatasetMetricCalculator(self._net_config)
+        evaluator = DatasetMetricCalculator(self._net_config, average_precision=average_precision)
         for batch in batches:
             images, gt_objects, meta_infos = batch[:3]
             gt_segmap = batch[3] if len(batch) > 3 else None
@@ -108,12 +111,13 @@ class ModelRunner:
             logits, _, quads, classes, counts = self.predict_on_device(model, images)
             self.flush()                                # pipelined runner: this batch's postprocess before its evaluation
             scales = None if meta_infos is None else np.array([[m.xscale, m.yscale] for m in meta_infos], dtype=np.float64)
+            scores = model.score_objects_on_device(logits, quads, counts, self._net_config.get_scale()) if average_precision else None
             evaluator.evaluate_batch(gt_objects, (quads, classes, counts), gt_segmap=gt_segmap,
                                      classification_logits=logits if gt_segmap is not None else None,
-                                     meta_infos=meta_infos, scales=scales)
+                                     meta_infos=meta_infos, scales=scales, scores=scores)
         return evaluator.get_metrics()
 
-    def run(self, model, batches, n_images, save_dir=None, save_visualizations=False, rng=None):
+    def run(self, model, batches, n_images, save_dir=None, save_visualizations=False, rng=None, average_precision=False):
         """The contract of the reference's ModelRunner.run (model_runner.py:40-103): metrics, saved results and visualisations
         of up to ``n_images`` images.  ``batches``: an iterable of batches in the form ``evaluate_batches`` takes,
         (images, gt_objects, meta_infos[, gt_segmap]); it is read until ``n_images`` images have been seen (or it ends).  Per
@@ -125,11 +129,13 @@ class ModelRunner:
         are required: they name the files) the ground truth and the found objects of every image are written as CSV and, with
         ``save_visualizations``, every image is saved into the folders of its ImageResultCategories at ERROR_IOU_THRESHOLD.
         Returns (scalar_logs, visualizations): the dict of ``get_metrics`` and the last batch drawn as {'gt' (with label maps),
-        'seg_map', 'postprocessed'[, 'classification_gt']} of device uint8 tensors (N, H, W, 3) ({} when none was drawn)."""
+        'seg_map', 'postprocessed'[, 'classification_gt']} of device uint8 tensors (N, H, W, 3) ({} when none was drawn).
+        average_precision=True: the objects are scored and every batch ranked on the device as in ``evaluate_batches``; the
+        logs gain ``ap_iou*`` and ``map``."""
         from .evaluation import DatasetMetricCalculator, ImageResultCategories
         from .result_saver import ResultSaver
         from .visualizations import Visualizer
-        metrics = DatasetMetricCalculator(self._net_config)
+        metrics = DatasetMetricCalculator(self._net_config, average_precision=average_precision)
         writer = ResultSaver(save_dir, save_visualizations)
         generator = np.random.default_rng() if rng is None else rng
         preview_index = int(generator.integers(0, n_images))       # drawn even when save_dir makes it unused: one draw per run
@@ -148,9 +154,10 @@ class ModelRunner:
             logits, binary_map, quads, classes, counts = self.predict_on_device(model, x)
             self.flush()                                # pipelined runner: this batch's postprocess before its evaluation
             scales = None if meta_infos is None else np.array([[m.xscale, m.yscale] for m in meta_infos], dtype=np.float64)
+            scores = model.score_objects_on_device(logits, quads, counts, self._net_config.get_scale()) if average_precision else None
             records, mask = metrics.evaluate_batch(gt_objects, (quads, classes, counts), gt_segmap=labels,
                                                    classification_logits=logits if labels is not None else None,
-                                                   meta_infos=meta_infos, scales=scales)
+                                                   meta_infos=meta_infos, scales=scales, scores=scores)
             folders = None
             if save_dir:
                 writer.save_gt_and_prediction(gt_objects, self.rescale(self._found_lists(quads, classes, counts), meta_infos), meta_infos)
@@ -198,6 +205,30 @@ class ModelRunner:
         self.flush()                                    # pipelined runner: this batch's postprocess now, the copies below wait for it
         return self._assemble(counts.cpu().numpy(), quads.cpu().numpy(), classes.cpu().numpy() if classes is not None else None,
                               logits.cpu().numpy(), bmap.cpu().numpy(), rescale, meta_infos)
+
+    def predict_scored(self, model, images, rescale=False, meta_infos=None, min_score=None):
+        """``predict`` plus the confidence of every found object (no reference counterpart): returns ``predict``'s triple and
+        ``scores``, per image a float32 array in the order of ``found_objects[i]`` -- the mean detection probability over the
+        map pixels of the found box (``Model.score_objects_on_device``; the box, not the component's filled contour).  The scores
+        travel beside the markup records, not inside them.  ``min_score``: objects (and scores) below it are dropped, on the host.
+        A pipelined runner is flushed before the objects are scored."""
+        assert not rescale or (meta_infos is not None and len(images) == len(meta_infos))
+        x = np.asarray(images)
+        if x.dtype != np.uint8:
+            x = x.astype(np.float32, copy=False)
+        xt = torch.from_numpy(np.ascontiguousarray(x)).to(model.device)
+        logits, bmap, quads, classes, counts = self.predict_on_device(model, xt)
+        self.flush()                                    # pipelined runner: this batch's postprocess before its objects are scored
+        scores_h = model.score_objects_on_device(logits, quads, counts, self._net_config.get_scale()).cpu().numpy()
+        counts_h = counts.cpu().numpy()
+        det, cls_logits, found = self._assemble(counts_h, quads.cpu().numpy(), classes.cpu().numpy() if classes is not None else None,
+                                                logits.cpu().numpy(), bmap.cpu().numpy(), rescale, meta_infos)
+        scores = [np.array(scores_h[i, :int(counts_h[i])]) for i in range(len(counts_h))]
+        if min_score is not None:
+            keep = [s >= min_score for s in scores]
+            found = [[o for o, k in zip(objs, kept) if k] for objs, kept in zip(found, keep)]
+            scores = [s[k] for s, k in zip(scores, keep)]
+        return det, cls_logits, found, scores
 
     def _assemble(self, counts_h, quads_h, classes_h, logits_h, bmap_h, rescale, meta_infos, copy=False):
         """Host arrays -> the reference's return triple (model_runner.py:121-138).  copy: the arrays are reused staging buffers."""

@@ -440,6 +440,28 @@ class Model:
                 ws.data_ptr(), ws.numel(), self._stream()), "ubd_postprocess")
         return bmap, quads, classes, counts
 
+    def score_objects_on_device(self, logits, quads, counts, scale, out=None):
+        """Confidence of every found object (``ubd_score_objects``; no reference counterpart): the mean detection probability over
+        the map pixels ``ubd_build_label_maps`` would paint for the object's quad at ``scale``.  logits: fp32 (N,h,w,K) device tensor
+        of the forward pass; quads (N,cap,8) / counts (N): as ``postprocess_on_device`` returns them.  Returns an fp32 device tensor
+        (N,cap), 0.0 behind a list's end.  One launch on the current torch stream; ``out`` may hold a preallocated result."""
+        if logits.dtype != torch.float32 or logits.dim() != 4:
+            raise ValueError(f"logits must be a float32 (N,h,w,K) tensor, got {tuple(logits.shape)} {logits.dtype}")
+        logits = logits.contiguous()
+        n, mh, mw, k = (int(v) for v in logits.shape)
+        if quads.dtype != torch.int32 or counts.dtype != torch.int32 or quads.dim() != 3 or int(quads.shape[0]) != n or int(quads.shape[2]) != 8 \
+                or int(counts.numel()) != n:
+            raise ValueError(f"quads must be int32 ({n},cap,8) and counts int32 ({n}), got {tuple(quads.shape)} {quads.dtype}, "
+                             f"{tuple(counts.shape)} {counts.dtype}")
+        cap = int(quads.shape[1])
+        quads, counts = quads.contiguous(), counts.contiguous()
+        if out is None:
+            out = torch.empty((n, cap), dtype=torch.float32, device=logits.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ubd_score_objects(logits.data_ptr(), k, quads.data_ptr(), counts.data_ptr(), n, mh, mw, cap, int(scale),
+                                                   out.data_ptr(), self._stream()), "ubd_score_objects")
+        return out
+
 
 class GraphedForward:
     """``Model.predict_on_device`` of one fixed shape, captured once into a HIP graph and replayed: one host call instead of seven
