@@ -1,6 +1,7 @@
-"""A/B of the two forward forms of the Winograd dilated layer in ONE process: products on the fp32 MFMA (wino.hip, UBD_DILCONV=wino32)
-against three-way bf16 split products on the bf16 MFMA (wino6.hip, the default).  UBD_DILCONV is read when a handle is created, so the
-two models are created under different settings.  Prints, per layer, the error of each form against an fp64 convolution on the host
+"""Three-way comparison of the forward forms of the Winograd dilated layer in ONE process: products on the fp32 MFMA (wino.hip,
+UBD_DILCONV=wino32), three-way bf16 split products on the bf16 MFMA (wino6.hip, UBD_DILCONV=split3) and two-piece fp16 split products
+under per-row scales on the fp16 MFMA (wino6.hip, the default).  UBD_DILCONV is read when a handle is created, so the three models are
+created under different settings.  Prints, per layer, the error of each form against an fp64 convolution on the host
 (relative to max |y|) and the time per launch at 32 x 128 x 128 x 24 (HIP events around 300 back-to-back launches)."""
 import ctypes
 import os
@@ -33,7 +34,9 @@ def layer(mws, k, x, y):
 
 
 A = make("wino32")
+S = make("split3")
 B = make("")
+FORMS = (("fp32-MFMA", A), ("bf16x6", S), ("f16x3", B))
 os.environ.pop("UBD_DILCONV", None)
 dil = [1, 2, 4, 8, 16, 1]
 # ---- accuracy against fp64 on the host (2 x 72 x 100: ragged against every tile size)
@@ -49,26 +52,27 @@ for scale in (1.0, 255.0):
         off += 5208
         ref = torch.relu(torch.nn.functional.conv2d(torch.from_numpy(xs.astype(np.float64)).permute(0, 3, 1, 2), wk, bk, padding=dil[k], dilation=dil[k])).permute(0, 2, 3, 1).numpy()
         out = []
-        for mws in (A, B):
+        for _, mws in FORMS:
             y = torch.empty_like(x)
             layer(mws, k, x, y)
             torch.cuda.synchronize()
             out.append(np.abs(y.cpu().numpy().astype(np.float64) - ref).max() / np.abs(ref).max())
-        print(f"scale {scale:5.0f} layer {k} d {dil[k]:2d}: rel err fp32-MFMA {out[0]:.2e}  bf16x6 {out[1]:.2e}", flush=True)
-# bit-exact homogeneity: f(2x) = 2 f(x) with zero biases is not available here (biases are in the params); compare A and B directly instead
+        print(f"scale {scale:5.0f} layer {k} d {dil[k]:2d}: rel err fp32-MFMA {out[0]:.2e}  bf16x6 {out[1]:.2e}  f16x3 {out[2]:.2e}", flush=True)
+# bit-exact homogeneity: f(2x) = 2 f(x) with zero biases is not available here (biases are in the params); compare the forms directly instead
 x = torch.rand((32, 128, 128, 24), device="cuda") - 0.3
-ya, yb = torch.empty_like(x), torch.empty_like(x)
+ya, ys, yb = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
 for k in range(6):
-    layer(A, k, x, ya); layer(B, k, x, yb)
+    layer(A, k, x, ya); layer(S, k, x, ys); layer(B, k, x, yb)
     torch.cuda.synchronize()
-    print(f"layer {k}: max |fp32-MFMA - bf16x6| = {(ya - yb).abs().max().item():.3e} (max |y| {ya.abs().max().item():.3f})", flush=True)
+    print(f"layer {k}: max |fp32-MFMA - bf16x6| = {(ya - ys).abs().max().item():.3e}  |fp32-MFMA - f16x3| = {(ya - yb).abs().max().item():.3e}  "
+          f"|bf16x6 - f16x3| = {(ys - yb).abs().max().item():.3e} (max |y| {ya.abs().max().item():.3f})", flush=True)
 # ---- timing
 n = int(os.environ.get("N", 32))
 x = torch.rand((n, 128, 128, 24), device="cuda") - 0.3
 y = torch.empty_like(x)
 for _ in range(600): layer(B, 2, x, y)
 for rep in range(2):
-    for name, mws in (("fp32-MFMA", A), ("bf16x6", B)):
+    for name, mws in FORMS:
         res = []
         for k in range(6):
             for _ in range(30): layer(mws, k, x, y)
@@ -81,7 +85,7 @@ for rep in range(2):
         print(f"{name:10s} us per layer {res}  mean {sum(res) / 6:.2f}", flush=True)
 # ---- whole forward pass
 xin = torch.rand((32, 512, 512, 3), device="cuda")
-for name, m in (("fp32-MFMA", A[0]), ("bf16x6", B[0])):
+for name, m in ((name, mws[0]) for name, mws in FORMS):
     for _ in range(200): m.predict_on_device(xin)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -44,7 +44,8 @@ struct ubd_handle {
     int fuse_stem;            // UBD_STEM_*: the inference stem, with fuse_force the input of ubd_plan_stem (stem_plan.h, where both are defined)
     int use_wino;             // 1: Winograd F(2x2,3x3) dilated layers (default), 0: direct implicit GEMM (UBD_DILCONV=direct)
     int loss_chain;           // UBD_LOSS=chain: the loss as its five dependent launches (the batch-global mode's form) instead of the one-launch kernel (diagnostics / tests)
-    int wino_x6;              // forward Winograd products as three-way bf16 split products on the bf16 MFMA (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
+    int wino_x6;              // forward Winograd products as split products on the 16-bit MFMAs (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
+    int wino6_split3;         // UBD_DILCONV=split3: wino6.hip's products as three bf16 pieces, six MFMAs per product (the form before the two-piece fp16 split; the reference side of its tests), 0 (default): two fp16 pieces under power-of-two scales per tile row and per layer, three MFMAs
     int wino6_natural;        // UBD_WINO6_LAYOUT=natural: the fp32 inference pass keeps every activation in the natural column order (wino6.hip), no phase-major layouts between the layers (the reference side of the bit-identity tests)
 };
 
@@ -214,9 +215,11 @@ template <typename F> static inline void ubd_dispatch_input(int c_in, bool u8, F
 #define UBD_SEP_DW_FLOATS (9 * 6 * 64)           // per-lane depthwise taps per separable layer
 #define UBD_WINO_FRAG_FLOATS (16 * 6 * 64 * 2)   // Winograd-domain weights per dilated layer (wino.hip)
 #define UBD_FWD_DIRECT_FLOATS (3 * (UBD_SEP_FRAG_FLOATS + UBD_SEP_DW_FLOATS) + UBD_NUM_DIL * UBD_DIL_FRAG_FLOATS)
-#define UBD_WINO6_FRAG_U32 (16 * 2 * 3 * 64 * 4)  // the same weights as three bf16 pieces per value (wino6.hip): [xi 16][nt 2][piece 3][lane 64] x 4 dwords
+#define UBD_WINO6_FRAG_U32 (16 * 2 * 2 * 64 * 4)  // the same weights as two fp16 pieces per value (wino6.hip): [xi 16][nt 2][piece 2][lane 64] x 4 dwords = 64 KiB
+#define UBD_WINO6_FRAG3_U32 (16 * 2 * 3 * 64 * 4) // ... as three bf16 pieces per value (UBD_DILCONV=split3): [xi 16][nt 2][piece 3][lane 64] x 4 dwords = 96 KiB
+#define UBD_WINO6_SLOT_U32 UBD_WINO6_FRAG3_U32    // a layer's slot in the workspace holds either form; in the fp16 form dword UBD_WINO6_FRAG_U32 of the slot is 1 / t, the inverse of the layer's weight scale (float)
 #define UBD_FWD_WINO6_OFF (UBD_FWD_DIRECT_FLOATS + UBD_NUM_DIL * UBD_WINO_FRAG_FLOATS)      // in floats (= dwords) from the start of the packed weights
-#define UBD_FWD_FRAG_FLOATS (UBD_FWD_WINO6_OFF + UBD_NUM_DIL * UBD_WINO6_FRAG_U32)
+#define UBD_FWD_FRAG_FLOATS (UBD_FWD_WINO6_OFF + UBD_NUM_DIL * UBD_WINO6_SLOT_U32)
 
 struct ubd_fwd_layout {
     size_t off_tickets;   // int32 [64]: strip ticket counter of the one-kernel inference stem (zeroed per pass)

@@ -691,7 +691,7 @@ static void launch_dil(const ubd_handle *h, const float *params, const float *wf
                        int n, int H4, int W4, hipStream_t st, int lay_in = 1, int lay_out = 1)
 {
     if (h->wino_x6) {
-        ubd_launch_dilconv_wino6(h, 0, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
+        ubd_launch_dilconv_wino6(h, 0, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_SLOT_U32, params + h->off_dil_b[k],
                                  UBD_DILATIONS[k], in, out, n, H4, W4, st, nullptr, lay_in, lay_out);
         return;
     }
@@ -853,7 +853,7 @@ int ubd_forward_impl(ubd_handle *h, const float *params, const void *images, int
         float *nxt = (float *)(ws + L.off_acts[k + 1]);
         if (fuse_head && k == UBD_NUM_DIL - 1) {
             if (h->wino_x6)
-                ubd_launch_dilconv_wino6(h, 2, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_FRAG_U32, params + h->off_dil_b[k],
+                ubd_launch_dilconv_wino6(h, 2, (const unsigned *)(wfrag + UBD_FWD_WINO6_OFF) + (size_t)k * UBD_WINO6_SLOT_U32, params + h->off_dil_b[k],
                                          UBD_DILATIONS[k], cur, logits, n, H4, W4, st, params + h->off_head_k, phase_major ? phase_lay[k] : 1, 1);
             else
                 ubd_launch_dilconv_wino(h, 2, wfrag + UBD_FWD_DIRECT_FLOATS + (size_t)k * UBD_WINO_FRAG_FLOATS, params + h->off_dil_b[k], UBD_F32,

@@ -1,29 +1,50 @@
 // Dense dilated 3x3 convolution 24 -> 24, fp32 in / fp32 out, as Winograd F(2x2, 3x3) on the dilation sub-grids with the 16
-// transform-domain GEMMs computed as EXACT THREE-WAY bf16 SPLIT PRODUCTS on v_mfma_f32_16x16x32_bf16 (fp32 accumulate).
+// transform-domain GEMMs computed as SPLIT PRODUCTS on the 16-bit MFMAs (fp32 accumulate): by default two fp16 pieces per value
+// under power-of-two scales on v_mfma_f32_16x16x32_f16, three MFMAs per product; with UBD_DILCONV=split3 three bf16 pieces on
+// v_mfma_f32_16x16x32_bf16, six MFMAs per product (the form of rounds 6..14, the reference side of tests/test_gpu_wino6_f16.py).
 //
 // Reference semantics: conv_bn(dilation_rate=d) (semantic_segmentation/net.py:298-304): 'same' zero padding d per side,
 // cross-correlation, + bias + ReLU (and, for the last layer of an inference pass with one output channel, the 1x1 head of
 // net.py:308-311 in the epilogue).  Same tiling, addressing and transforms as wino.hip (the fp32-MFMA form, kept for the data
 // gradient and as the reference side of the bit-level tests); what changes is the arithmetic of the products.
 //
-// Why: the fp32 MFMA (v_mfma_f32_16x16x4_f32) runs at the fp32 VECTOR rate -- 32 cycles of its SIMD per instruction, 192 per
-// group of 16 tiles -- and the fp32 vector work of the transforms does not overlap with it (times add: DESIGN.md 5.1a), which
-// left the layer at 36 us for 32 x 128 x 128 maps.  The bf16 MFMA of the same shape class takes 16 cycles for EIGHT times the
-// K, holds the vector issue port for 8 of them only, and fp32 vector instructions run beside it.
-// How, without giving up fp32 results: every fp32 value v is the EXACT sum of three bf16 values obtained by truncation,
+// Why 16-bit MFMAs: the fp32 MFMA (v_mfma_f32_16x16x4_f32) runs at the fp32 VECTOR rate -- 32 cycles of its SIMD per
+// instruction, 192 per group of 16 tiles -- and the fp32 vector work of the transforms does not overlap with it (times add:
+// DESIGN.md 5.1a), which left the layer at 36 us for 32 x 128 x 128 maps.  A 16-bit MFMA of the same shape class takes 16 cycles
+// for EIGHT times the K, holds the vector issue port for 8 of them only, and fp32 vector instructions run beside it.  K = 24
+// input channels fit ONE K = 32 step, so a (transform point, N tile) costs one MFMA per piece product.
+//
+// Three bf16 pieces (F16 = false): every fp32 value v is the EXACT sum of three bf16 values obtained by truncation,
 //     v = v1 + v2 + v3,   v1 = hi16(v),  v2 = hi16(v - v1),  v3 = hi16(v - v1 - v2)       (8 + 8 + 8 = 24 significand bits),
-// so a product of two fp32 values is the sum of nine bf16 x bf16 products (each exact in fp32).  The six with i + j <= 4 are
-// kept (v1u1, v1u2, v2u1, v1u3, v3u1, v2u2); the three dropped ones are <= 2^-24 of the product -- the size of the rounding
-// of an fp32 multiply.  K = 24 input channels fit ONE K = 32 step, so a (transform point, N tile) costs 6 bf16 MFMAs where the
-// fp32 form cost 6 fp32 MFMAs: 16 x 2 x 6 x 16 = 3072 matrix-pipe cycles per group instead of 6144.  The six products are
-// chained into one accumulator from the smallest term to the largest so that the big term is rounded once.
-// The weights U = G g G^T are split once, at pack time; the transformed samples V = B^T D B are split on the vector ALU
-// (v_and / v_sub / v_perm: 5.5 instructions per value) beside the MFMAs.  Scaling the input by a power of two scales every
-// piece by it: f(2x) = 2 f(x) stays bit-exact.
+// and the six piece products with i + j <= 4 are kept (the three dropped ones are <= 2^-24 of the product): 192 MFMAs per group,
+// 96 KiB of weight pieces, 5.5 vector instructions per sample value for the split (v_and / v_sub / v_perm).  bf16 has fp32's
+// exponent range, so no scale is needed.  The layer was bound by the SIMD's shared issue port (matrix pipe busy 44 % of the
+// launch, vector ALU 66 %, either 94 %: profiles/r06_experiment_notes.txt A.4), so instructions had to go.
+//
+// Two fp16 pieces (F16 = true, the default): fp16 carries 11 significand bits, two pieces 22,
+//     h1 = f16(x),  h2 = f16(x - h1)   both rounded to NEAREST (truncation costs 4x the error: tools/sim_f16_split.py),
+// and THREE piece products are kept, chained from the smallest to the largest so that the big term is rounded once:
+// h2 g1, then h1 g2, then h1 g1 (the dropped h2 g2 is <= 2^-22 of the product's bound).  96 MFMAs per group, 64 KiB of weight
+// pieces (4 ds_read_b128 per point instead of 6), 3 vector instructions per value for the split (v_cvt_pk_f16_f32,
+// v_cvt_f32_f16, v_sub) plus one for the scale.  fp16's narrow exponent range is handled EXACTLY by power-of-two scales
+// (split2h.h):
+//   * weights: one scale t per layer, max |U| t in [2^12, 2^13), applied at pack time; 1 / t rides behind the fragments;
+//   * samples: one scale s per TILE and TRANSFORM ROW a, from the largest |T| of the row's 4 x 24 values T = (B^T D)[a] (the four
+//     lanes i, i + 16, i + 32, i + 48 hold a tile's channel quarters: v_max3 in the lane, two v_permlane swaps across);
+//     |V| <= 2 max |T| and max |T| s in [2^13, 2^14), so |V s| < 2^15.  Per row, not per tile, because only three of a tile's
+//     four sample rows are live at a time, and a row's own scale is the tighter one.  The scale never looks at another tile, so
+//     results do not depend on which tiles share a wave (tests/test_gpu_wino6_layout.py: bit-identity of the groupings);
+//   * a lane's four accumulators are four output channels of the lane's own tile, so unscaling is lane-local: the output
+//     transform along a adds Z / (s t) into Y with one fma per term, which replaces the add (the product is exact).
+// Scales are powers of two and commute with every rounding: f(2^k x) = 2^k f(x) stays bit-exact, an all-zero kernel gives
+// relu(bias) exactly, and a small image beside a large one, or a small region of a map, keeps its own 22 bits.
+// Measured (profiles/r15_wino6_f16_notes.txt): error against fp64 <= 2.0e-7 of max |y| per layer (three pieces 1.8e-7, fp32
+// MFMA 2.5e-7).
 #include "common.h"
 #include "split3.h"
+#include "split2h.h"
 
-// U fragments of one layer: [xi = a*4+b (16)][nt (2)][piece (3)][lane (64)] x 4 dwords (8 bf16 k-slots of the lane's k-group)
+// U fragments of one layer, three-piece form: [xi = a*4+b (16)][nt (2)][piece (3)][lane (64)] x 4 dwords (8 bf16 k-slots of the lane's k-group)
 //   lane = (m = lane & 15 : output channel co = m + 16 nt, zero rows for co >= 24;  q = lane >> 4 : k-group)
 //   k-slot e of group q holds input channel ci = e < 4 ? 4q + e : 16 + 2q + (e - 4) for e < 6, zero for e = 6, 7
 //   (the same channel-to-lane map as the sample registers of the kernel: the input transform stays lane-local)
@@ -61,11 +82,69 @@ __global__ void pack_wino6_kernel(const float *__restrict__ params, unsigned *__
     }
 }
 
+// The fp16 form: U fragments [xi (16)][nt (2)][piece (2)][lane (64)] x 4 dwords (8 fp16 k-slots, the lane and slot maps above) of
+// U t, where t is ONE power of two per layer with max |U| t in [2^12, 2^13) (split2h.h: the small piece of the largest weights
+// then sits 11 binades above fp16's subnormals; t = 1 for an all-zero kernel), and 1 / t behind the fragments, at dword
+// UBD_WINO6_FRAG_U32 of the layer's slot.  Four blocks per layer; each finds the layer's max |U| itself (9216 values, nine per thread).
+#define W6_PACK_BLOCKS 4
+__device__ __forceinline__ float wino6_u(const float *wk, int ta, int tb, int ci, int co)
+{
+    const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
+    float v = 0.f;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx)
+            v += G[ta][ky] * G[tb][kx] * wk[((ky * 3 + kx) * UBD_C + ci) * UBD_C + co];
+    return v;
+}
+__global__ __launch_bounds__(1024) void pack_wino6h_kernel(const float *__restrict__ params, unsigned *__restrict__ out, wino6_pack_args a)
+{
+    __shared__ unsigned s_max;
+    const int L = blockIdx.x / W6_PACK_BLOCKS, part = blockIdx.x % W6_PACK_BLOCKS;
+    const float *wk = params + a.off_dil_k[L];
+    if (threadIdx.x == 0) s_max = 0u;
+    __syncthreads();
+    unsigned mx = 0u;
+    for (int j = threadIdx.x; j < 16 * UBD_C * UBD_C; j += blockDim.x) {
+        const int co = j % UBD_C, ci = (j / UBD_C) % UBD_C, xi = j / (UBD_C * UBD_C);
+        const unsigned b = split2h_bits(wino6_u(wk, xi >> 2, xi & 3, ci, co)) & 0x7fffffffu;
+        mx = b > mx ? b : mx;
+    }
+    atomicMax(&s_max, mx);                                 // LDS: non-negative floats order as their bit patterns
+    __syncthreads();
+    unsigned t_bits, inv_bits;
+    split2h_scale(s_max, SPLIT2H_WEIGHT_TOP, SPLIT2H_WEIGHT_LO, t_bits, inv_bits);
+    const float t = split2h_float(t_bits);
+    unsigned *slot = out + (size_t)L * UBD_WINO6_SLOT_U32;
+    if (part == 0 && threadIdx.x == 0) slot[UBD_WINO6_FRAG_U32] = inv_bits;
+    const int per_block = 16 * 2 * 64 / W6_PACK_BLOCKS;
+    for (int k = threadIdx.x; k < per_block; k += blockDim.x) {
+        const int idx = part * per_block + k;              // (xi * 2 + nt) * 64 + lane
+        const int lane = idx & 63, nt = (idx >> 6) & 1, xi = idx >> 7;
+        const int q = lane >> 4, co = (lane & 15) + 16 * nt;
+        unsigned p[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        if (co < UBD_C) {
+            for (int e = 0; e < 6; ++e) {
+                const int ci = e < 4 ? 4 * q + e : 16 + 2 * q + (e - 4);
+                float g1, g2;
+                split2h_pieces(wino6_u(wk, xi >> 2, xi & 3, ci, co) * t, g1, g2);
+                const int sh = (e & 1) ? 16 : 0;          // even slot: low half of the dword
+                p[0][e >> 1] |= split2h_f16_bits(g1) << sh;
+                p[1][e >> 1] |= split2h_f16_bits(g2) << sh;
+            }
+        }
+        unsigned *o = slot + ((size_t)(idx >> 6) * 2 * 64 + lane) * 4;
+#pragma unroll
+        for (int pc = 0; pc < 2; ++pc)
+            *(u32x4 *)(o + pc * 64 * 4) = (u32x4){p[pc][0], p[pc][1], p[pc][2], p[pc][3]};
+    }
+}
+
 void ubd_launch_pack_wino6(const ubd_handle *h, const float *params, unsigned *out, hipStream_t st)
 {
     wino6_pack_args a;
     for (int k = 0; k < UBD_NUM_DIL; ++k) a.off_dil_k[k] = h->off_dil_k[k];
-    hipLaunchKernelGGL(pack_wino6_kernel, dim3(48), dim3(256), 0, st, params, out, a);
+    if (h->wino6_split3) hipLaunchKernelGGL(pack_wino6_kernel, dim3(48), dim3(256), 0, st, params, out, a);
+    else hipLaunchKernelGGL(pack_wino6h_kernel, dim3(UBD_NUM_DIL * W6_PACK_BLOCKS), dim3(1024), 0, st, params, out, a);
 }
 
 // All arithmetic below is plain C++ on vector types (no inline asm):
@@ -119,12 +198,15 @@ struct w6addr {
 
 // EPI 0: y = relu(conv + bias);  EPI 2: logits = head(relu(conv + bias)) (one output channel; y is never written)
 // LAY: false = natural input and output (layout terms compiled out), true = the layouts of G.phase / G.l2po
-template <int EPI, bool LAY>
+// F16: true = two fp16 pieces under per-row scales, 3 MFMAs per product (the default); false = three bf16 pieces, 6 MFMAs (UBD_DILCONV=split3)
+template <int EPI, bool LAY, bool F16 = true>
 __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const float *__restrict__ x, float *__restrict__ y,
                                                                      const unsigned *__restrict__ ufrag,
                                                                      const float *__restrict__ bias, w6geom G, const float *__restrict__ head UBD_STAMP_PARAM)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_u[UBD_WINO6_FRAG_U32];       // 96 KiB
+    constexpr int NPC = F16 ? 2 : 3;                                                 // pieces per weight
+    constexpr int FRAG_U32 = F16 ? UBD_WINO6_FRAG_U32 : UBD_WINO6_FRAG3_U32;
+    __shared__ __attribute__((aligned(16))) unsigned s_u[FRAG_U32];                  // 64 KiB (96 KiB for three pieces)
     const int lane = threadIdx.x & 63;
     const int i = lane & 15, q = lane >> 4;
     const int h = G.h, w = G.w, d = G.d, log2d = G.log2d, dm1 = G.d - 1;
@@ -141,6 +223,8 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
         if (q < 2) hB = *(const f32x4 *)(head + 16 + 4 * q);
         hbias = head[UBD_C];            // wave-uniform: one scalar load
     }
+    [[maybe_unused]] float inv_t = 1.f;           // 1 / (the layer's weight scale): wave-uniform, behind the fragments (pack_wino6h_kernel)
+    if constexpr (F16) inv_t = __builtin_bit_cast(float, ufrag[UBD_WINO6_FRAG_U32]);
     // XCD-aware split (see dilconv_f32_kernel)
     const int xcd = blockIdx.x & 7;
     const int nblk_x = (gridDim.x + 7 - xcd) >> 3;
@@ -223,15 +307,16 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
     load_row(D, A, 0);
     load_row(D, A, 2);
     load_row(D, A, 1);
-    // U (96 KiB) to LDS by LDS-DMA: 96 pieces of 1 KiB, 12 per wave, handed out in ROUNDS (round r, wave w -> piece 8 r + w), so that the
-    // pieces of the first transform points are the first to land: pieces 0..23 (points 0..3, the first transform row) are rounds 0..2.
-    // The block starts computing behind THOSE (barrier A); the other nine rounds land under the first row of the first group and are
-    // awaited once, before point 4's weights are read (barrier B; waves without a group wait there too, then leave).  The copy used to
-    // stand in front of every launch whole: ~3.5 us of a 33 us launch, x 6 launches per pass.
+    // U (64 KiB; 96 KiB for three pieces) to LDS by LDS-DMA: 64 (96) pieces of 1 KiB, 8 (12) per wave, handed out in ROUNDS (round r,
+    // wave w -> piece 8 r + w), so that the pieces of the first transform points are the first to land: pieces 0..15 (0..23) (points
+    // 0..3, the first transform row) are rounds 0..1 (0..2).  The block starts computing behind THOSE (barrier A); the other six (nine)
+    // rounds land under the first row of the first group and are awaited once, before point 4's weights are read (barrier B; waves
+    // without a group wait there too, then leave).  The copy used to stand in front of every launch whole: ~3.5 us of a 33 us launch,
+    // x 6 launches per pass.
     // (asm form: outside hipcc's bookkeeping -- its own waits for the sample rows can only over-wait, the DMAs being younger.)
-    constexpr int PER_WAVE = UBD_WINO6_FRAG_U32 * 4 / 1024 / W6_WAVES;          // 12
-    constexpr int EARLY_ROUNDS = 4 * 6 / W6_WAVES;                                // 3: the 24 pieces of points 0..3
-    static_assert(PER_WAVE - EARLY_ROUNDS == 9, "the counted wait below is written for nine late rounds");
+    constexpr int PER_WAVE = FRAG_U32 * 4 / 1024 / W6_WAVES;                      // 8 (12)
+    constexpr int EARLY_ROUNDS = 4 * 2 * NPC / W6_WAVES;                          // 2 (3): the 16 (24) pieces of points 0..3
+    static_assert(PER_WAVE - EARLY_ROUNDS == (F16 ? 6 : 9), "the counted wait below is written for six (nine) late rounds");
     {
         const unsigned lds_u = ubd_lds_addr(s_u);
 #pragma unroll
@@ -240,7 +325,9 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
             ubd_glds16_sbase((const char *)ufrag + (size_t)piece * 1024, (unsigned)lane * 16u, lds_u + (unsigned)piece * 1024u);
         }
     }
-    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");          // the sample rows (older) and this wave's rounds 0..2 have landed
+    // the sample rows (older) and this wave's early rounds have landed
+    if constexpr (F16) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
     __builtin_amdgcn_s_barrier();                             // A: points 0..3 of the weights are in LDS
     WSTAMP(true, 1);
     if (g >= g_end || wave_in_block >= G.wpb) {
@@ -251,7 +338,8 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
     bool weights_pending = true;                              // wave-uniform: barrier B is still owed (first group only)
     [[maybe_unused]] int gcount = 0;
     const u32x4 *su4 = (const u32x4 *)s_u + lane;
-    // Schedule of one transform point xi = 4a + b (16 per group, fully unrolled):
+    // Schedule of one transform point xi = 4a + b (16 per group, fully unrolled), written for the three-piece form; the fp16 form follows it with
+    // 4 weight reads, one split of six values into two quads and 6 MFMAs:
     //   1. request the point's weights (6 ds_read_b128: 2 N tiles x 3 pieces);
     //   2. split the lane's six values of V[a][b] into three bf16 pieces (12 v_and + 6 v_pk_add + 9 v_perm; hides the LDS latency);
     //   3. 12 MFMAs, the two N tiles' chains alternating (no back-to-back dependent pair), with the vector work that does not
@@ -262,6 +350,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
         f32x4 Z0[2], Z1[2];    // output transform along b of the current row a
         f32x4 V4[4];           // V[a][b], channels 4q .. 4q+3
         f32x2 V2[4];           //          channels 16+2q, 17+2q
+        [[maybe_unused]] float inv_s[4];      // F16: 1 / (scale of transform row a x weight scale) of this lane's tile
         // V[a] = (B^T D)[a] B from the sample rows that row a needs
         auto make_v = [&](int a) {
             f32x4 T4[4];
@@ -273,6 +362,31 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                 else if (a == 2) { T4[b] = D.v4[2][b] - D.v4[1][b]; T2[b] = D.v2[2][b] - D.v2[1][b]; }
                 else { T4[b] = D.v4[1][b] - D.v4[3][b]; T2[b] = D.v2[1][b] - D.v2[3][b]; }
             }
+            if constexpr (F16) {
+                // The scale of transform row a of this lane's TILE: from the largest |T| over the row's 4 x 24 values, which four lanes
+                // hold (i, i + 16, i + 32, i + 48: the channel quarters, all k of one accumulation).  |V| <= 2 max |T|, so |V s| < 2^15.
+                // A row's scale, not the tile's: the tile's fourth sample row is not here before row 3 (three of four are live), and a
+                // row's own scale is the tighter one.  It depends on this tile's samples only -- never on the group -- so the result
+                // does not depend on which tiles share a wave (the layouts' bit-identity), and it is a power of two.
+                float mx = 0.f;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    mx = fmaxf(fmaxf(fabsf(T4[b][0]), fabsf(T4[b][1])), mx);
+                    mx = fmaxf(fmaxf(fabsf(T4[b][2]), fabsf(T4[b][3])), mx);
+                    mx = fmaxf(fmaxf(fabsf(T2[b][0]), fabsf(T2[b][1])), mx);
+                }
+                unsigned mb = __builtin_bit_cast(unsigned, mx);          // non-negative floats order as their bit patterns
+                const u32x2 h16 = __builtin_amdgcn_permlane16_swap(mb, mb, false, false);      // {rows 0 0 2 2, rows 1 1 3 3} of mb
+                mb = h16[0] > h16[1] ? h16[0] : h16[1];
+                const u32x2 h32 = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);      // {halves 0 0, halves 1 1}
+                mb = h32[0] > h32[1] ? h32[0] : h32[1];
+                unsigned s_bits, inv_bits;
+                split2h_scale(mb, SPLIT2H_SAMPLE_TOP, SPLIT2H_SAMPLE_LO, s_bits, inv_bits);
+                const float s = __builtin_bit_cast(float, s_bits);
+                inv_s[a] = __builtin_bit_cast(float, inv_bits) * inv_t;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) { T4[b] *= s; T2[b] *= s; }          // exact
+            }
             V4[0] = T4[0] - T4[2]; V4[1] = T4[1] + T4[2]; V4[2] = T4[2] - T4[1]; V4[3] = T4[1] - T4[3];
             V2[0] = T2[0] - T2[2]; V2[1] = T2[1] + T2[2]; V2[2] = T2[2] - T2[1]; V2[3] = T2[1] - T2[3];
         };
@@ -283,7 +397,20 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                 if (b == 0) Z0[nt] = m[nt];
                 else if (b == 1) { Z0[nt] += m[nt]; Z1[nt] = m[nt]; }
                 else if (b == 2) { Z0[nt] += m[nt]; Z1[nt] -= m[nt]; }
-                else {
+                else if constexpr (F16) {
+                    // the row's products carry its scale and the layer's: Z / (s t) is exact, so each sum below rounds once, as the plain sums do
+                    Z1[nt] -= m[nt];
+                    const float iv = inv_s[a];
+                    f32x4 &y00 = Y[0][0][nt], &y01 = Y[0][1][nt], &y10 = Y[1][0][nt], &y11 = Y[1][1][nt];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float z0 = Z0[nt][r], z1 = Z1[nt][r];
+                        if (a == 0) { y00[r] = z0 * iv; y01[r] = z1 * iv; }
+                        else if (a == 1) { y00[r] = fmaf(z0, iv, y00[r]); y01[r] = fmaf(z1, iv, y01[r]); y10[r] = z0 * iv; y11[r] = z1 * iv; }
+                        else if (a == 2) { y00[r] = fmaf(z0, iv, y00[r]); y01[r] = fmaf(z1, iv, y01[r]); y10[r] = fmaf(-z0, iv, y10[r]); y11[r] = fmaf(-z1, iv, y11[r]); }
+                        else { y10[r] = fmaf(-z0, iv, y10[r]); y11[r] = fmaf(-z1, iv, y11[r]); }
+                    }
+                } else {
                     Z1[nt] -= m[nt];
                     if (a == 0) { Y[0][0][nt] = Z0[nt]; Y[0][1][nt] = Z1[nt]; }
                     else if (a == 1) { Y[0][0][nt] += Z0[nt]; Y[0][1][nt] += Z1[nt]; Y[1][0][nt] = Z0[nt]; Y[1][1][nt] = Z1[nt]; }
@@ -296,6 +423,59 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
         // Software pipeline over the 16 points: the MFMA phase of point xi carries, two vector instructions behind each MFMA (the part
         // of an MFMA's 16 cycles in which the vector issue port is free), the truncation residuals of point xi + 1; the tail of the
         // phase requests the weights of xi + 1, packs its three operand quads, and transforms the accumulators of xi.
+        if constexpr (F16) {
+        // The fp16 form of the same pipeline: per point 4 weight reads, 6 MFMAs (per N tile h2 g1, then h1 g2, then h1 g1: small terms
+        // first, the big term rounded once) and, behind the MFMAs, the split of point xi + 1 into its two operand quads
+        // (3 v_cvt_pk_f16_f32 + 6 v_cvt_f32_f16 + 6 v_sub_f32 + 3 v_cvt_pk_f16_f32 for six values: 3 per value, and with the scaling of
+        // T in make_v 4).
+        u32x4 U[2][2];
+        u32x4 P1, P2, N1, N2;
+        auto load_u = [&](int xi) {
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                for (int pc = 0; pc < 2; ++pc) U[nt][pc] = su4[((xi * 2 + nt) * 2 + pc) * 64];
+        };
+        load_u(0);
+        split2h_6(V4[0], V2[0], P1, P2);
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) {
+            const int a = xi >> 2, b = xi & 3;
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 m[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+            m[0] = mfma16h(U[0][0], P2, m[0]); m[1] = mfma16h(U[1][0], P2, m[1]);
+            m[0] = mfma16h(U[0][1], P1, m[0]); m[1] = mfma16h(U[1][1], P1, m[1]);
+            m[0] = mfma16h(U[0][0], P1, m[0]); m[1] = mfma16h(U[1][0], P1, m[1]);
+            // in the MFMAs' shadows: the pieces of the next point of this row (b < 3: V[b + 1] is there; the next row's V does not exist yet)
+            if (b < 3) split2h_6(V4[b + 1], V2[b + 1], N1, N2);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);      // three vector instructions behind it
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (xi == 3 && weights_pending) {                 // first group of the launch: the rest of the weight copy (rounds 2..7)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();                 // B
+                weights_pending = false;
+            }
+            if (xi < 15) load_u(xi + 1);
+            if (b == 3 && a < 3) {
+                make_v(a + 1);
+                if (a == 1) load_row(D, A, 3);               // sample row 2 is dead (rows 1 and 3 make row 3)
+                if (a == 2) {
+                    const int gn = g + stride;               // as in the three-piece form below
+                    set_addr(An, gn < g_last ? gn : g_last);
+                    load_row(D, An, 0);
+                    load_row(D, An, 2);
+                }
+                split2h_6(V4[0], V2[0], N1, N2);
+            }
+            if (xi < 15) { P1 = N1; P2 = N2; }
+            consume(a, b, m);
+            WSTAMP(gcount == 1 && (xi & 3) == 3, 2 + (xi >> 2));
+        }
+        } else {
         u32x4 U[2][3];
         u32x4 P1, P2, P3;
         f32x4 r4, t4;
@@ -353,6 +533,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
             consume(a, b, m);
             WSTAMP(gcount == 1 && (xi & 3) == 3, 2 + (xi >> 2));
         }
+        }
         // Row 1 of the NEXT group is requested here, BEFORE this group's stores: the vector-memory counter retires in issue order, so a
         // load issued after the stores is only known to have landed once the stores have been acknowledged -- the wait for row 1 (three
         // points into the next group) then ended with the stores' round trip to L2, ~1 us later than the load itself (the kernel ran
@@ -403,7 +584,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
 
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
-// frag: this layer's UBD_WINO6_FRAG_U32 packed dwords; epi 0 / 2 as in ubd_launch_dilconv_wino
+// frag: this layer's slot of packed dwords (UBD_WINO6_SLOT_U32; which form it holds follows h->wino6_split3, as in the pack); epi 0 / 2 as in ubd_launch_dilconv_wino
 // lay_in / lay_out: column layout periods of the input and output rows (powers of two, 1: natural; lay_in is 1 or 2 * dilation)
 void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag, const float *bias, int dilation,
                               const float *in, float *out, int n, int H4, int W4, hipStream_t st, const float *head,
@@ -423,7 +604,7 @@ void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag
     // ... / 16 and D <= 2^12 for every supported shape (tensor bytes <= 2^30); D = 1 needs the identity
     G.magic_gx = groups_x == 1 ? 0u : (unsigned)(0xFFFFFFFFul / (unsigned long)groups_x + 1ul);
     G.magic_hr = half_rows == 1 ? 0u : (unsigned)(0xFFFFFFFFul / (unsigned long)half_rows + 1ul);
-    // 96 KiB of LDS: one 8-wave block per CU.  A launch with fewer than eight groups per CU (one 512 x 512 image: 256 groups) lets only
+    // 64 KiB of LDS (96 KiB for three pieces) and 198-255 registers: one 8-wave block per CU.  A launch with fewer than eight groups per CU (one 512 x 512 image: 256 groups) lets only
     // `wpb` waves of a block take groups, so that the groups spread over all CUs instead of filling 32 of them (batch-1 latency,
     // predict.py:73-78: 10.2 -> 7 us per layer); the other waves still copy their share of the weights and leave.
     int wpb = (int)((groups + h->num_cus - 1) / h->num_cus);
@@ -433,12 +614,15 @@ void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag
     int grid = ubd_grid_for(groups, h->num_cus, wpb, 1);
     grid = (grid + 7) / 8 * 8;
     const bool lay = lay_in != 1 || lay_out != 1;
-    if (epi == 2 && lay)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<2, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
-    else if (epi == 2)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<2, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
-    else if (lay)
-        hipLaunchKernelGGL((dilconv_wino6_kernel<0, true>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
-    else
-        hipLaunchKernelGGL((dilconv_wino6_kernel<0, false>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
+    ubd_dispatch_bool(h->wino6_split3 == 0, [&](auto f16_tag) {
+        constexpr bool F16 = decltype(f16_tag)::value;
+        if (epi == 2 && lay)
+            hipLaunchKernelGGL((dilconv_wino6_kernel<2, true, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
+        else if (epi == 2)
+            hipLaunchKernelGGL((dilconv_wino6_kernel<2, false, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
+        else if (lay)
+            hipLaunchKernelGGL((dilconv_wino6_kernel<0, true, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
+        else
+            hipLaunchKernelGGL((dilconv_wino6_kernel<0, false, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
+    });
 }
