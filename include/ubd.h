@@ -389,6 +389,57 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
                         const int32_t *quads, const int32_t *counts, int n, int cap, const double *scales, double expand,
                         uint8_t *patches, int patch_h, int patch_w, int32_t *patch_quads, void *stream);
 
+/* --- decoding of the object patches: EAN-13 / UPC-A / EAN-8 ------------------------
+ * The stage behind ubd_extract_objects: the digits of the retail symbol in every patch, read where the patches lie, so that
+ * 64 bytes per object cross to the host instead of the patch.  One family, defined by the public EAN/UPC tables: EAN-13, UPC-A
+ * (an EAN-13 whose first digit is 0) and EAN-8; `symbologies` is a mask so that other families can join behind the same
+ * entry point.  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy restatement
+ * tests/decode_oracle.py is matched bit for bit.
+ *   patches (n, cap, patch_h, patch_w, channels) uint8 and counts (n) int32: DEVICE pointers, exactly as ubd_extract_objects
+ *     writes and reads them; slots j >= min(counts[i], cap) are not read and their result rows are NOT written.
+ *   params: HOST pointer, read before the call returns.
+ *   results: DEVICE int32 (n, cap, 16): [0] symbology: 0 none, 13 or 8; [1] votes; [2] direction mask: bit 0 read left to
+ *     right, bit 1 read right to left (the patch is the half-turned one); [3..15] the digits, an EAN-8 fills eight and the rest
+ *     is -1.  For "none" every digit is -1 and votes and mask are 0.
+ * Per patch:
+ *   luma: the byte (1 channel) or (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (3 channels: Pillow's convert('L')).
+ *   scan lines k = 0..S-1: centre row r_k = ((2k + 1) * patch_h) / (2S); p[x] = the luma sum over the rows [r_k - b, r_k + b]
+ *     clipped to the patch, m = the number of those rows.
+ *   local threshold: lo[x], hi[x] = min, max of p over [x - R, x + R] clipped to the line; d[x] = 2 p[x] - lo[x] - hi[x];
+ *     where hi[x] - lo[x] < C * m, d[x] = max(d[x], 1).  A pixel is dark iff d[x] < 0.
+ *   edges: between x and x + 1 wherever the darkness differs, in 1/256 pixel: e = 256 x + (256 |d[x]|) / (|d[x]| + |d[x+1]|),
+ *     light-to-dark or dark-to-light.  Reading right to left is DEFINED on the mirrored list e'_j = 256 (patch_w - 1) - e_(E-1-j)
+ *     with the polarities swapped, not on a second pass over the pixels.
+ *   candidates: a light-to-dark edge i with the next 59 runs (EAN-13, 95 modules) or 43 runs (EAN-8, 67 modules) behind it;
+ *     St = e[i + runs] - e[i].  The light run q before edge i and the one after the last run must each satisfy
+ *     modules * q >= QZ * St; where that neighbouring edge is missing (the patch border) the test passes.  Every run w of the
+ *     start guard (3 runs), the centre guard (5 runs) and the end guard (3 runs) must satisfy (2 * modules * w + St) / (2 St) == 1.
+ *   characters: 4 runs w0..w3 of sum S4, edge to similar edge: E1 = (14 (w0 + w1) + S4) / (2 S4), E2 = (14 (w1 + w2) + S4) / (2 S4),
+ *     both in 2..5; of the patterns n0..n3 of the allowed sets with n0 + n1 == E1 and n1 + n2 == E2 the one with the least
+ *     |7 (w0 + w2) - S4 (n0 + n2)|; a tie rejects the candidate.  Set L, run widths in scan order for the digits 0..9:
+ *     3211 2221 2122 1411 1132 1231 1114 1312 1213 3112; set R the same widths; set G those of L reversed.
+ *     EAN-13: six left characters of {L, G}, whose parity word gives the first digit (0..9: LLLLLL LLGLGG LLGGLG LLGGGL LGLLGG
+ *     LGGLLG LGGGLL LGLGLG LGLGGL LGGLGL; any other word rejects), then six of {R}.  EAN-8: four of {L}, four of {R}.
+ *   checksums: EAN-13 (10 - (d0 + d2 + .. + d10 + 3 (d1 + d3 + .. + d11)) % 10) % 10 == d12;
+ *     EAN-8 (10 - (3 (d0 + d2 + d4 + d6) + d1 + d3 + d5) % 10) % 10 == d7.
+ *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
+ *     (symbology, digits).  The payload with the most votes wins, its mask is the OR of the directions that voted for it; fewer
+ *     than min_votes, or another payload with as many votes: none.
+ * Limits (non-zero return, ubd_last_error begins with "ubd_decode_patches", nothing launched, nothing written): no null
+ * pointer, n >= 1, cap >= 1, n * cap < 2^31, patch_w 32..1024, patch_h 1..1024, channels 1 or 3, and the ranges below.
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
+typedef struct ubd_decode_params {
+    int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8; at least one */
+    int32_t scan_rows;               /* S, 1..32        default 8  */
+    int32_t band;                    /* b, 0..8         default 1  */
+    int32_t window;                  /* R, 1..64        default 16 */
+    int32_t contrast;                /* C, 0..255       default 24 */
+    int32_t quiet;                   /* QZ, 0..16 modules, default 3 */
+    int32_t min_votes;               /* 1..2*S          default 2  */
+} ubd_decode_params;
+int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                       const ubd_decode_params *params, int32_t *results, void *stream);
+
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one
  * operation ("stage") per image per call, for n

@@ -46,6 +46,10 @@ class UbdPixelRecord(ctypes.Structure):
                 ("object_acc_sum", ctypes.c_double)]
 
 
+class UbdDecodeParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("symbologies", "scan_rows", "band", "window", "contrast", "quiet", "min_votes")]
+
+
 # every symbol include/ubd.h declares: name -> (restype, argtypes)
 _vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
 _f = ctypes.c_float
@@ -88,6 +92,7 @@ SIGNATURES = {
     "ubd_resize_images": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp]),
     "ubd_warp_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_extract_objects": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _i, _i, _vp, _vp]),
+    "ubd_decode_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_photometric_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_noise_alpha_images": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _vp]),
     "ubd_evaluate_accumulator_bytes": (_sz, [_i, _i]),

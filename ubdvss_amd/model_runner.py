@@ -278,8 +278,22 @@ class ModelRunner:
             raise RuntimeError("ModelRunner.predict_patches needs an MI355X; there is no CPU fallback")
         return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)))
 
-    def _predict_images(self, model, images, batch_size, patch):
-        """The loop of ``predict_images``; patch = (patch_h, patch_w, expand): also the patches of ``predict_patches``, else None."""
+    def predict_decoded(self, model, images, patch_size=(64, 256), expand=1.25, batch_size=None, **params):
+        """``predict_images`` plus the digits of every found object that is an EAN-13, UPC-A or EAN-8 symbol: the patches of
+        ``predict_patches`` stay on the device and are decoded there (``barcode_decoder.decode_patches_on_device``; ``params``
+        are its keywords).  ``expand`` 1.25 leaves the quiet zone around a tightly found code.  Returns (found, decoded):
+        ``found`` is exactly ``predict_images``' result, ``decoded[k][j]`` a ``DecodedBarcode`` or None for ``found[k][j]``.
+        The only extra read per group is the int32 result tensor (n, fullest list of the group, 16)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelRunner.predict_decoded needs an MI355X; there is no CPU fallback")
+        from .barcode_decoder import make_params
+        make_params(**params)                           # an unknown keyword fails before any work
+        return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)), decode=params)
+
+    def _predict_images(self, model, images, batch_size, patch, decode=None):
+        """The loop of ``predict_images``; patch = (patch_h, patch_w, expand): also the patches of ``predict_patches``, else None;
+        decode = the decoder's keywords: the patches are decoded on the device and the records returned in their place."""
+        from .barcode_decoder import decode_patches_on_device, results_to_records
         from .object_patches import _extract_staged
         from .segmap_manager import SegmapManager, ResizeMeta
         groups = {}
@@ -310,10 +324,17 @@ class ModelRunner:
                 if patch:
                     ph, pw, expand = patch
                     most = int(counts_h.max())
-                    host = np.zeros((len(part), 0, ph, pw, stage[3]), np.uint8)
+                    on_device = None
                     if most:                            # the patch tensor holds the fullest list of the group, not the capacity
-                        host = _extract_staged(stage, quads[:, :most].contiguous(), counts, metas, (ph, pw), expand, False, model.device,
-                                               zero=False).cpu().numpy()
+                        on_device = _extract_staged(stage, quads[:, :most].contiguous(), counts, metas, (ph, pw), expand, False,
+                                                    model.device, zero=False)
+                    if decode is not None:              # the patches stay on the device: one read of (n, most, 16) integers
+                        records = results_to_records(decode_patches_on_device(on_device, counts, **decode), counts_h) if most else \
+                            [[] for _ in part]
+                        for j, k in enumerate(part):
+                            patches[k] = records[j]
+                        continue
+                    host = on_device.cpu().numpy() if most else np.zeros((len(part), 0, ph, pw, stage[3]), np.uint8)
                     for j, k in enumerate(part):
                         patches[k] = np.array(host[j, :len(found[k])])
         return found, patches
