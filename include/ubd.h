@@ -392,8 +392,8 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
 /* --- decoding of the object patches: EAN-13 / UPC-A / EAN-8 ------------------------
  * The stage behind ubd_extract_objects: the digits of the retail symbol in every patch, read where the patches lie, so that
  * 64 bytes per object cross to the host instead of the patch.  One family, defined by the public EAN/UPC tables: EAN-13, UPC-A
- * (an EAN-13 whose first digit is 0) and EAN-8; `symbologies` is a mask so that other families can join behind the same
- * entry point.  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy restatement
+ * (an EAN-13 whose first digit is 0) and EAN-8; `symbologies` is a mask whose bits are numbered over all families: bit 2,
+ * Code 128, has a result row of its own and is read by ubd_decode_text_patches below, not here.  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy restatement
  * tests/decode_oracle.py is matched bit for bit.
  *   patches (n, cap, patch_h, patch_w, channels) uint8 and counts (n) int32: DEVICE pointers, exactly as ubd_extract_objects
  *     writes and reads them; slots j >= min(counts[i], cap) are not read and their result rows are NOT written.
@@ -429,7 +429,8 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
  * pointer, n >= 1, cap >= 1, n * cap < 2^31, patch_w 32..1024, patch_h 1..1024, channels 1 or 3, and the ranges below.
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 typedef struct ubd_decode_params {
-    int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8; at least one */
+    int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8: ubd_decode_patches takes 1..3; bit 2 Code 128:
+                                        ubd_decode_text_patches takes 4.  The bits are numbered over all families */
     int32_t scan_rows;               /* S, 1..32        default 8  */
     int32_t band;                    /* b, 0..8         default 1  */
     int32_t window;                  /* R, 1..64        default 16 */
@@ -439,6 +440,56 @@ typedef struct ubd_decode_params {
 } ubd_decode_params;
 int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                        const ubd_decode_params *params, int32_t *results, void *stream);
+
+/* --- decoding of the object patches: Code 128 / GS1-128 ------------------------------
+ * The second family behind ubd_extract_objects: the text of the Code 128 symbol in every patch, 128 bytes per object.  The
+ * contract is that of ubd_decode_patches (device patches and counts as ubd_extract_objects writes them, params a HOST pointer
+ * read before the call returns, slots j >= min(counts[i], cap) neither read nor written), the params struct is the same, and
+ * `symbologies` must be 4 (bit 2).  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy
+ * restatement tests/text_decode_oracle.py is matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 128, or 0 for none; [1] votes; [2] direction mask (bit 0 read
+ *     left to right, bit 1 read right to left: the patch is the half-turned one); [3] T, the number of text elements; [4] flags,
+ *     bit 0: the first data character is FNC1 (GS1-128); [5] D, the number of data symbol characters; [6] the start value
+ *     (103 / 104 / 105); [7] the check value; [8 .. 8 + T) the text elements; the rest 0xFF.  For "none" bytes 0..7 are 0 and
+ *     bytes 8..127 are 0xFF.  A text element is an ASCII code 0..127 or 0xF1..0xF4 for FNC1..FNC4 (FNC4's Latin-1 meaning is
+ *     not interpreted).
+ * Per patch:
+ *   luma, scan lines, local threshold, edges and the mirrored list for reading right to left: those of ubd_decode_patches.
+ *   character: six runs w0..w5 (a bar first) of sum S; E_k = (22 (w_k + w_(k+1)) + S) / (2 S) for k = 0..3, each in 2..7; the
+ *     pattern n0..n5 is the one of the table with n_k + n_(k+1) == E_k for all four k (the 107 keys are distinct); with
+ *     V = n0 + n2 + n4 it must satisfy 2 |11 (w0 + w2 + w4) - S V| < 3 S.  Otherwise there is no character.
+ *   table: run widths for the values 0..106, a bar first; 103 / 104 / 105 are Start A / B / C, 106 is the first six runs of
+ *     the stop:
+ *     212222 222122 222221 121223 121322 131222 122213 122312 132212 221213 221312 231212 112232 122132 122231 113222 123122
+ *     123221 223211 221132 221231 213212 223112 312131 311222 321122 321221 312212 322112 322211 212123 212321 232121 111323
+ *     131123 131321 112313 132113 132311 211313 231113 231311 112133 112331 132131 113123 113321 133121 313121 211331 231131
+ *     213113 213311 213131 311123 311321 331121 312113 312311 332111 314111 221411 431111 111224 111422 121124 121421 141122
+ *     141221 112214 112412 122114 122411 142112 142211 241211 221114 413111 241112 134111 111242 121142 121241 114212 124112
+ *     124211 411212 421112 421211 212141 214121 412121 111143 111341 131141 114113 114311 411113 411311 113141 114131 311141
+ *     411131 211412 211214 211232 233111
+ *   candidate at a light-to-dark edge i of the direction's list e (E edges):
+ *     1. the character at i (edges i..i+6) is a start, 103 / 104 / 105; S_0 is its width;
+ *     2. if i >= 1: 11 (e_i - e_(i-1)) >= QZ * S_0;
+ *     3. the characters at j = i + 6, i + 12, ..: character j needs the edges j..j+6, its width S must satisfy
+ *        3 S_prev <= 4 S <= 5 S_prev, and it must decode to 0..102 (data) or 106 (stop); no character, or a value 103..105,
+ *        rejects the candidate, and so do more than 62 values (start + 60 data + check) before a stop;
+ *     4. at the stop edge j+7 must exist and the last bar b = e_(j+7) - e_(j+6) satisfy (22 b + S) / (2 S) == 2; if edge j+8
+ *        exists: 11 (e_(j+8) - e_(j+7)) >= QZ * S;
+ *     5. the values are start, d_1..d_D, check: D >= 1 and (start + sum k d_k) mod 103 == check.
+ *   votes: per (line, direction) only the valid candidate with the lowest start index counts, one vote for its whole value
+ *     sequence (sequences are compared in full).  The sequence with the most votes wins, its mask is the OR of the directions
+ *     that voted for it; fewer than min_votes, or another sequence with as many votes: none.
+ *   text of the winner: the set in force comes from the start value (A, B, C).  In set C the values 0..99 are two digit
+ *     characters, 100 switches to B, 101 to A, 102 is FNC1.  In sets A and B: 0..95 are ASCII (A: 0..63 -> 32..95, 64..95 ->
+ *     0..31; B: 0..95 -> 32..127), 96 FNC3, 97 FNC2, 98 Shift (the next one data character is read in the other of A and B; a
+ *     Shift as the last data character is dropped, a shifted Shift is a Shift again), 99 switches to C, 100 is Code B in A and
+ *     FNC4 in B, 101 is FNC4 in A and Code A in B, 102 FNC1.  D <= 60 bounds T at 120.
+ * Limits (non-zero return, ubd_last_error begins with "ubd_decode_text_patches", nothing launched, nothing written): those of
+ * ubd_decode_patches (no null pointer, n >= 1, cap >= 1, n * cap < 2^31, patch_w 32..1024, patch_h 1..1024, channels 1 or 3,
+ * the ranges of ubd_decode_params), symbologies == 4, results aligned to 4 bytes.
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
+int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                            const ubd_decode_params *params, uint8_t *results, void *stream);
 
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one

@@ -1,7 +1,9 @@
 """The digits of the retail symbols (EAN-13, UPC-A, EAN-8) in the object patches, decoded on the MI355X where
 ``extract_objects_on_device`` left them (``ubd_decode_patches``, include/ubd.h): 64 bytes per object come back instead of the
 patch.  The rules are written out in include/ubd.h; tests/decode_oracle.py restates them and the device matches it bit for bit.
-A patch may be the half-turned one (object_patches.py): both reading directions are tried and the result says which one read."""
+A patch may be the half-turned one (object_patches.py): both reading directions are tried and the result says which one read.
+The text of Code 128 / GS1-128 symbols is a second kernel with a result row of its own (``ubd_decode_text_patches``, 128 bytes
+per object; tests/text_decode_oracle.py): ``decode_text_patches_on_device`` and ``text_results_to_records``."""
 import collections
 import ctypes
 
@@ -11,13 +13,21 @@ import torch
 from . import _lib
 
 EAN13, EAN8 = 1, 2                                       # bits of ``symbologies``
+CODE128 = 4                                              # bit 2: read by ubd_decode_text_patches, not by ubd_decode_patches
 DEFAULT_PARAMS = dict(symbologies=EAN13 | EAN8, scan_rows=8, band=1, window=16, contrast=24, quiet=3, min_votes=2)
 RESULT_INTS = 16
+TEXT_RESULT_BYTES = 128
+FNC1, FNC2, FNC3, FNC4 = 0xF1, 0xF2, 0xF3, 0xF4          # text elements of a Code 128 result beside the ASCII codes 0..127
 
 DecodedBarcode = collections.namedtuple("DecodedBarcode", ["symbology", "text", "votes", "upside_down", "is_upc_a"])
 DecodedBarcode.__doc__ = """One decoded object.  symbology: 'EAN-13' or 'EAN-8'; text: all its digits, the check digit included;
 votes: the (scan line, direction) readings that agreed; upside_down: the patch was read right to left only (it is the half-turned
 one); is_upc_a: an EAN-13 whose first digit is 0 (its UPC-A number is text[1:])."""
+
+DecodedText = collections.namedtuple("DecodedText", ["symbology", "text", "votes", "upside_down", "gs1", "elements"])
+DecodedText.__doc__ = """One decoded Code 128 object.  symbology: 'Code 128'; text: its ASCII elements as a str, a leading FNC1 dropped
+(it sets gs1), any later FNC1 as '\\x1d', FNC2..FNC4 left out; votes and upside_down as in DecodedBarcode; gs1: the first data
+character is FNC1 (GS1-128); elements: every text element as a tuple of integers, ASCII codes 0..127 and 0xF1..0xF4 for FNC1..FNC4."""
 
 
 def make_params(**params):
@@ -29,33 +39,79 @@ def make_params(**params):
     return _lib.UbdDecodeParams(*[int(merged[k]) for k, _ in _lib.UbdDecodeParams._fields_])
 
 
-def decode_patches_on_device(patches, counts, **params):
-    """``patches``: uint8 device tensor (n, cap, patch_h, patch_w, c) and ``counts``: int32 (n), as ``extract_objects_on_device``
-    writes and takes them (counts may be a host array).  ``params``: symbologies, scan_rows, band, window, contrast, quiet,
-    min_votes (DEFAULT_PARAMS; ranges in include/ubd.h).  Returns the int32 device tensor (n, cap, 16) of ``ubd_decode_patches``:
-    [symbology 0 / 13 / 8, votes, direction mask, 13 digits or -1]; rows of slots that hold no object are all zero.
-    One launch on the current stream; nothing is read back."""
+def _device_arguments(what, patches, counts):
+    """the checks and conversions both entry points share -> (contiguous patches, device counts, shape)"""
     if not torch.cuda.is_available():
-        raise RuntimeError("decode_patches_on_device needs an MI355X; there is no CPU fallback")
+        raise RuntimeError(f"{what} needs an MI355X; there is no CPU fallback")
     if not (isinstance(patches, torch.Tensor) and patches.is_cuda and patches.dtype == torch.uint8 and patches.dim() == 5):
         raise ValueError("patches must be a uint8 device tensor (n, cap, patch_h, patch_w, c)")
-    lib = _lib.load()
-    p = make_params(**params)
     device = patches.device
     patches = patches.contiguous()
-    n, cap, ph, pw, c = (int(v) for v in patches.shape)
+    n = int(patches.shape[0])
     if isinstance(counts, torch.Tensor):
         counts = counts.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
     else:
         counts = torch.from_numpy(np.ascontiguousarray(np.asarray(counts), dtype=np.int32)).to(device, non_blocking=True)
     if tuple(counts.shape) != (n,):
         raise ValueError(f"counts must be ({n},), got {tuple(counts.shape)}")
+    return patches, counts, tuple(int(v) for v in patches.shape)
+
+
+def decode_patches_on_device(patches, counts, **params):
+    """``patches``: uint8 device tensor (n, cap, patch_h, patch_w, c) and ``counts``: int32 (n), as ``extract_objects_on_device``
+    writes and takes them (counts may be a host array).  ``params``: symbologies, scan_rows, band, window, contrast, quiet,
+    min_votes (DEFAULT_PARAMS; ranges in include/ubd.h).  Returns the int32 device tensor (n, cap, 16) of ``ubd_decode_patches``:
+    [symbology 0 / 13 / 8, votes, direction mask, 13 digits or -1]; rows of slots that hold no object are all zero.
+    One launch on the current stream; nothing is read back."""
+    patches, counts, (n, cap, ph, pw, c) = _device_arguments("decode_patches_on_device", patches, counts)
+    lib = _lib.load()
+    p = make_params(**params)
+    device = patches.device
     results = torch.zeros((n, cap, RESULT_INTS), dtype=torch.int32, device=device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     with torch.cuda.device(device):
         _lib.check(lib.ubd_decode_patches(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
                                           stream), "ubd_decode_patches")
     return results
+
+
+def decode_text_patches_on_device(patches, counts, **params):
+    """``patches`` and ``counts`` as for ``decode_patches_on_device``; ``params`` the same keywords, ``symbologies`` defaulting to
+    CODE128 (the only value ``ubd_decode_text_patches`` takes).  Returns the uint8 device tensor (n, cap, 128) of
+    ``ubd_decode_text_patches``: [128 or 0, votes, direction mask, T, flags, D, start value, check value, T text elements, 0xFF..];
+    rows of slots that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream;
+    nothing is read back."""
+    patches, counts, (n, cap, ph, pw, c) = _device_arguments("decode_text_patches_on_device", patches, counts)
+    lib = _lib.load()
+    p = make_params(**dict({"symbologies": CODE128}, **params))
+    results = torch.zeros((n, cap, TEXT_RESULT_BYTES), dtype=torch.uint8, device=patches.device)
+    results[:, :, 8:] = 0xFF
+    stream = ctypes.c_void_p(torch.cuda.current_stream(patches.device).cuda_stream)
+    with torch.cuda.device(patches.device):
+        _lib.check(lib.ubd_decode_text_patches(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
+                                               stream), "ubd_decode_text_patches")
+    return results
+
+
+def text_results_to_records(results, counts):
+    """(n, cap, 128) results of ``decode_text_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
+    min(counts[i], cap) entries, a ``DecodedText`` or None where nothing was read"""
+    r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    out = []
+    for i in range(r.shape[0]):
+        row = []
+        for j in range(min(int(c[i]), r.shape[1])):
+            code, votes, mask, t, flags = (int(v) for v in r[i, j, :5])
+            if code == 0:
+                row.append(None)
+                continue
+            elements = tuple(int(v) for v in r[i, j, 8:8 + t])
+            gs1 = bool(flags & 1)
+            text = "".join("\x1d" if v == FNC1 else chr(v) for v in elements[1 if gs1 else 0:] if v < 128 or v == FNC1)
+            row.append(DecodedText("Code 128", text, votes, mask == 2, gs1, elements))
+        out.append(row)
+    return out
 
 
 def results_to_records(results, counts):

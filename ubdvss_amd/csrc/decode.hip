@@ -4,13 +4,11 @@
 // tests/decode_oracle.py, which this kernel matches bit for bit (tests/test_gpu_decode.py).  The symbol tables (sets L, G, R,
 // the parity words, the checksums) are those of the public EAN/UPC specification (ISO/IEC 15420).
 //
-// Integer arithmetic only, and every intermediate fits an int32 at the limits (patch_w <= 1024, band <= 8, window <= 64):
-//   profile p <= 17 rows * 255 = 4335; d = 2p - lo - hi, |d| <= 8670 (kept as int16); contrast * m <= 255 * 17;
-//   edge e = 256 x + 256 |d| / (|d| + |d'|) <= 256 * 1023 = 261888 < 2^18, so every run, St and S4 are < 2^18;
+// Integer arithmetic only, and every intermediate fits an int32 at the limits (patch_w <= 1024, band <= 8, window <= 64).  The
+// profile, the threshold and the edges are decode_scan.h's, shared with decode_text.hip: every edge, run and sum of runs is < 2^18.
 //   quiet zone: modules * q <= 95 * 2^18 < 2^25 and QZ * St <= 16 * 2^18 = 2^22; guards: 2 * modules * w + St < 191 * 2^18 < 2^26;
 //   characters: 14 (w0 + w1) < 2^22, 11 * S4 < 2^22 and |7 (w0 + w2) - S4 (n0 + n2)| < 7 * 2^18 < 2^21.
-// The one division left (the edge position) has a non-negative dividend, so C's truncation is the floor of the rules; the
-// floors of the guard and character rules are taken by comparing products, which is the same thing without the division.
+// The floors of the guard and character rules are taken by comparing products, which is the same thing without the division.
 //
 // Shape: one workgroup of DC_WAVES waves per patch slot; a workgroup whose slot holds no object returns after one load of
 // counts[i].  One wave per scan line, DC_WAVES lines per round.  Per line in LDS: the profile p (int32), over which the edge list
@@ -22,14 +20,8 @@
 // valid candidate ends the search and its lowest lane writes the vote.  Votes go to a fixed table of 4 * scan_rows slots, slot
 // (line, direction, symbology), each written by at most one lane, so the result does not depend on the order in which waves run;
 // the tally counts, for every slot, the slots that hold the same payload, and lanes 0..15 of wave 0 store the result row.
-#include "common.h"
+#include "decode_scan.h"
 
-#define DC_WAVES 8
-#define DC_THREADS (DC_WAVES * 64)
-#define DC_MAX_W 1024
-#define DC_MIN_W 32
-#define DC_MAX_H 1024
-#define DC_MAX_ROWS 32
 #define DC_MAX_VOTES (4 * DC_MAX_ROWS)
 #define DC_TABLE_BYTES (DC_MAX_VOTES * 8 + DC_MAX_VOTES * 4)       // the vote table (uint64) and the tally's counts (int32)
 
@@ -46,21 +38,6 @@
 // 1 = set G): LLLLLL LLGLGG LLGGLG LLGGGL LGLLGG LGGLLG LGGGLL LGLGLG LGLGGL LGGLGL
 #define DC_PARITY_WORDS ((0x00ull) | (0x0Bull << 6) | (0x0Dull << 12) | (0x0Eull << 18) | (0x13ull << 24) | (0x19ull << 30) | \
                          (0x1Cull << 36) | (0x15ull << 42) | (0x16ull << 48) | (0x1Aull << 54))
-
-struct DcLine {                 // the edge list of one scan line as one reading direction sees it
-    const int32_t *e;           // positions in 1/256 pixel, left to right
-    int n;                      // number of edges
-    int flip;                   // 256 * (patch_w - 1)
-    int l2d0;                   // 1: the first edge, left to right, goes from light to dark (polarities alternate)
-    bool rev;                   // the mirrored list e'_j = flip - e_(n-1-j), polarities swapped
-};
-
-static __device__ __forceinline__ int dc_edge(const DcLine &L, int j) { return L.rev ? L.flip - L.e[L.n - 1 - j] : L.e[j]; }
-
-static __device__ __forceinline__ bool dc_light_to_dark(const DcLine &L, int j)
-{
-    return L.rev ? !((L.l2d0 ^ (L.n - 1 - j)) & 1) : ((L.l2d0 ^ j) & 1);
-}
 
 // floor((14 a + s4) / (2 s4)) without a division: it is >= k exactly when 14 a >= (2k - 1) s4; 0: outside 2..5
 static __device__ __forceinline__ int dc_distance(int a, int s4)
@@ -149,70 +126,17 @@ __global__ __launch_bounds__(DC_THREADS) void decode_kernel(const uint8_t *__res
     uint64_t *votes = (uint64_t *)dc_smem;
     int32_t *tally = (int32_t *)(dc_smem + DC_MAX_VOTES * 8);
     const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-    const int pwp = (pw + 1) & ~1;                                              // int16 rows end on a dword boundary
-    int32_t *pe = (int32_t *)(dc_smem + DC_TABLE_BYTES + (size_t)wave * pwp * 6);   // pw int32: the profile, then the edges (at most pw - 1)
-    int16_t *dd = (int16_t *)(pe + pwp);                                        // pw int16: d
     const uint8_t *src = patches + (int64_t)slot * ph * pw * C;
     const int S = P.scan_rows, nv = 4 * S;
-    const unsigned long long below = (1ull << lane) - 1ull;
 
     for (int t = (int)threadIdx.x; t < nv; t += DC_THREADS) votes[t] = 0;       // ordered before the first vote by the barriers of round 0
 
     for (int k0 = 0; k0 < S; k0 += DC_WAVES) {
         const int k = k0 + wave;
         const bool on = k < S;                                                  // uniform over the wave
-        int m = 1;
-        if (on) {                                                               // the profile of scan line k
-            const int r = ((2 * k + 1) * ph) / (2 * S);
-            const int r0 = r - P.band < 0 ? 0 : r - P.band, r1 = r + P.band > ph - 1 ? ph - 1 : r + P.band;
-            m = r1 - r0 + 1;
-            for (int x = lane; x < pw; x += 64) {
-                int acc = 0;
-                for (int y = r0; y <= r1; ++y) {
-                    const uint8_t *q = src + ((int64_t)y * pw + x) * C;
-                    acc += C == 1 ? (int)q[0] : (19595 * (int)q[0] + 38470 * (int)q[1] + 7471 * (int)q[2] + 0x8000) >> 16;
-                }
-                pe[x] = acc;
-            }
-        }
-        __syncthreads();
-        if (on) {                                                               // the local threshold
-            const int flat = P.contrast * m;
-            for (int x = lane; x < pw; x += 64) {
-                const int x0 = x - P.window < 0 ? 0 : x - P.window, x1 = x + P.window > pw - 1 ? pw - 1 : x + P.window;
-                int lo = pe[x0], hi = lo;
-                for (int u = x0 + 1; u <= x1; ++u) {
-                    const int v = pe[u];
-                    lo = v < lo ? v : lo;
-                    hi = v > hi ? v : hi;
-                }
-                int d = 2 * pe[x] - lo - hi;
-                if (hi - lo < flat && d < 1) d = 1;
-                dd[x] = (int16_t)d;
-            }
-        }
-        __syncthreads();
-        int n_edges = 0, l2d0 = 0;
-        if (on) {                                                               // the edges, in order; they overwrite the profile
-            for (int xb = 0; xb < pw - 1; xb += 64) {
-                const int x = xb + lane;
-                bool is = false, l2d = false;
-                int pos = 0;
-                if (x < pw - 1) {
-                    const int a = dd[x], b = dd[x + 1];
-                    is = (a < 0) != (b < 0);
-                    if (is) {
-                        const int aa = a < 0 ? -a : a, bb = b < 0 ? -b : b;     // aa + bb >= 1: one of them is negative
-                        pos = 256 * x + (256 * aa) / (aa + bb);
-                        l2d = b < 0;
-                    }
-                }
-                const unsigned long long mask = __ballot(is), dark = __ballot(l2d);
-                if (is) pe[n_edges + __popcll(mask & below)] = pos;             // n_edges + 63 <= pw - 2: one edge per pixel pair at most
-                if (n_edges == 0 && mask) l2d0 = (int)((dark >> (__ffsll((long long)mask) - 1)) & 1ull);
-                n_edges += __popcll(mask);
-            }
-        }
+        int32_t *pe;
+        int n_edges, l2d0;
+        dc_scan_line<C>(src, ph, pw, k, S, on, wave, lane, P, dc_smem + DC_TABLE_BYTES, pe, n_edges, l2d0);
         __syncthreads();
         if (on) {                                                               // the candidates
             DcLine L;
@@ -284,7 +208,7 @@ extern "C" int ubd_decode_patches(const uint8_t *patches, const int32_t *counts,
     UBD_REQUIRE(patch_w >= DC_MIN_W && patch_w <= DC_MAX_W, "ubd_decode_patches: patch_w must be %d..%d, got %d", DC_MIN_W, DC_MAX_W, patch_w);
     UBD_REQUIRE(channels == 1 || channels == 3, "ubd_decode_patches: channels must be 1 or 3, got %d", channels);
     const ubd_decode_params P = *params;
-    UBD_REQUIRE(P.symbologies >= 1 && P.symbologies <= 3, "ubd_decode_patches: symbologies must be 1..3 (bit 0 EAN-13, bit 1 EAN-8), got %d", P.symbologies);
+    UBD_REQUIRE(P.symbologies >= 1 && P.symbologies <= 3, "ubd_decode_patches: symbologies must be 1..3 (bit 0 EAN-13, bit 1 EAN-8; bit 2, Code 128, is read by ubd_decode_text_patches), got %d", P.symbologies);
     UBD_REQUIRE(P.scan_rows >= 1 && P.scan_rows <= DC_MAX_ROWS, "ubd_decode_patches: scan_rows must be 1..%d, got %d", DC_MAX_ROWS, P.scan_rows);
     UBD_REQUIRE(P.band >= 0 && P.band <= 8, "ubd_decode_patches: band must be 0..8, got %d", P.band);
     UBD_REQUIRE(P.window >= 1 && P.window <= 64, "ubd_decode_patches: window must be 1..64, got %d", P.window);
@@ -294,7 +218,7 @@ extern "C" int ubd_decode_patches(const uint8_t *patches, const int32_t *counts,
                 2 * P.scan_rows, P.min_votes);
     UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "ubd_decode_patches: n * cap = %d * %d is not below 2^31", n, cap);
     const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
-    const size_t lds = DC_TABLE_BYTES + (size_t)DC_WAVES * ((patch_w + 1) & ~1) * 6;     // <= 1536 + 49152 bytes
+    const size_t lds = DC_TABLE_BYTES + dc_lines_bytes(patch_w);                          // <= 1536 + 49152 bytes
     if (channels == 3)
         hipLaunchKernelGGL(decode_kernel<3>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, results);
     else

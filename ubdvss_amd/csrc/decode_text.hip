@@ -1,0 +1,291 @@
+// Decoding of the object patches, second family: the text of a Code 128 / GS1-128 symbol out of every upright patch that
+// ubd_extract_objects wrote, on the device, so that 128 bytes per object cross to the host instead of the patch.  The rules are
+// written out at ubd_decode_text_patches in include/ubd.h and restated, from the rules and not from this file, by the numpy
+// oracle tests/text_decode_oracle.py, which this kernel matches bit for bit (tests/test_gpu_text_decode.py).  The patterns, the
+// code sets and the modulo-103 check are those of the public Code 128 specification (ISO/IEC 15417).
+//
+// Integer arithmetic only, and every intermediate fits an int32 at the limits (patch_w <= 1024, quiet <= 16).  Edges, runs and
+// sums of runs are < 2^18 (decode_scan.h), so
+//   characters: 22 (w + w') < 22 * 2^18 < 2^23 and 15 S < 2^22; bar sum: 11 (w0 + w2 + w4) < 2^22, S V <= 8 * 2^18 = 2^21, and
+//     twice their difference < 2^23; widths of neighbours: 5 S_prev < 2^21; stop bar: 22 b < 2^23;
+//   quiet zone: 11 q < 2^22 and QZ * S <= 16 * 2^18 = 2^22;
+//   check: start + sum k d_k over at most 61 values (the check value is taken out again at the stop)
+//     <= 105 + 102 * (61 * 62 / 2) = 192987.
+// No division is left: the floors of the character, stop-bar and quiet-zone rules are taken by comparing products.
+//
+// Shape: that of decode.hip.  One workgroup of DC_WAVES waves per patch slot; a workgroup whose slot holds no object returns
+// after one load of counts[i].  One wave per scan line, DC_WAVES lines per round, profile, threshold and edges from
+// decode_scan.h, stages separated by uniform workgroup barriers.  Before round 0 the 107 patterns (immediates, one hex digit
+// per run) are spread into a table of 6^4 entries in LDS, key ((E0 - 2) * 6 + (E1 - 2)) * 6 .. -> value | V << 8 (0xFFFF: no
+// pattern); the 107 keys are distinct, so no two lanes write one entry.  Candidates take one lane per start edge, 64 starts a
+// step in rising order; almost every lane ends at the start-character test.  A lane walks its candidate without keeping the
+// values (count, running check sum and last value are enough to accept it); the first step that holds a valid candidate ends
+// the search, and its lowest lane decodes the characters once more and writes count and values into the 64-byte vote slot of
+// (line, direction).  Each slot is written by at most one lane, so the result does not depend on the order in which waves run.
+// The tally compares whole slots (16 dwords; the count in byte 0 and zeroes behind the values make equal slots equal payloads).
+// Thread 0 expands the winner's text into a 128-byte row in LDS, which leaves as 32 dword stores.
+// LDS: 4096 (votes) + 256 (tally) + 2592 (key table) + 128 (row) + at most 49152 (lines) = 56224 bytes.
+#include "decode_scan.h"
+
+#define TX_MAX_VOTES (2 * DC_MAX_ROWS)          // slots (line, direction)
+#define TX_SLOT 64                              // bytes of a vote slot: [0] the number of values, [1..] the values, then zeroes
+#define TX_MAX_VALUES 62                        // start + 60 data + check
+#define TX_KEYS 1296                            // 6^4
+#define TX_ROW 128                              // bytes of a result row
+#define TX_OFF_TALLY (TX_MAX_VOTES * TX_SLOT)
+#define TX_OFF_KEYS (TX_OFF_TALLY + TX_MAX_VOTES * 4)
+#define TX_OFF_ROW (TX_OFF_KEYS + TX_KEYS * 2)
+#define TX_TABLE_BYTES (TX_OFF_ROW + TX_ROW)    // 7072, a multiple of 16
+#define TX_START_A 103
+#define TX_STOP 106
+
+// run widths for the values 0..106, a bar first, one hex digit per run; 103 / 104 / 105 are Start A / B / C, 106 is the first
+// six runs of the stop
+__constant__ uint32_t tx_patterns[107] = {
+    0x212222, 0x222122, 0x222221, 0x121223, 0x121322, 0x131222, 0x122213, 0x122312, 0x132212, 0x221213, 0x221312, 0x231212,
+    0x112232, 0x122132, 0x122231, 0x113222, 0x123122, 0x123221, 0x223211, 0x221132, 0x221231, 0x213212, 0x223112, 0x312131,
+    0x311222, 0x321122, 0x321221, 0x312212, 0x322112, 0x322211, 0x212123, 0x212321, 0x232121, 0x111323, 0x131123, 0x131321,
+    0x112313, 0x132113, 0x132311, 0x211313, 0x231113, 0x231311, 0x112133, 0x112331, 0x132131, 0x113123, 0x113321, 0x133121,
+    0x313121, 0x211331, 0x231131, 0x213113, 0x213311, 0x213131, 0x311123, 0x311321, 0x331121, 0x312113, 0x312311, 0x332111,
+    0x314111, 0x221411, 0x431111, 0x111224, 0x111422, 0x121124, 0x121421, 0x141122, 0x141221, 0x112214, 0x112412, 0x122114,
+    0x122411, 0x142112, 0x142211, 0x241211, 0x221114, 0x413111, 0x241112, 0x134111, 0x111242, 0x121142, 0x121241, 0x114212,
+    0x124112, 0x124211, 0x411212, 0x421112, 0x421211, 0x212141, 0x214121, 0x412121, 0x111143, 0x111341, 0x131141, 0x114113,
+    0x114311, 0x411113, 0x411311, 0x113141, 0x114131, 0x311141, 0x411131, 0x211412, 0x211214, 0x211232, 0x233111};
+
+// floor((22 a + s) / (2 s)) - 2 without a division: the floor is >= m exactly when 22 a >= (2m - 1) s; -1: outside 2..7
+static __device__ __forceinline__ int tx_distance(int a, int s)
+{
+    const int t = 22 * a;
+    if (t < 3 * s || t >= 15 * s) return -1;
+    return (t >= 5 * s) + (t >= 7 * s) + (t >= 9 * s) + (t >= 11 * s) + (t >= 13 * s);
+}
+
+// One character of six runs between the edges e[0..6]: its value 0..106, or -1.
+static __device__ __forceinline__ int tx_character(const int (&e)[7], const uint16_t *keys)
+{
+    const int s = e[6] - e[0];
+    if (s <= 0) return -1;
+    const int d0 = tx_distance(e[2] - e[0], s), d1 = tx_distance(e[3] - e[1], s), d2 = tx_distance(e[4] - e[2], s),
+              d3 = tx_distance(e[5] - e[3], s);
+    if ((d0 | d1 | d2 | d3) < 0) return -1;
+    const int entry = keys[((d0 * 6 + d1) * 6 + d2) * 6 + d3];
+    if (entry == 0xFFFF) return -1;
+    int off = 11 * ((e[1] - e[0]) + (e[3] - e[2]) + (e[5] - e[4])) - s * (entry >> 8);
+    off = off < 0 ? -off : off;
+    if (2 * off >= 3 * s) return -1;
+    return entry & 0xFF;
+}
+
+static __device__ __forceinline__ void tx_load(const DcLine &L, int j, int (&e)[7])
+{
+#pragma unroll
+    for (int k = 0; k < 7; ++k) e[k] = dc_edge(L, j + k);
+}
+
+// The candidate that starts at edge i: the number of its values (start, data, check: 3..62), or 0.
+static __device__ int tx_candidate(const DcLine &L, int i, int quiet, const uint16_t *keys)
+{
+    if (!dc_light_to_dark(L, i) || i + 6 >= L.n) return 0;
+    int e[7];
+    tx_load(L, i, e);
+    int v = tx_character(e, keys);
+    if (v < TX_START_A || v > TX_START_A + 2) return 0;
+    int sp = e[6] - e[0];
+    if (i >= 1 && 11 * (e[0] - dc_edge(L, i - 1)) < quiet * sp) return 0;
+    int sum = v, cnt = 1, last = 0, s, j = i + 6;
+    for (;; j += 6) {
+        if (j + 6 >= L.n) return 0;
+        tx_load(L, j, e);
+        s = e[6] - e[0];
+        if (4 * s < 3 * sp || 4 * s > 5 * sp) return 0;
+        v = tx_character(e, keys);
+        if (v < 0 || (v >= TX_START_A && v <= TX_START_A + 2)) return 0;
+        if (v == TX_STOP) break;
+        if (cnt == TX_MAX_VALUES) return 0;
+        sum += cnt * v;                                                         // the data weight k of value number cnt is cnt
+        last = v;
+        ++cnt;
+        sp = s;
+    }
+    if (j + 7 >= L.n) return 0;
+    const int e7 = dc_edge(L, j + 7), bar = 22 * (e7 - e[6]);
+    if (bar < 3 * s || bar >= 5 * s) return 0;                                  // (22 b + S) / (2 S) == 2
+    if (j + 8 < L.n && 11 * (dc_edge(L, j + 8) - e7) < quiet * s) return 0;
+    if (cnt < 3) return 0;
+    sum -= (cnt - 1) * last;                                                    // the last value is the check, not data
+    return sum % 103 == last ? cnt : 0;
+}
+
+// The values of the valid candidate at edge i into its vote slot (zeroed before round 0).
+static __device__ void tx_write_values(const DcLine &L, int i, int cnt, const uint16_t *keys, uint8_t *slot)
+{
+    slot[0] = (uint8_t)cnt;
+    for (int c = 0; c < cnt; ++c) {                                             // cnt <= 62: bytes 1..62
+        int e[7];
+        tx_load(L, i + 6 * c, e);
+        slot[1 + c] = (uint8_t)tx_character(e, keys);
+    }
+}
+
+// The text elements of the values in a vote slot into row[8..]; returns their number T (<= 2 * 60).
+static __device__ int tx_expand(const uint8_t *slot, uint8_t *text)
+{
+    const int cnt = slot[0];
+    int cur = slot[1] - TX_START_A, t = 0;                                      // 0 / 1 / 2: set A / B / C
+    bool shift = false;
+    for (int k = 2; k < cnt; ++k) {                                             // slot[2 .. cnt - 1] are the data values
+        const int v = slot[k];
+        if (cur == 2) {
+            if (v < 100) { text[t++] = (uint8_t)(48 + v / 10); text[t++] = (uint8_t)(48 + v % 10); }
+            else if (v == 102) text[t++] = 0xF1;
+            else cur = v == 100 ? 1 : 0;
+            continue;
+        }
+        const int code = shift ? 1 - cur : cur;                                 // a shifted character is read in the other set
+        shift = false;
+        if (v < 96) text[t++] = (uint8_t)(code == 0 ? (v < 64 ? v + 32 : v - 64) : v + 32);
+        else if (v == 96) text[t++] = 0xF3;
+        else if (v == 97) text[t++] = 0xF2;
+        else if (v == 98) shift = true;
+        else if (v == 99) cur = 2;
+        else if (v == 100) { if (code == 0) cur = 1; else text[t++] = 0xF4; }
+        else if (v == 101) { if (code == 0) text[t++] = 0xF4; else cur = 0; }
+        else text[t++] = 0xF1;
+    }
+    return t;
+}
+
+static __device__ __forceinline__ bool tx_same(const uint32_t *a, const uint32_t *b)
+{
+    bool same = true;
+#pragma unroll
+    for (int q = 0; q < TX_SLOT / 4; ++q) same = same && a[q] == b[q];
+    return same;
+}
+
+template <int C>
+__global__ __launch_bounds__(DC_THREADS) void decode_text_kernel(const uint8_t *__restrict__ patches, const int32_t *__restrict__ counts, int cap,
+                                                                 int ph, int pw, ubd_decode_params P, uint32_t *__restrict__ results)
+{
+    extern __shared__ __align__(16) unsigned char tx_smem[];
+    const int slot = (int)blockIdx.x;                                           // n * cap < 2^31 (checked on the host)
+    const int i = slot / cap, j = slot - i * cap;
+    if (j >= counts[i]) return;                                                 // j < cap already
+    uint32_t *votes = (uint32_t *)tx_smem;
+    int32_t *tally = (int32_t *)(tx_smem + TX_OFF_TALLY);
+    uint16_t *keys = (uint16_t *)(tx_smem + TX_OFF_KEYS);
+    uint32_t *row = (uint32_t *)(tx_smem + TX_OFF_ROW);
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint8_t *src = patches + (int64_t)slot * ph * pw * C;
+    const int S = P.scan_rows, nv = 2 * S;
+
+    for (int t = tid; t < nv * (TX_SLOT / 4); t += DC_THREADS) votes[t] = 0;
+    for (int t = tid; t < TX_KEYS / 2; t += DC_THREADS) ((uint32_t *)keys)[t] = 0xFFFFFFFFu;
+    if (tid < TX_ROW / 4) row[tid] = tid < 2 ? 0u : 0xFFFFFFFFu;                // the row of "none"
+    __syncthreads();
+    if (tid < 107) {
+        const uint32_t p = tx_patterns[tid];
+        int n[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) n[k] = (int)((p >> (4 * (5 - k))) & 15u);
+        const int key = (((n[0] + n[1] - 2) * 6 + (n[1] + n[2] - 2)) * 6 + (n[2] + n[3] - 2)) * 6 + (n[3] + n[4] - 2);   // sums of two widths: 2..7 for these patterns
+        keys[key] = (uint16_t)(tid | (n[0] + n[2] + n[4]) << 8);
+    }                                                                           // ordered before the first candidate by the barriers of round 0
+
+    for (int k0 = 0; k0 < S; k0 += DC_WAVES) {
+        const int k = k0 + wave;
+        const bool on = k < S;                                                  // uniform over the wave
+        int32_t *pe;
+        int n_edges, l2d0;
+        dc_scan_line<C>(src, ph, pw, k, S, on, wave, lane, P, tx_smem + TX_TABLE_BYTES, pe, n_edges, l2d0);
+        __syncthreads();
+        if (on) {                                                               // the candidates
+            DcLine L;
+            L.e = pe; L.n = n_edges; L.flip = 256 * (pw - 1); L.l2d0 = l2d0;
+            const int starts = n_edges - 25;                                    // start, one data, check and stop take the edges i .. i + 25
+            for (int dir = 0; dir < 2; ++dir) {
+                L.rev = dir == 1;
+                for (int ib = 0; ib < starts; ib += 64) {
+                    const int c = ib + lane;
+                    const int cnt = c < starts ? tx_candidate(L, c, P.quiet, keys) : 0;
+                    const unsigned long long valid = __ballot(cnt != 0);
+                    if (valid) {                                                // the lowest start index of this (line, direction)
+                        if (lane == __ffsll((long long)valid) - 1) tx_write_values(L, c, cnt, keys, (uint8_t *)(votes + (k * 2 + dir) * (TX_SLOT / 4)));
+                        break;
+                    }
+                }
+            }
+        }
+        __syncthreads();                                                        // the next round overwrites the edges
+    }
+
+    // the tally: per slot the number of slots with the same payload and the OR of their direction bits
+    if (tid < nv) {
+        const uint32_t *mine = votes + tid * (TX_SLOT / 4);
+        int cnt = 0, mask = 0;
+        if (mine[0] & 0xFFu)
+            for (int u = 0; u < nv; ++u)
+                if (tx_same(mine, votes + u * (TX_SLOT / 4))) { ++cnt; mask |= 1 << (u & 1); }
+        tally[tid] = cnt | mask << 16;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int best = 0, at = -1;
+        for (int u = 0; u < nv; ++u) {
+            const int c = tally[u] & 0xffff;
+            if (c > best) { best = c; at = u; }
+        }
+        bool won = at >= 0 && best >= P.min_votes;
+        for (int u = 0; won && u < nv; ++u)
+            if ((tally[u] & 0xffff) == best && !tx_same(votes + at * (TX_SLOT / 4), votes + u * (TX_SLOT / 4))) won = false;   // another payload has as many
+        if (won) {
+            const uint8_t *win = (const uint8_t *)(votes + at * (TX_SLOT / 4));
+            uint8_t *bytes = (uint8_t *)row;
+            const int cnt = win[0];
+            bytes[0] = 128;
+            bytes[1] = (uint8_t)best;                                           // <= 2 * 32
+            bytes[2] = (uint8_t)(tally[at] >> 16);
+            bytes[3] = (uint8_t)tx_expand(win, bytes + 8);                      // T <= 120: bytes 8..127
+            bytes[4] = win[2] == 102 ? 1 : 0;                                   // the first data character is FNC1
+            bytes[5] = (uint8_t)(cnt - 2);
+            bytes[6] = win[1];
+            bytes[7] = win[cnt];
+        }
+    }
+    __syncthreads();
+    if (tid < TX_ROW / 4) results[(int64_t)slot * (TX_ROW / 4) + tid] = row[tid];
+}
+
+extern "C" int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                                       const ubd_decode_params *params, uint8_t *results, void *stream)
+{
+    UBD_REQUIRE(patches, "ubd_decode_text_patches: patches is null");
+    UBD_REQUIRE(counts, "ubd_decode_text_patches: counts is null");
+    UBD_REQUIRE(params, "ubd_decode_text_patches: params is null");
+    UBD_REQUIRE(results, "ubd_decode_text_patches: results is null");
+    UBD_REQUIRE(((uintptr_t)results & 3) == 0, "ubd_decode_text_patches: results must be aligned to 4 bytes");
+    UBD_REQUIRE(n >= 1, "ubd_decode_text_patches: n must be >= 1, got %d", n);
+    UBD_REQUIRE(cap >= 1, "ubd_decode_text_patches: cap must be >= 1, got %d", cap);
+    UBD_REQUIRE(patch_h >= 1 && patch_h <= DC_MAX_H, "ubd_decode_text_patches: patch_h must be 1..%d, got %d", DC_MAX_H, patch_h);
+    UBD_REQUIRE(patch_w >= DC_MIN_W && patch_w <= DC_MAX_W, "ubd_decode_text_patches: patch_w must be %d..%d, got %d", DC_MIN_W, DC_MAX_W, patch_w);
+    UBD_REQUIRE(channels == 1 || channels == 3, "ubd_decode_text_patches: channels must be 1 or 3, got %d", channels);
+    const ubd_decode_params P = *params;
+    UBD_REQUIRE(P.symbologies == 4, "ubd_decode_text_patches: symbologies must be 4 (bit 2 Code 128; bits 0 and 1 are ubd_decode_patches'), got %d",
+                P.symbologies);
+    UBD_REQUIRE(P.scan_rows >= 1 && P.scan_rows <= DC_MAX_ROWS, "ubd_decode_text_patches: scan_rows must be 1..%d, got %d", DC_MAX_ROWS, P.scan_rows);
+    UBD_REQUIRE(P.band >= 0 && P.band <= 8, "ubd_decode_text_patches: band must be 0..8, got %d", P.band);
+    UBD_REQUIRE(P.window >= 1 && P.window <= 64, "ubd_decode_text_patches: window must be 1..64, got %d", P.window);
+    UBD_REQUIRE(P.contrast >= 0 && P.contrast <= 255, "ubd_decode_text_patches: contrast must be 0..255, got %d", P.contrast);
+    UBD_REQUIRE(P.quiet >= 0 && P.quiet <= 16, "ubd_decode_text_patches: quiet must be 0..16, got %d", P.quiet);
+    UBD_REQUIRE(P.min_votes >= 1 && P.min_votes <= 2 * P.scan_rows, "ubd_decode_text_patches: min_votes must be 1..2 * scan_rows = %d, got %d",
+                2 * P.scan_rows, P.min_votes);
+    UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "ubd_decode_text_patches: n * cap = %d * %d is not below 2^31", n, cap);
+    const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
+    const size_t lds = TX_TABLE_BYTES + dc_lines_bytes(patch_w);                // <= 7072 + 49152 bytes
+    if (channels == 3)
+        hipLaunchKernelGGL(decode_text_kernel<3>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, (uint32_t *)results);
+    else
+        hipLaunchKernelGGL(decode_text_kernel<1>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, (uint32_t *)results);
+    UBD_CHECK_HIP(hipGetLastError());
+    return 0;
+}

@@ -283,17 +283,21 @@ class ModelRunner:
         ``predict_patches`` stay on the device and are decoded there (``barcode_decoder.decode_patches_on_device``; ``params``
         are its keywords).  ``expand`` 1.25 leaves the quiet zone around a tightly found code.  Returns (found, decoded):
         ``found`` is exactly ``predict_images``' result, ``decoded[k][j]`` a ``DecodedBarcode`` or None for ``found[k][j]``.
-        The only extra read per group is the int32 result tensor (n, fullest list of the group, 16)."""
+        The only extra read per group is the int32 result tensor (n, fullest list of the group, 16).
+        With bit 2 of ``symbologies`` (``barcode_decoder.CODE128``; 7 reads every family) the same device patches also go through
+        ``decode_text_patches_on_device``, the retail kernel running only if bit 0 or 1 is set: ``decoded[k][j]`` is the retail
+        record if there is one, else the ``DecodedText``, else None, and the uint8 results (n, fullest list, 128) are read too."""
         if not torch.cuda.is_available():
             raise RuntimeError("ModelRunner.predict_decoded needs an MI355X; there is no CPU fallback")
-        from .barcode_decoder import make_params
-        make_params(**params)                           # an unknown keyword fails before any work
+        from .barcode_decoder import make_params, CODE128
+        symbologies = make_params(**params).symbologies     # an unknown keyword fails before any work
+        if symbologies & CODE128 and symbologies & ~7:
+            raise ValueError(f"symbologies {symbologies}: bits 0..2 (EAN-13, EAN-8, Code 128) are the known families")
         return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)), decode=params)
 
     def _predict_images(self, model, images, batch_size, patch, decode=None):
         """The loop of ``predict_images``; patch = (patch_h, patch_w, expand): also the patches of ``predict_patches``, else None;
         decode = the decoder's keywords: the patches are decoded on the device and the records returned in their place."""
-        from .barcode_decoder import decode_patches_on_device, results_to_records
         from .object_patches import _extract_staged
         from .segmap_manager import SegmapManager, ResizeMeta
         groups = {}
@@ -329,8 +333,7 @@ class ModelRunner:
                         on_device = _extract_staged(stage, quads[:, :most].contiguous(), counts, metas, (ph, pw), expand, False,
                                                     model.device, zero=False)
                     if decode is not None:              # the patches stay on the device: one read of (n, most, 16) integers
-                        records = results_to_records(decode_patches_on_device(on_device, counts, **decode), counts_h) if most else \
-                            [[] for _ in part]
+                        records = self._decode_records(on_device, counts, counts_h, decode) if most else [[] for _ in part]
                         for j, k in enumerate(part):
                             patches[k] = records[j]
                         continue
@@ -338,6 +341,23 @@ class ModelRunner:
                     for j, k in enumerate(part):
                         patches[k] = np.array(host[j, :len(found[k])])
         return found, patches
+
+    @staticmethod
+    def _decode_records(on_device, counts, counts_h, decode):
+        """the records of one group's device patches; bit 2 of ``symbologies`` adds the text kernel on the same patches"""
+        from .barcode_decoder import decode_patches_on_device, results_to_records, decode_text_patches_on_device, \
+            text_results_to_records, DEFAULT_PARAMS, CODE128
+        symbologies = int(decode.get("symbologies", DEFAULT_PARAMS["symbologies"]))
+        if not symbologies & CODE128:
+            return results_to_records(decode_patches_on_device(on_device, counts, **decode), counts_h)
+        retail = None
+        if symbologies & ~CODE128:                      # both kernels are launched before the first result is read
+            retail = decode_patches_on_device(on_device, counts, **dict(decode, symbologies=symbologies & ~CODE128))
+        text = decode_text_patches_on_device(on_device, counts, **dict(decode, symbologies=CODE128))
+        records = text_results_to_records(text, counts_h)
+        if retail is not None:
+            records = [[a if a is not None else b for a, b in zip(ra, rb)] for ra, rb in zip(results_to_records(retail, counts_h), records)]
+        return records
 
     def predict_stream(self, model, batches, rescale=False, meta_infos=None, copy_threads=8):
         """The loop of the reference's ``ModelRunner.run`` (model_runner.py:60-67: ``predict`` batch after batch) as ONE pipeline:
