@@ -1,6 +1,7 @@
-"""Three-way comparison of the forward forms of the Winograd dilated layer in ONE process: products on the fp32 MFMA (wino.hip,
+"""Four-way comparison of the forward forms of the Winograd dilated layer in ONE process: products on the fp32 MFMA (wino.hip,
 UBD_DILCONV=wino32), three-way bf16 split products on the bf16 MFMA (wino6.hip, UBD_DILCONV=split3) and two-piece fp16 split products
-under per-row scales on the fp16 MFMA (wino6.hip, the default).  UBD_DILCONV is read when a handle is created, so the three models are
+under per-row scales on the fp16 MFMA (wino6.hip), the samples split by conversions of the scaled T (UBD_WINO6_SPLIT=cvt) or by
+mixed-precision fmas with the scale folded in (the default).  The switches are read when a handle is created, so the four models are
 created under different settings.  Prints, per layer, the error of each form against an fp64 convolution on the host
 (relative to max |y|) and the time per launch at 32 x 128 x 128 x 24 (HIP events around 300 back-to-back launches)."""
 import ctypes
@@ -17,9 +18,10 @@ torch.cuda.set_device(0)
 lib = _lib.load()
 
 
-def make(env):
-    if env: os.environ["UBD_DILCONV"] = env
-    else: os.environ.pop("UBD_DILCONV", None)
+def make(env, split=""):
+    for name, value in (("UBD_DILCONV", env), ("UBD_WINO6_SPLIT", split)):
+        if value: os.environ[name] = value
+        else: os.environ.pop(name, None)
     m = Model(NetConfig(grey=False), seed=1)
     ws = torch.empty(int(lib.ubd_forward_workspace_bytes(m._h, 1, 4, 4)), dtype=torch.uint8, device="cuda")
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -35,9 +37,9 @@ def layer(mws, k, x, y):
 
 A = make("wino32")
 S = make("split3")
+C = make("", "cvt")
 B = make("")
-FORMS = (("fp32-MFMA", A), ("bf16x6", S), ("f16x3", B))
-os.environ.pop("UBD_DILCONV", None)
+FORMS = (("fp32-MFMA", A), ("bf16x6", S), ("f16x3 cvt", C), ("f16x3", B))
 dil = [1, 2, 4, 8, 16, 1]
 # ---- accuracy against fp64 on the host (2 x 72 x 100: ragged against every tile size)
 rng = np.random.default_rng(5)
@@ -57,13 +59,14 @@ for scale in (1.0, 255.0):
             layer(mws, k, x, y)
             torch.cuda.synchronize()
             out.append(np.abs(y.cpu().numpy().astype(np.float64) - ref).max() / np.abs(ref).max())
-        print(f"scale {scale:5.0f} layer {k} d {dil[k]:2d}: rel err fp32-MFMA {out[0]:.2e}  bf16x6 {out[1]:.2e}  f16x3 {out[2]:.2e}", flush=True)
+        print(f"scale {scale:5.0f} layer {k} d {dil[k]:2d}: rel err fp32-MFMA {out[0]:.2e}  bf16x6 {out[1]:.2e}  f16x3 cvt {out[2]:.2e}  f16x3 {out[3]:.2e}", flush=True)
 # bit-exact homogeneity: f(2x) = 2 f(x) with zero biases is not available here (biases are in the params); compare the forms directly instead
 x = torch.rand((32, 128, 128, 24), device="cuda") - 0.3
-ya, ys, yb = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+ya, ys, yb, yc = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
 for k in range(6):
-    layer(A, k, x, ya); layer(S, k, x, ys); layer(B, k, x, yb)
+    layer(A, k, x, ya); layer(S, k, x, ys); layer(B, k, x, yb); layer(C, k, x, yc)
     torch.cuda.synchronize()
+    assert torch.equal(yb, yc), f"layer {k}: the fma split and the conversion split differ"
     print(f"layer {k}: max |fp32-MFMA - bf16x6| = {(ya - ys).abs().max().item():.3e}  |fp32-MFMA - f16x3| = {(ya - yb).abs().max().item():.3e}  "
           f"|bf16x6 - f16x3| = {(ys - yb).abs().max().item():.3e} (max |y| {ya.abs().max().item():.3f})", flush=True)
 # ---- timing

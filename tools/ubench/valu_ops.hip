@@ -31,6 +31,17 @@
 #define OP_SDWA(d) "v_or_b32_sdwa " d ", %0, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n"
 #define OP_MAXI(d) "v_max_i32 " d ", 0, %0\n"
 #define OP_OR(d) "v_or_b32 " d ", %0, %3\n"
+// round 16: the instructions of the fp16 split (split2h.h).  mixlo / mixhi write one half of the destination and keep the other, so each
+// destination register is a chain of its own (8 chains, as v_sub_f32 / v_fma_f32 above)
+#define OP_MIXLO(d) "v_fma_mixlo_f16 " d ", %0, %3, %0\n"
+#define OP_MIXLOH(d) "v_fma_mixlo_f16 " d ", %0, %3, -%3 op_sel_hi:[0,0,1]\n"
+#define OP_MIXHI(d) "v_fma_mixhi_f16 " d ", %0, %3, %0\n"
+#define OP_MIXHIH(d) "v_fma_mixhi_f16 " d ", %0, %3, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n"
+#define OP_CVTPKH(d) "v_cvt_pk_f16_f32 " d ", %0, %3\n"
+#define OP_CVTF(d) "v_cvt_f32_f16 " d ", %0\n"
+#define OP_CVTFS(d) "v_cvt_f32_f16_sdwa " d ", %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n"
+#define OP_MIXF(d) "v_fma_mix_f32 " d ", %0, %3, -%3 op_sel_hi:[0,0,1]\n"
+#define OP_MIXFH(d) "v_fma_mix_f32 " d ", %0, %3, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n"
 #define OP_SNOP(d) "s_nop 0\n"
 #define OP_SADD(d) "s_add_i32 s40, s41, s42\n"
 #define CLOB : "+v"(a) : "s"(sel), "s"(mask), "v"(b), "v"(pa), "v"(pb) : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v30", "v31", "s40", "s41", "s42"
@@ -68,11 +79,23 @@ template <int MODE, int NT> __global__ __launch_bounds__(NT) void k(float *out, 
         if constexpr (MODE == 24) asm volatile(R48(OP_SDWA) CLOB);
         if constexpr (MODE == 25) asm volatile(R48(OP_MAXI) CLOB);
         if constexpr (MODE == 26) asm volatile(R48(OP_OR) CLOB);
+        if constexpr (MODE == 27) asm volatile(R48(OP_MIXLO) CLOB);
+        if constexpr (MODE == 28) asm volatile(R48(OP_MIXLOH) CLOB);
+        if constexpr (MODE == 29) asm volatile(R48(OP_MIXHI) CLOB);
+        if constexpr (MODE == 30) asm volatile(R48(OP_MIXHIH) CLOB);
+        if constexpr (MODE == 31) asm volatile(R48(OP_CVTPKH) CLOB);
+        if constexpr (MODE == 32) asm volatile(R48(OP_CVTF) CLOB);
+        if constexpr (MODE == 33) asm volatile(R48(OP_CVTFS) CLOB);
+        if constexpr (MODE == 34) asm volatile(R48(OP_MIXF) CLOB);
+        if constexpr (MODE == 35) asm volatile(R48(OP_MIXFH) CLOB);
     }
     out[blockIdx.x * NT + threadIdx.x] = a;
 }
 static const char *names[] = {"v_add_f32", "v_sub_f32 (dependent on itself, 8 chains)", "v_and_b32 literal", "v_and_b32 sgpr", "v_perm_b32", "v_cvt_pk_bf16_f32", "v_pack_b32_f16 op_sel hi,hi",
-                              "v_and_or_b32", "v_bfi_b32", "v_alignbit_b32", "v_lshrrev_b32", "v_xor_b32", "v_fma_f32 (8 chains)", "v_mov_b32", "v_pk_add_f32", "v_pk_add_f32 neg", "v_pk_mul_f32", "v_med3_f32", "v_max_f32", "v_add3_u32", "v_add_u32", "v_add_u32 sgpr", "s_nop 0", "s_nop 0 (again)", "v_or_b32_sdwa src1 WORD_1", "v_max_i32", "v_or_b32"};
+                              "v_and_or_b32", "v_bfi_b32", "v_alignbit_b32", "v_lshrrev_b32", "v_xor_b32", "v_fma_f32 (8 chains)", "v_mov_b32", "v_pk_add_f32", "v_pk_add_f32 neg", "v_pk_mul_f32", "v_med3_f32", "v_max_f32", "v_add3_u32", "v_add_u32", "v_add_u32 sgpr", "s_nop 0", "s_nop 0 (again)", "v_or_b32_sdwa src1 WORD_1", "v_max_i32", "v_or_b32",
+                              "v_fma_mixlo_f16 f32,f32,f32 (8 chains)", "v_fma_mixlo_f16 f32,f32,-f16 (8 chains)", "v_fma_mixhi_f16 f32,f32,f32 (8 chains)", "v_fma_mixhi_f16 f32,f32,-f16 hi (8 chains)",
+                              "v_cvt_pk_f16_f32", "v_cvt_f32_f16", "v_cvt_f32_f16_sdwa src0 WORD_1",
+                              "v_fma_mix_f32 f32,f32,-f16", "v_fma_mix_f32 f32,f32,-f16 hi"};
 template <int MODE, int NT> void run(float *out, float *in)
 {
     const int iters = 4000;
@@ -89,10 +112,12 @@ template <int MODE, int NT> void run(float *out, float *in)
     printf("%-44s %d waves/SIMD: %.3f ns = %.2f cycles at 2.4 GHz\n", names[MODE], NT / 256, per, per * 2.4);
 }
 template <int MODE> void run3(float *out, float *in) { run<MODE, 256>(out, in); run<MODE, 512>(out, in); run<MODE, 1024>(out, in); }
-template <int M> void maybe(int want, float *out, float *in) { if (want == M || want < 0) run3<M>(out, in); }
+static int want_last = -1;      // with a second argument: modes argv[1] .. argv[2]
+template <int M> void maybe(int want, float *out, float *in) { if (want == M || want < 0 || (M > want && M <= want_last)) run3<M>(out, in); }
 int main(int argc, char **argv)
 {
-    const int want = argc > 1 ? atoi(argv[1]) : -1;
+    const int want = argc > 1 ? atoi(argv[1]) : -1;      // one mode, a range of modes, or all of them
+    if (argc > 2) want_last = atoi(argv[2]);
     float *out, *in;
     (void)hipMalloc(&out, 256 * 1024 * 4); (void)hipMalloc(&in, 4096 * 4);
     float h[4096];
@@ -125,5 +150,14 @@ int main(int argc, char **argv)
     maybe<24>(want, out, in);
     maybe<25>(want, out, in);
     maybe<26>(want, out, in);
+    maybe<27>(want, out, in);
+    maybe<28>(want, out, in);
+    maybe<29>(want, out, in);
+    maybe<30>(want, out, in);
+    maybe<31>(want, out, in);
+    maybe<32>(want, out, in);
+    maybe<33>(want, out, in);
+    maybe<34>(want, out, in);
+    maybe<35>(want, out, in);
     return 0;
 }

@@ -80,6 +80,7 @@ struct env_switch { const char *name; size_t field; const char *value; int set; 
 static const env_switch ENV_SWITCHES[] = {
     SW("UBD_DILCONV", use_wino, "direct", 0), SW("UBD_DILCONV", wino_x6, "direct", 0), SW("UBD_DILCONV", wino_x6, "wino32", 0),
     SW("UBD_DILCONV", wino6_split3, "split3", 1),
+    SW("UBD_WINO6_SPLIT", wino6_cvt_split, "cvt", 1),
     SW("UBD_WINO6_LAYOUT", wino6_natural, "natural", 1),
     SW("UBD_STEM", fuse_stem, "fused", UBD_STEM_FUSED23), SW("UBD_STEM", fuse_force, "fused", 1),
     SW("UBD_STEM", fuse_stem, "fused123", UBD_STEM_FUSED123), SW("UBD_STEM", fuse_force, "fused123", 1),

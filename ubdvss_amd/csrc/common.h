@@ -46,6 +46,7 @@ struct ubd_handle {
     int loss_chain;           // UBD_LOSS=chain: the loss as its five dependent launches (the batch-global mode's form) instead of the one-launch kernel (diagnostics / tests)
     int wino_x6;              // forward Winograd products as split products on the 16-bit MFMAs (wino6.hip; default), 0: on the fp32 MFMA (UBD_DILCONV=wino32)
     int wino6_split3;         // UBD_DILCONV=split3: wino6.hip's products as three bf16 pieces, six MFMAs per product (the form before the two-piece fp16 split; the reference side of its tests), 0 (default): two fp16 pieces under power-of-two scales per tile row and per layer, three MFMAs
+    int wino6_cvt_split;      // UBD_WINO6_SPLIT=cvt: the fp16 form of wino6.hip takes the residual x - h1 of the sample split by two conversions and a subtraction (split2h_6, six instructions per pair of values: the form before the fma residual and the reference side of tests/test_gpu_wino6_mix.py), 0 (default): by v_fma_mix_f32 (split2h_6m, four per pair); the same bits
     int wino6_natural;        // UBD_WINO6_LAYOUT=natural: the fp32 inference pass keeps every activation in the natural column order (wino6.hip), no phase-major layouts between the layers (the reference side of the bit-identity tests)
 };
 

@@ -111,6 +111,34 @@ __device__ __forceinline__ void split2h_6(f32x4 a, f32x2 b, u32x4 &P1, u32x4 &P2
     P1 = (u32x4){p1[0], p1[1], p1[2], 0u};
     P2 = (u32x4){p2[0], p2[1], p2[2], 0u};
 }
+// The same pieces with the residual taken by a mixed-precision fma: v_fma_mix_f32 computes a b + c in fp32 with each operand fp32
+// or one HALF of a packed fp16 register, so x - h1 reads h1 where v_cvt_pk_f16_f32 left it and the two conversions back to fp32
+// go: v_cvt_pk_f16_f32, 2 x v_fma_mix_f32, v_cvt_pk_f16_f32 -- four instructions for two values.  x 1 - h1 is exact, as x - h1 is:
+// the same bits.  v_fma_mix_f32 issues at the rate of the conversions (4.4 cycles per instruction and SIMD at two waves); the forms
+// that round to fp16 themselves (v_fma_mixlo_f16 / v_fma_mixhi_f16, which would save the last conversion too) take 8.4 and lose
+// (tools/ubench/valu_ops.hip, profiles/r16_ubench_valu_mix.txt).
+// `one` is a 1.0f that the caller hides from the optimiser (an empty asm): with a visible 1 the fma folds to a subtraction, which
+// hipcc builds from two conversions again.  The empty asm here makes the packed h1 opaque, so that its halves are read in place
+// (op_sel) instead of being recomputed.  Plain C++ otherwise: hipcc's scheduler and hazard recogniser see every instruction (wino6.hip).
+__device__ __forceinline__ void split2h_pair_m(float a, float b, float one, unsigned &p1, unsigned &p2)
+{
+    const f32x2 v = {a, b};
+    f16x2 h1 = __builtin_convertvector(v, f16x2);
+    asm("" : "+v"(h1));
+    const f32x2 r = {__builtin_fmaf(a, one, -(float)h1[0]), __builtin_fmaf(b, one, -(float)h1[1])};
+    const f16x2 h2 = __builtin_convertvector(r, f16x2);
+    p1 = __builtin_bit_cast(unsigned, h1);
+    p2 = __builtin_bit_cast(unsigned, h2);
+}
+__device__ __forceinline__ void split2h_6m(f32x4 a, f32x2 b, float one, u32x4 &P1, u32x4 &P2)
+{
+    unsigned p1[3], p2[3];
+    split2h_pair_m(a[0], a[1], one, p1[0], p2[0]);
+    split2h_pair_m(a[2], a[3], one, p1[1], p2[1]);
+    split2h_pair_m(b[0], b[1], one, p1[2], p2[2]);
+    P1 = (u32x4){p1[0], p1[1], p1[2], 0u};
+    P2 = (u32x4){p2[0], p2[1], p2[2], 0u};
+}
 __device__ __forceinline__ f32x4 mfma16h(u32x4 a, u32x4 b, f32x4 c)
 {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);

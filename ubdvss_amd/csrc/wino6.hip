@@ -25,9 +25,10 @@
 //     h1 = f16(x),  h2 = f16(x - h1)   both rounded to NEAREST (truncation costs 4x the error: tools/sim_f16_split.py),
 // and THREE piece products are kept, chained from the smallest to the largest so that the big term is rounded once:
 // h2 g1, then h1 g2, then h1 g1 (the dropped h2 g2 is <= 2^-22 of the product's bound).  96 MFMAs per group, 64 KiB of weight
-// pieces (4 ds_read_b128 per point instead of 6), 3 vector instructions per value for the split (v_cvt_pk_f16_f32,
-// v_cvt_f32_f16, v_sub) plus one for the scale.  fp16's narrow exponent range is handled EXACTLY by power-of-two scales
-// (split2h.h):
+// pieces (4 ds_read_b128 per point instead of 6), 2 vector instructions per value for the split (per pair of values
+// v_cvt_pk_f16_f32, 2 x v_fma_mix_f32 for x - h1 with h1 read as fp16, v_cvt_pk_f16_f32; with UBD_WINO6_SPLIT=cvt the 3 per
+// value of round 15: v_cvt_pk_f16_f32, v_cvt_f32_f16, v_sub -- the same bits) plus one for the scale.  fp16's narrow exponent
+// range is handled EXACTLY by power-of-two scales (split2h.h):
 //   * weights: one scale t per layer, max |U| t in [2^12, 2^13), applied at pack time; 1 / t rides behind the fragments;
 //   * samples: one scale s per TILE and TRANSFORM ROW a, from the largest |T| of the row's 4 x 24 values T = (B^T D)[a] (the four
 //     lanes i, i + 16, i + 32, i + 48 hold a tile's channel quarters: v_max3 in the lane, two v_permlane swaps across);
@@ -199,11 +200,18 @@ struct w6addr {
 // EPI 0: y = relu(conv + bias);  EPI 2: logits = head(relu(conv + bias)) (one output channel; y is never written)
 // LAY: false = natural input and output (layout terms compiled out), true = the layouts of G.phase / G.l2po
 // F16: true = two fp16 pieces under per-row scales, 3 MFMAs per product (the default); false = three bf16 pieces, 6 MFMAs (UBD_DILCONV=split3)
-template <int EPI, bool LAY, bool F16 = true>
+// MIX (F16 only): true = the residual x - h1 of the sample split by v_fma_mix_f32 (split2h_6m: 4 instructions per pair of values, the
+//      default); false = by two conversions and a subtraction (split2h_6: 6 per pair, UBD_WINO6_SPLIT=cvt -- the form of round 15, the
+//      reference side of tests/test_gpu_wino6_mix.py).  The same bits either way.
+#ifndef W6_MIX_FILL
+#define W6_MIX_FILL 2      // vector instructions placed behind each MFMA of a point in the MIX form: the next point's split is 12 for 6 MFMAs
+#endif
+template <int EPI, bool LAY, bool F16 = true, bool MIX = F16>
 __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const float *__restrict__ x, float *__restrict__ y,
                                                                      const unsigned *__restrict__ ufrag,
                                                                      const float *__restrict__ bias, w6geom G, const float *__restrict__ head UBD_STAMP_PARAM)
 {
+    static_assert(F16 || !MIX, "the fma residual belongs to the fp16 form");
     constexpr int NPC = F16 ? 2 : 3;                                                 // pieces per weight
     constexpr int FRAG_U32 = F16 ? UBD_WINO6_FRAG_U32 : UBD_WINO6_FRAG3_U32;
     __shared__ __attribute__((aligned(16))) unsigned s_u[FRAG_U32];                  // 64 KiB (96 KiB for three pieces)
@@ -225,6 +233,8 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
     }
     [[maybe_unused]] float inv_t = 1.f;           // 1 / (the layer's weight scale): wave-uniform, behind the fragments (pack_wino6h_kernel)
     if constexpr (F16) inv_t = __builtin_bit_cast(float, ufrag[UBD_WINO6_FRAG_U32]);
+    [[maybe_unused]] float one = 1.f;             // MIX: the factor of x 1 - h1, hidden so that the fma stays an fma (split2h_6m)
+    if constexpr (MIX) asm volatile("" : "+v"(one));
     // XCD-aware split (see dilconv_f32_kernel)
     const int xcd = blockIdx.x & 7;
     const int nblk_x = (gridDim.x + 7 - xcd) >> 3;
@@ -427,9 +437,13 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
         // The fp16 form of the same pipeline: per point 4 weight reads, 6 MFMAs (per N tile h2 g1, then h1 g2, then h1 g1: small terms
         // first, the big term rounded once) and, behind the MFMAs, the split of point xi + 1 into its two operand quads
         // (3 v_cvt_pk_f16_f32 + 6 v_cvt_f32_f16 + 6 v_sub_f32 + 3 v_cvt_pk_f16_f32 for six values: 3 per value, and with the scaling of
-        // T in make_v 4).
+        // T in make_v 4).  MIX: 3 v_cvt_pk_f16_f32 + 6 v_fma_mix_f32 + 3 v_cvt_pk_f16_f32: 2 per value, 3 with the scaling.
         u32x4 U[2][2];
         u32x4 P1, P2, N1, N2;
+        auto split = [&](int b, u32x4 &Q1, u32x4 &Q2) {
+            if constexpr (MIX) split2h_6m(V4[b], V2[b], one, Q1, Q2);
+            else split2h_6(V4[b], V2[b], Q1, Q2);
+        };
         auto load_u = [&](int xi) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt)
@@ -437,7 +451,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                 for (int pc = 0; pc < 2; ++pc) U[nt][pc] = su4[((xi * 2 + nt) * 2 + pc) * 64];
         };
         load_u(0);
-        split2h_6(V4[0], V2[0], P1, P2);
+        split(0, P1, P2);
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi) {
             const int a = xi >> 2, b = xi & 3;
@@ -447,11 +461,11 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
             m[0] = mfma16h(U[0][1], P1, m[0]); m[1] = mfma16h(U[1][1], P1, m[1]);
             m[0] = mfma16h(U[0][0], P1, m[0]); m[1] = mfma16h(U[1][0], P1, m[1]);
             // in the MFMAs' shadows: the pieces of the next point of this row (b < 3: V[b + 1] is there; the next row's V does not exist yet)
-            if (b < 3) split2h_6(V4[b + 1], V2[b + 1], N1, N2);
+            if (b < 3) split(b + 1, N1, N2);
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);      // three vector instructions behind it
+                __builtin_amdgcn_sched_group_barrier(0x002, MIX ? W6_MIX_FILL : 3, 0);      // the vector instructions behind it (12 or 18 in all)
             }
             __builtin_amdgcn_sched_barrier(0);
             if (xi == 3 && weights_pending) {                 // first group of the launch: the rest of the weight copy (rounds 2..7)
@@ -469,7 +483,7 @@ __global__ __launch_bounds__(64 * W6_WAVES) void dilconv_wino6_kernel(const floa
                     load_row(D, An, 0);
                     load_row(D, An, 2);
                 }
-                split2h_6(V4[0], V2[0], N1, N2);
+                split(0, N1, N2);
             }
             if (xi < 15) { P1 = N1; P2 = N2; }
             consume(a, b, m);
@@ -614,15 +628,19 @@ void ubd_launch_dilconv_wino6(const ubd_handle *h, int epi, const unsigned *frag
     int grid = ubd_grid_for(groups, h->num_cus, wpb, 1);
     grid = (grid + 7) / 8 * 8;
     const bool lay = lay_in != 1 || lay_out != 1;
-    ubd_dispatch_bool(h->wino6_split3 == 0, [&](auto f16_tag) {
-        constexpr bool F16 = decltype(f16_tag)::value;
+    // three bf16 pieces (UBD_DILCONV=split3) / two fp16 pieces split by conversions (UBD_WINO6_SPLIT=cvt) / by v_fma_mix_f32 (the default)
+    auto launch = [&](auto f16_tag, auto mix_tag) {
+        constexpr bool F16 = decltype(f16_tag)::value, MIX = decltype(mix_tag)::value;
         if (epi == 2 && lay)
-            hipLaunchKernelGGL((dilconv_wino6_kernel<2, true, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
+            hipLaunchKernelGGL((dilconv_wino6_kernel<2, true, F16, MIX>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
         else if (epi == 2)
-            hipLaunchKernelGGL((dilconv_wino6_kernel<2, false, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
+            hipLaunchKernelGGL((dilconv_wino6_kernel<2, false, F16, MIX>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, head UBD_STAMP_ARG("wino6"));
         else if (lay)
-            hipLaunchKernelGGL((dilconv_wino6_kernel<0, true, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
+            hipLaunchKernelGGL((dilconv_wino6_kernel<0, true, F16, MIX>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
         else
-            hipLaunchKernelGGL((dilconv_wino6_kernel<0, false, F16>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
-    });
+            hipLaunchKernelGGL((dilconv_wino6_kernel<0, false, F16, MIX>), dim3(grid), dim3(64 * W6_WAVES), 0, st, in, out, frag, bias, G, nullptr UBD_STAMP_ARG("wino6"));
+    };
+    if (h->wino6_split3) launch(std::false_type{}, std::false_type{});
+    else if (h->wino6_cvt_split) launch(std::true_type{}, std::false_type{});
+    else launch(std::true_type{}, std::true_type{});
 }
