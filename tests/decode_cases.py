@@ -81,6 +81,39 @@ def flat_patch(symbols, px_per_module, height, width, start, gap=0, channels=1):
     return np.ascontiguousarray(np.broadcast_to(row[None, :, None], (height, width, channels)))
 
 
+# The four helpers below are those of the GPU tests of both decoder families (tests/test_gpu_decode.py, tests/test_gpu_text_decode.py),
+# which import them under these names.
+def _tint(grey, c, seed=0):
+    """(.., h, w) uint8 -> (.., h, w, c): for c = 3 three different channel gains, so that the luma weights matter"""
+    if c == 1:
+        return grey[..., None]
+    gains = np.random.default_rng(seed).uniform(0.6, 1.0, 3)
+    return (grey[..., None].astype(np.float64) * gains).astype(np.uint8)
+
+
+def _stripes(rng, h, w, lo=1, hi=8):
+    row, x, v = np.zeros(w, np.uint8), 0, 0
+    while x < w:
+        k = int(rng.integers(lo, hi + 1))
+        row[x:x + k] = 225 if v else 35
+        x, v = x + k, 1 - v
+    return np.broadcast_to(row[None, :], (h, w)).copy()
+
+
+def _noisy(rng, grey, sigma=6.0):
+    return np.clip(np.rint(grey + rng.normal(0, sigma, grey.shape)), 0, 255).astype(np.uint8)
+
+
+def _row_from_pixel_runs(runs_px, width, start):
+    row, x = np.full(width, 225, np.uint8), start
+    for k, w in enumerate(runs_px):
+        if k % 2 == 0:
+            row[x:x + w] = 35
+        x += w
+    assert x <= width
+    return row
+
+
 def _blur(img, sigma):
     r = 3
     k = np.exp(-0.5 * (np.arange(-r, r + 1) / sigma) ** 2)

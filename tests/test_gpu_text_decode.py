@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # the helper modules beside this file
 import decode_cases as dc  # noqa: E402
+from decode_cases import _noisy, _row_from_pixel_runs, _stripes, _tint  # noqa: E402
 import decode_oracle as do  # noqa: E402
 import object_patches_oracle as opo  # noqa: E402
 import text_decode_cases as tc  # noqa: E402
@@ -63,27 +64,6 @@ def _run_and_check(patches, counts, **kw):
     assert np.array_equal(got, want), [(i, j, got[i, j, :24].tolist(), want[i, j, :24].tolist())
                                        for i in range(n) for j in range(cap) if not np.array_equal(got[i, j], want[i, j])]
     return got
-
-
-def _tint(grey, c, seed=0):
-    """(.., h, w) uint8 -> (.., h, w, c): for c = 3 three different channel gains, so that the luma weights matter"""
-    if c == 1:
-        return grey[..., None]
-    gains = np.random.default_rng(seed).uniform(0.6, 1.0, 3)
-    return (grey[..., None].astype(np.float64) * gains).astype(np.uint8)
-
-
-def _stripes(rng, h, w, lo=1, hi=8):
-    row, x, v = np.zeros(w, np.uint8), 0, 0
-    while x < w:
-        k = int(rng.integers(lo, hi + 1))
-        row[x:x + k] = 225 if v else 35
-        x, v = x + k, 1 - v
-    return np.broadcast_to(row[None, :], (h, w)).copy()
-
-
-def _noisy(rng, grey, sigma=6.0):
-    return np.clip(np.rint(grey + rng.normal(0, sigma, grey.shape)), 0, 255).astype(np.uint8)
 
 
 def _symbol(h, w, values, rng=None):
@@ -211,16 +191,6 @@ def test_two_symbols_side_by_side_the_lowest_start_counts():
     assert got[0, 0].tolist() == _row(SHORT_A, 1, 1) and got[0, 1].tolist() == _row(SHORT_A, 1, 2)
     got = _run_and_check(patches, [2], scan_rows=5, band=0)
     assert got[0, 0, :3].tolist() == [128, 5, 1]
-
-
-def _row_from_pixel_runs(runs_px, width, start):
-    row, x = np.full(width, 225, np.uint8), start
-    for k, w in enumerate(runs_px):
-        if k % 2 == 0:
-            row[x:x + w] = 35
-        x += w
-    assert x <= width
-    return row
 
 
 def test_rejections_check_value_bar_sum_and_tie():

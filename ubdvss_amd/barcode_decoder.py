@@ -57,22 +57,31 @@ def _device_arguments(what, patches, counts):
     return patches, counts, tuple(int(v) for v in patches.shape)
 
 
+def _launch(entry, patches, counts, params, row, dtype, fill_from=None):
+    """one launch of the C entry point ``entry`` (ubd_X; its public function here is X_on_device) with the keyword ``params`` on
+    the current stream -> its (n, cap, row) device results of ``dtype``; the rows start as zeros, with 0xFF from element
+    ``fill_from`` on if that is given, which is what an unused slot keeps"""
+    patches, counts, (n, cap, ph, pw, c) = _device_arguments(entry[len("ubd_"):] + "_on_device", patches, counts)
+    lib = _lib.load()
+    p = make_params(**params)
+    device = patches.device
+    results = torch.zeros((n, cap, row), dtype=dtype, device=device)
+    if fill_from is not None:
+        results[:, :, fill_from:] = 0xFF
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(getattr(lib, entry)(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
+                                       stream), entry)
+    return results
+
+
 def decode_patches_on_device(patches, counts, **params):
     """``patches``: uint8 device tensor (n, cap, patch_h, patch_w, c) and ``counts``: int32 (n), as ``extract_objects_on_device``
     writes and takes them (counts may be a host array).  ``params``: symbologies, scan_rows, band, window, contrast, quiet,
     min_votes (DEFAULT_PARAMS; ranges in include/ubd.h).  Returns the int32 device tensor (n, cap, 16) of ``ubd_decode_patches``:
     [symbology 0 / 13 / 8, votes, direction mask, 13 digits or -1]; rows of slots that hold no object are all zero.
     One launch on the current stream; nothing is read back."""
-    patches, counts, (n, cap, ph, pw, c) = _device_arguments("decode_patches_on_device", patches, counts)
-    lib = _lib.load()
-    p = make_params(**params)
-    device = patches.device
-    results = torch.zeros((n, cap, RESULT_INTS), dtype=torch.int32, device=device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_decode_patches(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
-                                          stream), "ubd_decode_patches")
-    return results
+    return _launch("ubd_decode_patches", patches, counts, params, RESULT_INTS, torch.int32)
 
 
 def decode_text_patches_on_device(patches, counts, **params):
@@ -81,53 +90,42 @@ def decode_text_patches_on_device(patches, counts, **params):
     ``ubd_decode_text_patches``: [128 or 0, votes, direction mask, T, flags, D, start value, check value, T text elements, 0xFF..];
     rows of slots that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream;
     nothing is read back."""
-    patches, counts, (n, cap, ph, pw, c) = _device_arguments("decode_text_patches_on_device", patches, counts)
-    lib = _lib.load()
-    p = make_params(**dict({"symbologies": CODE128}, **params))
-    results = torch.zeros((n, cap, TEXT_RESULT_BYTES), dtype=torch.uint8, device=patches.device)
-    results[:, :, 8:] = 0xFF
-    stream = ctypes.c_void_p(torch.cuda.current_stream(patches.device).cuda_stream)
-    with torch.cuda.device(patches.device):
-        _lib.check(lib.ubd_decode_text_patches(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
-                                               stream), "ubd_decode_text_patches")
-    return results
+    return _launch("ubd_decode_text_patches", patches, counts, dict({"symbologies": CODE128}, **params), TEXT_RESULT_BYTES, torch.uint8,
+                   fill_from=8)
+
+
+def _records(results, counts, parse):
+    """per image the list of ``parse(row)`` over its min(counts[i], cap) result rows; ``parse`` gives None where nothing was read"""
+    r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
+    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    return [[parse(r[i, j]) for j in range(min(int(c[i]), r.shape[1]))] for i in range(r.shape[0])]
+
+
+def _text_record(row):
+    code, votes, mask, t, flags = (int(v) for v in row[:5])
+    if code == 0:
+        return None
+    elements = tuple(int(v) for v in row[8:8 + t])
+    gs1 = bool(flags & 1)
+    text = "".join("\x1d" if v == FNC1 else chr(v) for v in elements[1 if gs1 else 0:] if v < 128 or v == FNC1)
+    return DecodedText("Code 128", text, votes, mask == 2, gs1, elements)
+
+
+def _retail_record(row):
+    code, votes, mask = (int(v) for v in row[:3])
+    if code == 0:
+        return None
+    text = "".join(str(int(d)) for d in row[3:3 + code])
+    return DecodedBarcode("EAN-13" if code == 13 else "EAN-8", text, votes, mask == 2, code == 13 and text[0] == "0")
 
 
 def text_results_to_records(results, counts):
     """(n, cap, 128) results of ``decode_text_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
     min(counts[i], cap) entries, a ``DecodedText`` or None where nothing was read"""
-    r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
-    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
-    out = []
-    for i in range(r.shape[0]):
-        row = []
-        for j in range(min(int(c[i]), r.shape[1])):
-            code, votes, mask, t, flags = (int(v) for v in r[i, j, :5])
-            if code == 0:
-                row.append(None)
-                continue
-            elements = tuple(int(v) for v in r[i, j, 8:8 + t])
-            gs1 = bool(flags & 1)
-            text = "".join("\x1d" if v == FNC1 else chr(v) for v in elements[1 if gs1 else 0:] if v < 128 or v == FNC1)
-            row.append(DecodedText("Code 128", text, votes, mask == 2, gs1, elements))
-        out.append(row)
-    return out
+    return _records(results, counts, _text_record)
 
 
 def results_to_records(results, counts):
     """(n, cap, 16) results (device tensor or array) and counts (n) -> per image a list of min(counts[i], cap) entries, a
     ``DecodedBarcode`` or None where nothing was read"""
-    r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
-    c = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
-    out = []
-    for i in range(r.shape[0]):
-        row = []
-        for j in range(min(int(c[i]), r.shape[1])):
-            code, votes, mask = (int(v) for v in r[i, j, :3])
-            if code == 0:
-                row.append(None)
-                continue
-            text = "".join(str(int(d)) for d in r[i, j, 3:3 + code])
-            row.append(DecodedBarcode("EAN-13" if code == 13 else "EAN-8", text, votes, mask == 2, code == 13 and text[0] == "0"))
-        out.append(row)
-    return out
+    return _records(results, counts, _retail_record)

@@ -10,16 +10,13 @@
 //   characters: 14 (w0 + w1) < 2^22, 11 * S4 < 2^22 and |7 (w0 + w2) - S4 (n0 + n2)| < 7 * 2^18 < 2^21.
 // The floors of the guard and character rules are taken by comparing products, which is the same thing without the division.
 //
-// Shape: one workgroup of DC_WAVES waves per patch slot; a workgroup whose slot holds no object returns after one load of
-// counts[i].  One wave per scan line, DC_WAVES lines per round.  Per line in LDS: the profile p (int32), over which the edge list
-// is later written (p is dead by then), and d (int16).  The four stages of a round (profile, threshold, edges, candidates) are
-// separated by workgroup barriers; the round loop and the barriers are uniform over the workgroup, a wave beyond the last line
-// idles between them.  The sliding minimum and maximum are the plain loop over the 2R + 1 neighbours: at the defaults that is
-// 33 LDS reads per pixel of a 256-pixel line.  Edges are compacted in order, 64 pixels a step, with a ballot and the popcount
-// of the lanes below.  Candidates take one lane per start edge, 64 starts a step in rising order; the first step that holds a
-// valid candidate ends the search and its lowest lane writes the vote.  Votes go to a fixed table of 4 * scan_rows slots, slot
-// (line, direction, symbology), each written by at most one lane, so the result does not depend on the order in which waves run;
-// the tally counts, for every slot, the slots that hold the same payload, and lanes 0..15 of wave 0 store the result row.
+// Shape: that of decode_scan.h, which holds the kernel (dc_decode_kernel: prologue, rounds, search, tally, winner rule) and the
+// host side of the entry point (dc_decode); decode_text.hip runs the same two with its own policy.  This file holds the EAN
+// tables, the character and candidate rules (dc_distance, dc_character, dc_candidate) and the policy DcRetail.  The sliding
+// minimum and maximum of the scan are the plain loop over the 2R + 1 neighbours: at the defaults that is 33 LDS reads per pixel
+// of a 256-pixel line.  A line is searched for two symbologies, so votes go to a table of 4 * scan_rows slots, slot (line,
+// direction, symbology), each a 56-bit payload key (0: no vote); the tally counts, for every slot, the slots that hold the same
+// key, and lanes 0..15 of wave 0 store the result row.  LDS: 1024 (votes) + 512 (tally) + at most 49152 (lines) = 50688 bytes.
 #include "decode_scan.h"
 
 #define DC_MAX_VOTES (4 * DC_MAX_ROWS)
@@ -115,114 +112,52 @@ static __device__ uint64_t dc_candidate(const DcLine &L, int i, int sym, int qui
     return (uint64_t)(sym ? 8 : 13) << 52 | digits;
 }
 
-template <int C>
-__global__ __launch_bounds__(DC_THREADS) void decode_kernel(const uint8_t *__restrict__ patches, const int32_t *__restrict__ counts, int cap,
-                                                            int ph, int pw, ubd_decode_params P, int32_t *__restrict__ results)
-{
-    extern __shared__ __align__(8) unsigned char dc_smem[];
-    const int slot = (int)blockIdx.x;                                           // n * cap < 2^31 (checked on the host)
-    const int i = slot / cap, j = slot - i * cap;
-    if (j >= counts[i]) return;                                                 // j < cap already
-    uint64_t *votes = (uint64_t *)dc_smem;
-    int32_t *tally = (int32_t *)(dc_smem + DC_MAX_VOTES * 8);
-    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-    const uint8_t *src = patches + (int64_t)slot * ph * pw * C;
-    const int S = P.scan_rows, nv = 4 * S;
+// The policy of dc_decode_kernel (decode_scan.h).  LDS tables: the vote table, one payload key per slot (0: no vote), then the tally.
+struct DcRetail {
+    typedef int32_t Word;
+    static constexpr int ROW_WORDS = 16, SYMS = 2, SLOT_BYTES = 8, OFF_TALLY = DC_MAX_VOTES * 8, TABLE_BYTES = DC_TABLE_BYTES;
 
-    for (int t = (int)threadIdx.x; t < nv; t += DC_THREADS) votes[t] = 0;       // ordered before the first vote by the barriers of round 0
-
-    for (int k0 = 0; k0 < S; k0 += DC_WAVES) {
-        const int k = k0 + wave;
-        const bool on = k < S;                                                  // uniform over the wave
-        int32_t *pe;
-        int n_edges, l2d0;
-        dc_scan_line<C>(src, ph, pw, k, S, on, wave, lane, P, dc_smem + DC_TABLE_BYTES, pe, n_edges, l2d0);
-        __syncthreads();
-        if (on) {                                                               // the candidates
-            DcLine L;
-            L.e = pe; L.n = n_edges; L.flip = 256 * (pw - 1); L.l2d0 = l2d0;
-            for (int dir = 0; dir < 2; ++dir) {
-                L.rev = dir == 1;
-                for (int sym = 0; sym < 2; ++sym) {
-                    if (!((P.symbologies >> sym) & 1)) continue;
-                    const int starts = n_edges - (sym ? 43 : 59);               // start i needs the edges i .. i + runs
-                    for (int ib = 0; ib < starts; ib += 64) {
-                        const int c = ib + lane;
-                        const uint64_t key = c < starts ? dc_candidate(L, c, sym, P.quiet) : 0;
-                        const unsigned long long valid = __ballot(key != 0);
-                        if (valid) {                                            // the lowest start index of this (line, direction, symbology)
-                            if (lane == __ffsll((long long)valid) - 1) votes[(k * 2 + dir) * 2 + sym] = key;
-                            break;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();                                                        // the next round overwrites the edges
+    static __device__ __forceinline__ uint64_t *votes() { return (uint64_t *)dc_smem; }
+    static __device__ __forceinline__ void setup(int) {}
+    static __device__ __forceinline__ int starts(const ubd_decode_params &P, int sym, int n_edges)
+    {
+        return (P.symbologies >> sym) & 1 ? n_edges - (sym ? 43 : 59) : 0;      // start i needs the edges i .. i + runs
     }
+    static __device__ __forceinline__ uint64_t candidate(const DcLine &L, int i, int sym, int quiet) { return dc_candidate(L, i, sym, quiet); }
+    static __device__ __forceinline__ void vote(const DcLine &, int, uint64_t key, int slot) { votes()[slot] = key; }
+    static __device__ __forceinline__ bool empty(int u) { return votes()[u] == 0; }
+    static __device__ __forceinline__ bool same(int u, int v) { return votes()[u] == votes()[v]; }
 
-    // the tally: per slot the number of slots with the same payload and the OR of their direction bits
-    if ((int)threadIdx.x < nv) {
-        const uint64_t key = votes[threadIdx.x];
-        int cnt = 0, mask = 0;
-        if (key)
-            for (int u = 0; u < nv; ++u)
-                if (votes[u] == key) { ++cnt; mask |= 1 << ((u >> 1) & 1); }
-        tally[threadIdx.x] = cnt | mask << 16;
-    }
-    __syncthreads();
-    if (wave == 0) {                                                            // every lane walks the table (LDS broadcasts)
-        int best = 0, at = -1;
-        for (int u = 0; u < nv; ++u) {
-            const int c = tally[u] & 0xffff;
-            if (c > best) { best = c; at = u; }
-        }
-        uint64_t key = at >= 0 ? votes[at] : 0;
-        for (int u = 0; u < nv; ++u)
-            if (key && (tally[u] & 0xffff) == best && votes[u] != key) { key = 0; break; }   // another payload has as many
-        if (best < P.min_votes) key = 0;
-        if (lane < 16) {
+    // every lane of wave 0 walks the table (LDS broadcasts); lanes 0..15 store the row
+    static __device__ __forceinline__ void emit(const int32_t *tally, int nv, int min_votes, int tid, int32_t *row)
+    {
+        if (tid >= 64) return;
+        int best;
+        const int at = dc_winner<DcRetail>(tally, nv, min_votes, best);
+        const uint64_t key = at >= 0 ? votes()[at] : 0;
+        if (tid < 16) {
             int v;
-            if (lane == 0) v = (int)(key >> 52);
-            else if (lane == 1) v = key ? best : 0;
-            else if (lane == 2) v = key ? tally[at] >> 16 : 0;
+            if (tid == 0) v = (int)(key >> 52);
+            else if (tid == 1) v = key ? best : 0;
+            else if (tid == 2) v = key ? tally[at] >> 16 : 0;
             else {
-                const int nib = key ? (int)((key >> (4 * (15 - lane))) & 15ull) : 15;
+                const int nib = key ? (int)((key >> (4 * (15 - tid))) & 15ull) : 15;
                 v = nib == 15 ? -1 : nib;
             }
-            results[(int64_t)slot * 16 + lane] = v;
+            row[tid] = v;
         }
     }
-}
+
+    static int check_results(const char *, const void *) { return 0; }
+    static int check_symbologies(const char *who, int symbologies)
+    {
+        UBD_REQUIRE(symbologies >= 1 && symbologies <= 3, "%s: symbologies must be 1..3 (bit 0 EAN-13, bit 1 EAN-8; bit 2, Code 128, is read by ubd_decode_text_patches), got %d", who, symbologies);
+        return 0;
+    }
+};
 
 extern "C" int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                                   const ubd_decode_params *params, int32_t *results, void *stream)
 {
-    UBD_REQUIRE(patches, "ubd_decode_patches: patches is null");
-    UBD_REQUIRE(counts, "ubd_decode_patches: counts is null");
-    UBD_REQUIRE(params, "ubd_decode_patches: params is null");
-    UBD_REQUIRE(results, "ubd_decode_patches: results is null");
-    UBD_REQUIRE(n >= 1, "ubd_decode_patches: n must be >= 1, got %d", n);
-    UBD_REQUIRE(cap >= 1, "ubd_decode_patches: cap must be >= 1, got %d", cap);
-    UBD_REQUIRE(patch_h >= 1 && patch_h <= DC_MAX_H, "ubd_decode_patches: patch_h must be 1..%d, got %d", DC_MAX_H, patch_h);
-    UBD_REQUIRE(patch_w >= DC_MIN_W && patch_w <= DC_MAX_W, "ubd_decode_patches: patch_w must be %d..%d, got %d", DC_MIN_W, DC_MAX_W, patch_w);
-    UBD_REQUIRE(channels == 1 || channels == 3, "ubd_decode_patches: channels must be 1 or 3, got %d", channels);
-    const ubd_decode_params P = *params;
-    UBD_REQUIRE(P.symbologies >= 1 && P.symbologies <= 3, "ubd_decode_patches: symbologies must be 1..3 (bit 0 EAN-13, bit 1 EAN-8; bit 2, Code 128, is read by ubd_decode_text_patches), got %d", P.symbologies);
-    UBD_REQUIRE(P.scan_rows >= 1 && P.scan_rows <= DC_MAX_ROWS, "ubd_decode_patches: scan_rows must be 1..%d, got %d", DC_MAX_ROWS, P.scan_rows);
-    UBD_REQUIRE(P.band >= 0 && P.band <= 8, "ubd_decode_patches: band must be 0..8, got %d", P.band);
-    UBD_REQUIRE(P.window >= 1 && P.window <= 64, "ubd_decode_patches: window must be 1..64, got %d", P.window);
-    UBD_REQUIRE(P.contrast >= 0 && P.contrast <= 255, "ubd_decode_patches: contrast must be 0..255, got %d", P.contrast);
-    UBD_REQUIRE(P.quiet >= 0 && P.quiet <= 16, "ubd_decode_patches: quiet must be 0..16, got %d", P.quiet);
-    UBD_REQUIRE(P.min_votes >= 1 && P.min_votes <= 2 * P.scan_rows, "ubd_decode_patches: min_votes must be 1..2 * scan_rows = %d, got %d",
-                2 * P.scan_rows, P.min_votes);
-    UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "ubd_decode_patches: n * cap = %d * %d is not below 2^31", n, cap);
-    const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
-    const size_t lds = DC_TABLE_BYTES + dc_lines_bytes(patch_w);                          // <= 1536 + 49152 bytes
-    if (channels == 3)
-        hipLaunchKernelGGL(decode_kernel<3>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, results);
-    else
-        hipLaunchKernelGGL(decode_kernel<1>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, results);
-    UBD_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dc_decode<DcRetail>("ubd_decode_patches", patches, counts, n, cap, patch_h, patch_w, channels, params, results, stream);
 }

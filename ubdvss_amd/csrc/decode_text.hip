@@ -13,17 +13,16 @@
 //     <= 105 + 102 * (61 * 62 / 2) = 192987.
 // No division is left: the floors of the character, stop-bar and quiet-zone rules are taken by comparing products.
 //
-// Shape: that of decode.hip.  One workgroup of DC_WAVES waves per patch slot; a workgroup whose slot holds no object returns
-// after one load of counts[i].  One wave per scan line, DC_WAVES lines per round, profile, threshold and edges from
-// decode_scan.h, stages separated by uniform workgroup barriers.  Before round 0 the 107 patterns (immediates, one hex digit
-// per run) are spread into a table of 6^4 entries in LDS, key ((E0 - 2) * 6 + (E1 - 2)) * 6 .. -> value | V << 8 (0xFFFF: no
-// pattern); the 107 keys are distinct, so no two lanes write one entry.  Candidates take one lane per start edge, 64 starts a
-// step in rising order; almost every lane ends at the start-character test.  A lane walks its candidate without keeping the
-// values (count, running check sum and last value are enough to accept it); the first step that holds a valid candidate ends
-// the search, and its lowest lane decodes the characters once more and writes count and values into the 64-byte vote slot of
-// (line, direction).  Each slot is written by at most one lane, so the result does not depend on the order in which waves run.
-// The tally compares whole slots (16 dwords; the count in byte 0 and zeroes behind the values make equal slots equal payloads).
-// Thread 0 expands the winner's text into a 128-byte row in LDS, which leaves as 32 dword stores.
+// Shape: that of decode_scan.h, which holds the kernel (dc_decode_kernel: prologue, rounds, search, tally, winner rule) and the
+// host side of the entry point (dc_decode); decode.hip runs the same two with its own policy.  This file holds the patterns,
+// the character and candidate rules (tx_distance .. tx_expand, tx_same) and the policy TxText.  Before round 0 the 107 patterns
+// (one hex digit per run) are spread into a table of 6^4 entries in LDS, key ((E0 - 2) * 6 + (E1 - 2)) * 6 .. -> value | V << 8
+// (0xFFFF: no pattern); the 107 keys are distinct, so no two lanes write one entry.  Of the lanes of a search step almost every
+// one ends at the start-character test.  A lane walks its candidate without keeping the values (count, running check sum and
+// last value are enough to accept it); the lane that votes decodes the characters once more and writes count and values into the
+// 64-byte vote slot of (line, direction).  The tally compares whole slots (16 dwords; the count in byte 0 and zeroes behind the
+// values make equal slots equal payloads).  Thread 0 expands the winner's text into a 128-byte row in LDS, which leaves as 32
+// dword stores.
 // LDS: 4096 (votes) + 256 (tally) + 2592 (key table) + 128 (row) + at most 49152 (lines) = 56224 bytes.
 #include "decode_scan.h"
 
@@ -163,129 +162,77 @@ static __device__ __forceinline__ bool tx_same(const uint32_t *a, const uint32_t
     return same;
 }
 
-template <int C>
-__global__ __launch_bounds__(DC_THREADS) void decode_text_kernel(const uint8_t *__restrict__ patches, const int32_t *__restrict__ counts, int cap,
-                                                                 int ph, int pw, ubd_decode_params P, uint32_t *__restrict__ results)
-{
-    extern __shared__ __align__(16) unsigned char tx_smem[];
-    const int slot = (int)blockIdx.x;                                           // n * cap < 2^31 (checked on the host)
-    const int i = slot / cap, j = slot - i * cap;
-    if (j >= counts[i]) return;                                                 // j < cap already
-    uint32_t *votes = (uint32_t *)tx_smem;
-    int32_t *tally = (int32_t *)(tx_smem + TX_OFF_TALLY);
-    uint16_t *keys = (uint16_t *)(tx_smem + TX_OFF_KEYS);
-    uint32_t *row = (uint32_t *)(tx_smem + TX_OFF_ROW);
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint8_t *src = patches + (int64_t)slot * ph * pw * C;
-    const int S = P.scan_rows, nv = 2 * S;
+// The policy of dc_decode_kernel (decode_scan.h).  LDS tables: the vote table, the tally, the key table and the result row.
+struct TxText {
+    typedef uint32_t Word;
+    static constexpr int ROW_WORDS = TX_ROW / 4, SYMS = 1, SLOT_BYTES = TX_SLOT, OFF_TALLY = TX_OFF_TALLY, TABLE_BYTES = TX_TABLE_BYTES;
 
-    for (int t = tid; t < nv * (TX_SLOT / 4); t += DC_THREADS) votes[t] = 0;
-    for (int t = tid; t < TX_KEYS / 2; t += DC_THREADS) ((uint32_t *)keys)[t] = 0xFFFFFFFFu;
-    if (tid < TX_ROW / 4) row[tid] = tid < 2 ? 0u : 0xFFFFFFFFu;                // the row of "none"
-    __syncthreads();
-    if (tid < 107) {
-        const uint32_t p = tx_patterns[tid];
-        int n[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) n[k] = (int)((p >> (4 * (5 - k))) & 15u);
-        const int key = (((n[0] + n[1] - 2) * 6 + (n[1] + n[2] - 2)) * 6 + (n[2] + n[3] - 2)) * 6 + (n[3] + n[4] - 2);   // sums of two widths: 2..7 for these patterns
-        keys[key] = (uint16_t)(tid | (n[0] + n[2] + n[4]) << 8);
-    }                                                                           // ordered before the first candidate by the barriers of round 0
+    static __device__ __forceinline__ uint32_t *votes(int u) { return (uint32_t *)dc_smem + u * (TX_SLOT / 4); }
+    static __device__ __forceinline__ uint16_t *keys() { return (uint16_t *)(dc_smem + TX_OFF_KEYS); }
+    static __device__ __forceinline__ uint32_t *lds_row() { return (uint32_t *)(dc_smem + TX_OFF_ROW); }
 
-    for (int k0 = 0; k0 < S; k0 += DC_WAVES) {
-        const int k = k0 + wave;
-        const bool on = k < S;                                                  // uniform over the wave
-        int32_t *pe;
-        int n_edges, l2d0;
-        dc_scan_line<C>(src, ph, pw, k, S, on, wave, lane, P, tx_smem + TX_TABLE_BYTES, pe, n_edges, l2d0);
+    // the key table of the 107 patterns and the row of "none"
+    static __device__ __forceinline__ void setup(int tid)
+    {
+        for (int t = tid; t < TX_KEYS / 2; t += DC_THREADS) ((uint32_t *)keys())[t] = 0xFFFFFFFFu;
+        if (tid < TX_ROW / 4) lds_row()[tid] = tid < 2 ? 0u : 0xFFFFFFFFu;
         __syncthreads();
-        if (on) {                                                               // the candidates
-            DcLine L;
-            L.e = pe; L.n = n_edges; L.flip = 256 * (pw - 1); L.l2d0 = l2d0;
-            const int starts = n_edges - 25;                                    // start, one data, check and stop take the edges i .. i + 25
-            for (int dir = 0; dir < 2; ++dir) {
-                L.rev = dir == 1;
-                for (int ib = 0; ib < starts; ib += 64) {
-                    const int c = ib + lane;
-                    const int cnt = c < starts ? tx_candidate(L, c, P.quiet, keys) : 0;
-                    const unsigned long long valid = __ballot(cnt != 0);
-                    if (valid) {                                                // the lowest start index of this (line, direction)
-                        if (lane == __ffsll((long long)valid) - 1) tx_write_values(L, c, cnt, keys, (uint8_t *)(votes + (k * 2 + dir) * (TX_SLOT / 4)));
-                        break;
-                    }
-                }
+        if (tid < 107) {
+            const uint32_t p = tx_patterns[tid];
+            int n[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) n[k] = (int)((p >> (4 * (5 - k))) & 15u);
+            const int key = (((n[0] + n[1] - 2) * 6 + (n[1] + n[2] - 2)) * 6 + (n[2] + n[3] - 2)) * 6 + (n[3] + n[4] - 2);   // sums of two widths: 2..7 for these patterns
+            keys()[key] = (uint16_t)(tid | (n[0] + n[2] + n[4]) << 8);
+        }
+    }
+    static __device__ __forceinline__ int starts(const ubd_decode_params &, int, int n_edges)
+    {
+        return n_edges - 25;                                                    // start, one data, check and stop take the edges i .. i + 25
+    }
+    static __device__ __forceinline__ int candidate(const DcLine &L, int i, int, int quiet) { return tx_candidate(L, i, quiet, keys()); }
+    static __device__ __forceinline__ void vote(const DcLine &L, int i, int cnt, int slot) { tx_write_values(L, i, cnt, keys(), (uint8_t *)votes(slot)); }
+    static __device__ __forceinline__ bool empty(int u) { return (votes(u)[0] & 0xFFu) == 0; }
+    static __device__ __forceinline__ bool same(int u, int v) { return tx_same(votes(u), votes(v)); }
+
+    // thread 0 turns the row of "none" into the winner's, 32 threads store it
+    static __device__ __forceinline__ void emit(const int32_t *tally, int nv, int min_votes, int tid, uint32_t *row)
+    {
+        if (tid == 0) {
+            int best;
+            const int at = dc_winner<TxText>(tally, nv, min_votes, best);
+            if (at >= 0) {
+                const uint8_t *win = (const uint8_t *)votes(at);
+                uint8_t *bytes = (uint8_t *)lds_row();
+                const int cnt = win[0];
+                bytes[0] = 128;
+                bytes[1] = (uint8_t)best;                                       // <= 2 * 32
+                bytes[2] = (uint8_t)(tally[at] >> 16);
+                bytes[3] = (uint8_t)tx_expand(win, bytes + 8);                  // T <= 120: bytes 8..127
+                bytes[4] = win[2] == 102 ? 1 : 0;                               // the first data character is FNC1
+                bytes[5] = (uint8_t)(cnt - 2);
+                bytes[6] = win[1];
+                bytes[7] = win[cnt];
             }
         }
-        __syncthreads();                                                        // the next round overwrites the edges
+        __syncthreads();                                                        // uniform: every thread of the workgroup is here
+        if (tid < TX_ROW / 4) row[tid] = lds_row()[tid];
     }
 
-    // the tally: per slot the number of slots with the same payload and the OR of their direction bits
-    if (tid < nv) {
-        const uint32_t *mine = votes + tid * (TX_SLOT / 4);
-        int cnt = 0, mask = 0;
-        if (mine[0] & 0xFFu)
-            for (int u = 0; u < nv; ++u)
-                if (tx_same(mine, votes + u * (TX_SLOT / 4))) { ++cnt; mask |= 1 << (u & 1); }
-        tally[tid] = cnt | mask << 16;
+    static int check_results(const char *who, const void *results)
+    {
+        UBD_REQUIRE(((uintptr_t)results & 3) == 0, "%s: results must be aligned to 4 bytes", who);
+        return 0;
     }
-    __syncthreads();
-    if (tid == 0) {
-        int best = 0, at = -1;
-        for (int u = 0; u < nv; ++u) {
-            const int c = tally[u] & 0xffff;
-            if (c > best) { best = c; at = u; }
-        }
-        bool won = at >= 0 && best >= P.min_votes;
-        for (int u = 0; won && u < nv; ++u)
-            if ((tally[u] & 0xffff) == best && !tx_same(votes + at * (TX_SLOT / 4), votes + u * (TX_SLOT / 4))) won = false;   // another payload has as many
-        if (won) {
-            const uint8_t *win = (const uint8_t *)(votes + at * (TX_SLOT / 4));
-            uint8_t *bytes = (uint8_t *)row;
-            const int cnt = win[0];
-            bytes[0] = 128;
-            bytes[1] = (uint8_t)best;                                           // <= 2 * 32
-            bytes[2] = (uint8_t)(tally[at] >> 16);
-            bytes[3] = (uint8_t)tx_expand(win, bytes + 8);                      // T <= 120: bytes 8..127
-            bytes[4] = win[2] == 102 ? 1 : 0;                                   // the first data character is FNC1
-            bytes[5] = (uint8_t)(cnt - 2);
-            bytes[6] = win[1];
-            bytes[7] = win[cnt];
-        }
+    static int check_symbologies(const char *who, int symbologies)
+    {
+        UBD_REQUIRE(symbologies == 4, "%s: symbologies must be 4 (bit 2 Code 128; bits 0 and 1 are ubd_decode_patches'), got %d", who, symbologies);
+        return 0;
     }
-    __syncthreads();
-    if (tid < TX_ROW / 4) results[(int64_t)slot * (TX_ROW / 4) + tid] = row[tid];
-}
+};
 
 extern "C" int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                                        const ubd_decode_params *params, uint8_t *results, void *stream)
 {
-    UBD_REQUIRE(patches, "ubd_decode_text_patches: patches is null");
-    UBD_REQUIRE(counts, "ubd_decode_text_patches: counts is null");
-    UBD_REQUIRE(params, "ubd_decode_text_patches: params is null");
-    UBD_REQUIRE(results, "ubd_decode_text_patches: results is null");
-    UBD_REQUIRE(((uintptr_t)results & 3) == 0, "ubd_decode_text_patches: results must be aligned to 4 bytes");
-    UBD_REQUIRE(n >= 1, "ubd_decode_text_patches: n must be >= 1, got %d", n);
-    UBD_REQUIRE(cap >= 1, "ubd_decode_text_patches: cap must be >= 1, got %d", cap);
-    UBD_REQUIRE(patch_h >= 1 && patch_h <= DC_MAX_H, "ubd_decode_text_patches: patch_h must be 1..%d, got %d", DC_MAX_H, patch_h);
-    UBD_REQUIRE(patch_w >= DC_MIN_W && patch_w <= DC_MAX_W, "ubd_decode_text_patches: patch_w must be %d..%d, got %d", DC_MIN_W, DC_MAX_W, patch_w);
-    UBD_REQUIRE(channels == 1 || channels == 3, "ubd_decode_text_patches: channels must be 1 or 3, got %d", channels);
-    const ubd_decode_params P = *params;
-    UBD_REQUIRE(P.symbologies == 4, "ubd_decode_text_patches: symbologies must be 4 (bit 2 Code 128; bits 0 and 1 are ubd_decode_patches'), got %d",
-                P.symbologies);
-    UBD_REQUIRE(P.scan_rows >= 1 && P.scan_rows <= DC_MAX_ROWS, "ubd_decode_text_patches: scan_rows must be 1..%d, got %d", DC_MAX_ROWS, P.scan_rows);
-    UBD_REQUIRE(P.band >= 0 && P.band <= 8, "ubd_decode_text_patches: band must be 0..8, got %d", P.band);
-    UBD_REQUIRE(P.window >= 1 && P.window <= 64, "ubd_decode_text_patches: window must be 1..64, got %d", P.window);
-    UBD_REQUIRE(P.contrast >= 0 && P.contrast <= 255, "ubd_decode_text_patches: contrast must be 0..255, got %d", P.contrast);
-    UBD_REQUIRE(P.quiet >= 0 && P.quiet <= 16, "ubd_decode_text_patches: quiet must be 0..16, got %d", P.quiet);
-    UBD_REQUIRE(P.min_votes >= 1 && P.min_votes <= 2 * P.scan_rows, "ubd_decode_text_patches: min_votes must be 1..2 * scan_rows = %d, got %d",
-                2 * P.scan_rows, P.min_votes);
-    UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "ubd_decode_text_patches: n * cap = %d * %d is not below 2^31", n, cap);
-    const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
-    const size_t lds = TX_TABLE_BYTES + dc_lines_bytes(patch_w);                // <= 7072 + 49152 bytes
-    if (channels == 3)
-        hipLaunchKernelGGL(decode_text_kernel<3>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, (uint32_t *)results);
-    else
-        hipLaunchKernelGGL(decode_text_kernel<1>, grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, (uint32_t *)results);
-    UBD_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dc_decode<TxText>("ubd_decode_text_patches", patches, counts, n, cap, patch_h, patch_w, channels, params, results, stream);
 }
