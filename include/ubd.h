@@ -430,7 +430,8 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 typedef struct ubd_decode_params {
     int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8: ubd_decode_patches takes 1..3; bit 2 Code 128:
-                                        ubd_decode_text_patches takes 4.  The bits are numbered over all families */
+                                        ubd_decode_text_patches takes 4; bit 3 ITF, bit 4 Code 39: ubd_decode_width_patches
+                                        takes 8, 16 or 24.  The bits are numbered over all families */
     int32_t scan_rows;               /* S, 1..32        default 8  */
     int32_t band;                    /* b, 0..8         default 1  */
     int32_t window;                  /* R, 1..64        default 16 */
@@ -490,6 +491,61 @@ int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                             const ubd_decode_params *params, uint8_t *results, void *stream);
+
+/* --- decoding of the object patches: Interleaved 2 of 5 (ITF) / Code 39 ---------------
+ * The third family behind ubd_extract_objects: the two-width codes, in which every bar and every space is either narrow or
+ * wide: the digits of an ITF symbol (ITF-14 included) or the characters of a Code 39 symbol in every patch, 128 bytes per
+ * object.  The contract is that of ubd_decode_text_patches (device patches and counts as ubd_extract_objects writes them, params
+ * a HOST pointer read before the call returns, slots j >= min(counts[i], cap) neither read nor written), the params struct is
+ * the same, and `symbologies` must be 8 (bit 3, ITF), 16 (bit 4, Code 39) or 24 (both).  Integer arithmetic only, and no rule
+ * divides; the numpy restatement tests/width_decode_oracle.py is matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 25 (ITF) or 39 (Code 39), or 0 for none; [1] votes; [2]
+ *     direction mask (bit 0 read left to right, bit 1 read right to left: the patch is the half-turned one); [3] T, the number of
+ *     text elements; [4] flags, bit 0: the optional check character holds (below; informational, it never rejects); [5..7] 0;
+ *     [8 .. 8 + T) the ASCII codes of the elements; the rest 0xFF.  For "none" bytes 0..7 are 0 and bytes 8..127 are 0xFF.
+ * Per patch:
+ *   luma, scan lines, local threshold, edges and the mirrored list for reading right to left: those of ubd_decode_patches.
+ *   narrow or wide: over a group of runs with the least run lo and the greatest run hi, a run w is wide iff 2 w > lo + hi.
+ *     The group is valid only if it holds a wide run and 2 * (least wide run) >= 3 * (greatest narrow run).
+ *   ITF pair: ten runs (a bar first) of sum S.  The five bars are one group and the five spaces another, classified
+ *     separately; each must be valid, hold exactly two wide runs and show one of the patterns of the digits 0..9:
+ *     nnWWn WnnnW nWnnW WWnnn nnWnW WnWnn nWWnn nnnWW WnnWn nWnWn.  The bars give the first digit, the spaces the second.
+ *   ITF candidate at a light-to-dark edge i of the direction's list e (E edges):
+ *     1. the start is the four runs at the edges i..i+4 (edge i+4 must exist), of sum S4;
+ *     2. if i >= 1: 4 (e_i - e_(i-1)) >= QZ * S4;
+ *     3. pairs at j = i + 4, i + 14, ..: if the edges j..j+10 exist, the ten runs decode to a pair and, from the second pair
+ *        on, 7 S_prev <= 8 S <= 9 S_prev, the pair is data (data before stop); otherwise j must be the stop.  A 31st pair
+ *        rejects the candidate, and so do fewer than 3;
+ *     4. every run w of the start must satisfy lo <= 2 w <= lo + hi with lo, hi of the FIRST pair's group of w's colour;
+ *     5. the stop is the runs at the edges j..j+3 (edge j+3 must exist), against lo, hi of the LAST pair's groups: the first
+ *        bar wide (2 w > lo + hi of the bars), the space and the last bar with lo <= 2 w <= lo + hi of their colour; if edge
+ *        j+4 exists: 2 (e_(j+4) - e_(j+3)) >= QZ * (space + last bar).
+ *     The T = 2 * pairs elements are the digits as ASCII.  Flag bit 0 (the GS1 check digit):
+ *     (d_(T-1) + sum over k < T-1 of d_k * (3 if T-1-k is odd else 1)) % 10 == 0; 15400141288763 holds it.
+ *   Code 39 character: nine runs (a bar first) of sum S, one group; it must be valid, hold exactly three wide runs and show a
+ *     pattern of the table; N6 is the sum of its six narrow runs.  Table, with the bar columns 1..10 = WnnnW nWnnW WWnnn nnWnW
+ *     WnWnn nWWnn nnnWW WnnWn nWnWn nnWWn (bars and spaces interleaved, a bar first): the characters 1 2 3 4 5 6 7 8 9 0 take
+ *     the columns 1..10 with the spaces nWnn; A..J with nnWn; K..T with nnnW; U V W X Y Z - . space * with Wnnn; $ / + % have
+ *     five narrow bars and the spaces WWWn WWnW WnWW nWWW.  So 1 = WnnWnnnnW, A = WnnnnWnnW, * = nWnnWnWnn, % = nnnWnWnWn.
+ *     Check values: 0-9 -> 0..9, A-Z -> 10..35, - . space $ / + % -> 36..42.
+ *   Code 39 candidate at a light-to-dark edge i:
+ *     1. the character at i (edges i..i+9) is *; S_prev and N6 are its;
+ *     2. if i >= 1: 6 (e_i - e_(i-1)) >= QZ * N6;
+ *     3. characters at j = i + 10, i + 20, ..: the edges j..j+9 must exist; the gap g = e_j - e_(j-1) must satisfy
+ *        N6_prev <= 12 g and 2 g <= S_prev; the width 7 S_prev <= 8 S <= 9 S_prev; the character must decode.  A * is the stop,
+ *        every other character is data; a 61st data character rejects the candidate, and so does a stop behind none;
+ *     4. if edge j+10 exists behind the stop: 6 (e_(j+10) - e_(j+9)) >= QZ * N6 of the stop.
+ *     The T elements are the data characters as ASCII; pairs of Full ASCII are not interpreted.  Flag bit 0 (the modulo-43
+ *     check character): T >= 2 and (the sum of the first T-1 values) % 43 == the last value; "CODE 39" sums to 113, its check
+ *     character is R (27).
+ *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
+ *     (symbology, all elements), compared in full.  The payload with the most votes wins, its mask is the OR of the directions
+ *     that voted for it; fewer than min_votes, or another payload with as many votes: none.
+ * Limits (non-zero return, ubd_last_error begins with "ubd_decode_width_patches", nothing launched, nothing written): those
+ * of ubd_decode_text_patches, with symbologies 8, 16 or 24.
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
+int ubd_decode_width_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                             const ubd_decode_params *params, uint8_t *results, void *stream);
 
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one

@@ -1,5 +1,5 @@
-"""Both patch decoders (ubd_decode_patches, ubd_decode_text_patches) on the same patches on one MI355X: what reading Code 128 as
-well costs a caller of ModelRunner.predict_decoded(symbologies=7).
+"""The three patch decoders (ubd_decode_patches, ubd_decode_text_patches, ubd_decode_width_patches) in one run on one MI355X: what
+reading Code 128, and ITF and Code 39, as well costs a caller of ModelRunner.predict_decoded(symbologies=7 or 31).
 
 The workload: n = 32 images, cap = 4, every slot filled, one 64 x 256 RGB patch per object at 2 pixels per module with Gaussian
 noise (sigma 6, seeded), every other one half-turned: in turn an EAN-13, a Code 128 of five to seven characters, an EAN-8 and a
@@ -8,6 +8,9 @@ of tests/text_decode_oracle.py).  Prints one JSON line per kernel:
 HIP-event time per call at the default parameters (5 warm-up calls; windows of --calls back-to-back calls; median, minimum and
 90th percentile of --iters windows), patches and counts already in device memory, and how many of the objects of the kernel's
 own family decoded to what was drawn (the other family's must all read as none).
+The two-width kernel is timed twice: on those patches, which hold nothing of its family (the cost of looking), and on a workload
+of its own of the same shape (``width_workload``: in turn an ITF of six to ten digits and a Code 39 of two to four characters,
+2 pixels per narrow run, wide runs of 5, the same noise, every other one half-turned).
 Usage: python tools/bench_decode_text.py [--iters 200] [--calls 20]
 """
 import argparse
@@ -25,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import decode_cases as dc  # noqa: E402
 import text_decode_cases as tc  # noqa: E402
 import text_decode_oracle as to  # noqa: E402
+import width_decode_cases as wc  # noqa: E402
 from ubdvss_amd import _lib, barcode_decoder  # noqa: E402
 
 ALPHABET = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz-/.+"
@@ -54,6 +58,27 @@ def workload(n=32, cap=4, ph=64, pw=256, seed=1):
                 grey = grey[::-1, ::-1]
             patches[i, j] = grey[:, :, None]
     return patches, kinds, drawn
+
+
+def width_workload(n=32, cap=4, ph=64, pw=256, seed=2):
+    """-> (patches (n, cap, ph, pw, 3), drawn (n, cap): the digits of the ITF or the characters of the Code 39)"""
+    rng = np.random.default_rng(seed)
+    patches = np.zeros((n, cap, ph, pw, 3), np.uint8)
+    drawn = np.empty((n, cap), object)
+    for i in range(n):
+        for j in range(cap):
+            if (i + j) % 2 == 0:
+                drawn[i, j] = "".join(str(int(d)) for d in rng.integers(0, 10, 2 * int(rng.integers(3, 6))))
+                mods = wc.itf_modules(drawn[i, j], 2, 5)
+            else:
+                drawn[i, j] = "".join(wc.C39_CHARS[int(k)] for k in rng.integers(0, 43, int(rng.integers(2, 5))))
+                mods = wc.c39_modules(drawn[i, j], 2, 5)
+            row = tc.flat_row_modules([mods], 1, pw, (pw - len(mods)) // 2).astype(np.float64)
+            grey = np.clip(np.rint(row[None, :] + rng.normal(0, 6.0, (ph, pw))), 0, 255).astype(np.uint8)
+            if j % 2:
+                grey = grey[::-1, ::-1]
+            patches[i, j] = grey[:, :, None]
+    return patches, drawn
 
 
 def time_calls(call, iters, calls):
@@ -95,16 +120,31 @@ def main():
     def call_text():
         _lib.check(lib.ubd_decode_text_patches(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p_text),
                                                text.data_ptr(), stream), "ubd_decode_text_patches")
+    width = torch.zeros((n, cap, 128), dtype=torch.uint8, device="cuda")
+    p_width = barcode_decoder.make_params(symbologies=barcode_decoder.ITF | barcode_decoder.CODE39)
+    host_own, drawn_own = width_workload(n, cap, ph, pw)
+    own_patches = torch.from_numpy(host_own).cuda()
+
+    def call_width(which=patches):
+        _lib.check(lib.ubd_decode_width_patches(which.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p_width),
+                                                width.data_ptr(), stream), "ubd_decode_width_patches")
     t_retail, t_text = time_calls(call_retail, args.iters, args.calls), time_calls(call_text, args.iters, args.calls)
+    t_width = time_calls(call_width, args.iters, args.calls)
+    got_width = barcode_decoder.width_results_to_records(width, counts)
+    t_own = time_calls(lambda: call_width(own_patches), args.iters, args.calls)
+    got_own = barcode_decoder.width_results_to_records(width, counts)
     got_retail = barcode_decoder.results_to_records(retail, counts)
     got_text = barcode_decoder.text_results_to_records(text, counts)
     slots = [(i, j) for i in range(n) for j in range(cap)]
     for name, times, got, kind, right in (
             ("ubd_decode_patches", t_retail, got_retail, "retail", lambda r, d: r.text == "".join(map(str, d))),
-            ("ubd_decode_text_patches", t_text, got_text, "text", lambda r, d: r.elements == tuple(to.text_elements(d)))):
-        own = [s for s in slots if kinds[s] == kind]
-        correct = sum(got[i][j] is not None and right(got[i][j], drawn[i, j]) for i, j in own)
-        stray = sum(got[i][j] is not None for i, j in slots if kinds[i, j] != kind)
+            ("ubd_decode_text_patches", t_text, got_text, "text", lambda r, d: r.elements == tuple(to.text_elements(d))),
+            ("ubd_decode_width_patches", t_width, got_width, "width", None),
+            ("ubd_decode_width_patches_own_workload", t_own, got_own, "own", lambda r, d: r.text == d)):
+        own = slots if kind == "own" else [s for s in slots if kinds[s] == kind]
+        truth = drawn_own if kind == "own" else drawn
+        correct = sum(got[i][j] is not None and right(got[i][j], truth[i, j]) for i, j in own)
+        stray = 0 if kind == "own" else sum(got[i][j] is not None for i, j in slots if kinds[i, j] != kind)
         us = float(np.median(times))
         print(json.dumps({"leg": f"{name}_n{n}_cap{cap}_{ph}x{pw}x{c}", "iters": args.iters, "calls_per_window": args.calls,
                           "us_median": round(us, 1), "us_min": round(float(np.min(times)), 1),

@@ -94,6 +94,7 @@ SIGNATURES = {
     "ubd_extract_objects": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, ctypes.c_double, _vp, _i, _i, _vp, _vp]),
     "ubd_decode_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_decode_text_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
+    "ubd_decode_width_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_photometric_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_noise_alpha_images": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _vp]),
     "ubd_evaluate_accumulator_bytes": (_sz, [_i, _i]),

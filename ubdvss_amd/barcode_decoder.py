@@ -3,7 +3,9 @@
 patch.  The rules are written out in include/ubd.h; tests/decode_oracle.py restates them and the device matches it bit for bit.
 A patch may be the half-turned one (object_patches.py): both reading directions are tried and the result says which one read.
 The text of Code 128 / GS1-128 symbols is a second kernel with a result row of its own (``ubd_decode_text_patches``, 128 bytes
-per object; tests/text_decode_oracle.py): ``decode_text_patches_on_device`` and ``text_results_to_records``."""
+per object; tests/text_decode_oracle.py): ``decode_text_patches_on_device`` and ``text_results_to_records``.  The two-width codes,
+ITF and Code 39, are a third (``ubd_decode_width_patches``, 128 bytes per object; tests/width_decode_oracle.py):
+``decode_width_patches_on_device`` and ``width_results_to_records``."""
 import collections
 import ctypes
 
@@ -14,9 +16,11 @@ from . import _lib
 
 EAN13, EAN8 = 1, 2                                       # bits of ``symbologies``
 CODE128 = 4                                              # bit 2: read by ubd_decode_text_patches, not by ubd_decode_patches
+ITF, CODE39 = 8, 16                                      # bits 3 and 4: read by ubd_decode_width_patches
 DEFAULT_PARAMS = dict(symbologies=EAN13 | EAN8, scan_rows=8, band=1, window=16, contrast=24, quiet=3, min_votes=2)
 RESULT_INTS = 16
 TEXT_RESULT_BYTES = 128
+WIDTH_RESULT_BYTES = 128
 FNC1, FNC2, FNC3, FNC4 = 0xF1, 0xF2, 0xF3, 0xF4          # text elements of a Code 128 result beside the ASCII codes 0..127
 
 DecodedBarcode = collections.namedtuple("DecodedBarcode", ["symbology", "text", "votes", "upside_down", "is_upc_a"])
@@ -29,6 +33,11 @@ DecodedText.__doc__ = """One decoded Code 128 object.  symbology: 'Code 128'; te
 (it sets gs1), any later FNC1 as '\\x1d', FNC2..FNC4 left out; votes and upside_down as in DecodedBarcode; gs1: the first data
 character is FNC1 (GS1-128); elements: every text element as a tuple of integers, ASCII codes 0..127 and 0xF1..0xF4 for FNC1..FNC4."""
 
+DecodedWidth = collections.namedtuple("DecodedWidth", ["symbology", "text", "votes", "upside_down", "checked"])
+DecodedWidth.__doc__ = """One decoded two-width object.  symbology: 'ITF' or 'Code 39'; text: its digits or characters (of a Code 39
+the data between the two '*'; Full ASCII pairs are left as they are); votes and upside_down as in DecodedBarcode; checked: the
+last element is the optional check character of the rest (GS1's modulo 10 for ITF, modulo 43 for Code 39) -- it stays in text."""
+
 
 def make_params(**params):
     """keyword parameters over DEFAULT_PARAMS -> the ``UbdDecodeParams`` of the C entry point; an unknown name is an error"""
@@ -40,7 +49,7 @@ def make_params(**params):
 
 
 def _device_arguments(what, patches, counts):
-    """the checks and conversions both entry points share -> (contiguous patches, device counts, shape)"""
+    """the checks and conversions the entry points share -> (contiguous patches, device counts, shape)"""
     if not torch.cuda.is_available():
         raise RuntimeError(f"{what} needs an MI355X; there is no CPU fallback")
     if not (isinstance(patches, torch.Tensor) and patches.is_cuda and patches.dtype == torch.uint8 and patches.dim() == 5):
@@ -94,6 +103,15 @@ def decode_text_patches_on_device(patches, counts, **params):
                    fill_from=8)
 
 
+def decode_width_patches_on_device(patches, counts, **params):
+    """``patches`` and ``counts`` as for ``decode_patches_on_device``; ``params`` the same keywords, ``symbologies`` defaulting to
+    ITF | CODE39 (``ubd_decode_width_patches`` takes 8, 16 or 24).  Returns the uint8 device tensor (n, cap, 128) of
+    ``ubd_decode_width_patches``: [25, 39 or 0, votes, direction mask, T, flags, 0, 0, 0, T ASCII codes, 0xFF..]; rows of slots
+    that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream; nothing is read back."""
+    return _launch("ubd_decode_width_patches", patches, counts, dict({"symbologies": ITF | CODE39}, **params), WIDTH_RESULT_BYTES,
+                   torch.uint8, fill_from=8)
+
+
 def _records(results, counts, parse):
     """per image the list of ``parse(row)`` over its min(counts[i], cap) result rows; ``parse`` gives None where nothing was read"""
     r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
@@ -111,6 +129,13 @@ def _text_record(row):
     return DecodedText("Code 128", text, votes, mask == 2, gs1, elements)
 
 
+def _width_record(row):
+    code, votes, mask, t, flags = (int(v) for v in row[:5])
+    if code == 0:
+        return None
+    return DecodedWidth("ITF" if code == 25 else "Code 39", "".join(chr(int(v)) for v in row[8:8 + t]), votes, mask == 2, bool(flags & 1))
+
+
 def _retail_record(row):
     code, votes, mask = (int(v) for v in row[:3])
     if code == 0:
@@ -123,6 +148,12 @@ def text_results_to_records(results, counts):
     """(n, cap, 128) results of ``decode_text_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
     min(counts[i], cap) entries, a ``DecodedText`` or None where nothing was read"""
     return _records(results, counts, _text_record)
+
+
+def width_results_to_records(results, counts):
+    """(n, cap, 128) results of ``decode_width_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
+    min(counts[i], cap) entries, a ``DecodedWidth`` or None where nothing was read"""
+    return _records(results, counts, _width_record)
 
 
 def results_to_records(results, counts):

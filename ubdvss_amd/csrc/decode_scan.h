@@ -1,5 +1,6 @@
-// The part of the patch decoders that does not know a symbology.  decode.hip (EAN-13 / UPC-A / EAN-8) and decode_text.hip
-// (Code 128) include it and add a policy struct each (what a policy holds is listed at dc_decode_kernel).  Here are
+// The part of the patch decoders that does not know a symbology.  decode.hip (EAN-13 / UPC-A / EAN-8), decode_text.hip
+// (Code 128) and decode_width.hip (ITF, Code 39) include it and add a policy struct each (what a policy holds is listed at
+// dc_decode_kernel).  Here are
 //   the scan front end: the profile of a scan line, its local threshold and its sub-pixel edges, as the rules at
 //     ubd_decode_patches in include/ubd.h define them (dc_scan_line), and the edge list as one reading direction sees it (DcLine);
 //   the kernel (dc_decode_kernel): slot prologue, round loop, direction loop, the search for the first valid candidate, the
@@ -231,7 +232,7 @@ static int dc_decode(const char *who, const uint8_t *patches, const int32_t *cou
                 P.min_votes);
     UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "%s: n * cap = %d * %d is not below 2^31", who, n, cap);
     const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
-    const size_t lds = Sym::TABLE_BYTES + dc_lines_bytes(patch_w);              // <= 7072 + 49152 bytes
+    const size_t lds = Sym::TABLE_BYTES + dc_lines_bytes(patch_w);              // <= 9376 + 49152 bytes
     typename Sym::Word *rows = (typename Sym::Word *)results;
     if (channels == 3)
         hipLaunchKernelGGL((dc_decode_kernel<3, Sym>), grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, rows);

@@ -286,13 +286,16 @@ class ModelRunner:
         The only extra read per group is the int32 result tensor (n, fullest list of the group, 16).
         With bit 2 of ``symbologies`` (``barcode_decoder.CODE128``; 7 reads every family) the same device patches also go through
         ``decode_text_patches_on_device``, the retail kernel running only if bit 0 or 1 is set: ``decoded[k][j]`` is the retail
-        record if there is one, else the ``DecodedText``, else None, and the uint8 results (n, fullest list, 128) are read too."""
+        record if there is one, else the ``DecodedText``, else None, and the uint8 results (n, fullest list, 128) are read too.
+        Bits 3 and 4 (``barcode_decoder.ITF``, ``CODE39``; 31 reads every family) add ``decode_width_patches_on_device`` in the
+        same way: every requested kernel is launched before the first result is read, and ``decoded[k][j]`` is the retail record,
+        else the ``DecodedText``, else the ``DecodedWidth``, else None.  Bits beyond 0..4 are a ValueError."""
         if not torch.cuda.is_available():
             raise RuntimeError("ModelRunner.predict_decoded needs an MI355X; there is no CPU fallback")
-        from .barcode_decoder import make_params, CODE128
+        from .barcode_decoder import make_params
         symbologies = make_params(**params).symbologies     # an unknown keyword fails before any work
-        if symbologies & CODE128 and symbologies & ~7:
-            raise ValueError(f"symbologies {symbologies}: bits 0..2 (EAN-13, EAN-8, Code 128) are the known families")
+        if symbologies & ~31:
+            raise ValueError(f"symbologies {symbologies}: bits 0..4 (EAN-13, EAN-8, Code 128, ITF, Code 39) are the known families")
         return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)), decode=params)
 
     def _predict_images(self, model, images, batch_size, patch, decode=None):
@@ -344,19 +347,24 @@ class ModelRunner:
 
     @staticmethod
     def _decode_records(on_device, counts, counts_h, decode):
-        """the records of one group's device patches; bit 2 of ``symbologies`` adds the text kernel on the same patches"""
+        """the records of one group's device patches; bit 2 of ``symbologies`` adds the text kernel on the same patches, bits 3
+        and 4 the two-width kernel"""
         from .barcode_decoder import decode_patches_on_device, results_to_records, decode_text_patches_on_device, \
-            text_results_to_records, DEFAULT_PARAMS, CODE128
+            text_results_to_records, decode_width_patches_on_device, width_results_to_records, DEFAULT_PARAMS, EAN13, EAN8, CODE128, \
+            ITF, CODE39
         symbologies = int(decode.get("symbologies", DEFAULT_PARAMS["symbologies"]))
-        if not symbologies & CODE128:
+        if not symbologies & (CODE128 | ITF | CODE39):
             return results_to_records(decode_patches_on_device(on_device, counts, **decode), counts_h)
-        retail = None
-        if symbologies & ~CODE128:                      # both kernels are launched before the first result is read
-            retail = decode_patches_on_device(on_device, counts, **dict(decode, symbologies=symbologies & ~CODE128))
-        text = decode_text_patches_on_device(on_device, counts, **dict(decode, symbologies=CODE128))
-        records = text_results_to_records(text, counts_h)
-        if retail is not None:
-            records = [[a if a is not None else b for a, b in zip(ra, rb)] for ra, rb in zip(results_to_records(retail, counts_h), records)]
+        launched = []                                   # every kernel is launched before the first result is read
+        for bits, launch, to_records in (((EAN13 | EAN8), decode_patches_on_device, results_to_records),
+                                         (CODE128, decode_text_patches_on_device, text_results_to_records),
+                                         ((ITF | CODE39), decode_width_patches_on_device, width_results_to_records)):
+            if symbologies & bits:
+                launched.append((launch(on_device, counts, **dict(decode, symbologies=symbologies & bits)), to_records))
+        records = None
+        for results, to_records in launched:            # in the order of preference: retail, Code 128, two-width
+            more = to_records(results, counts_h)
+            records = more if records is None else [[a if a is not None else b for a, b in zip(ra, rb)] for ra, rb in zip(records, more)]
         return records
 
     def predict_stream(self, model, batches, rescale=False, meta_infos=None, copy_threads=8):
