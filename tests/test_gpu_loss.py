@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import loss_numpy as oloss
-from ubdvss_amd import losses, synthetic
+from ubdvss_amd import _lib, losses, synthetic
 
 pytestmark = pytest.mark.gpu
 
@@ -128,14 +128,14 @@ def _both_forms(yt, yp, num_cus=None):
             os.environ.pop("UBD_LOSS", None); os.environ.pop("UBD_TEST_NUM_CUS", None)
             if form == "chain": os.environ["UBD_LOSS"] = "chain"
             if num_cus: os.environ["UBD_TEST_NUM_CUS"] = str(num_cus)
-            losses._handles.clear()
+            _lib.reset_static_handles()
             l, g = losses.loss_and_grad(yt, yp)
             out.append((l.cpu().numpy(), g.cpu().numpy()))
         finally:
             for k, v in old.items():
                 if v is None: os.environ.pop(k, None)
                 else: os.environ[k] = v
-            losses._handles.clear()
+            _lib.reset_static_handles()
     return out
 
 

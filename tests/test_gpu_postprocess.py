@@ -23,8 +23,8 @@ def front_end(request, monkeypatch):
     of more than 64 vertices take; the other two variants run the wave-uniform register form), "global" = the multi-launch
     global-memory path that larger maps take (UBD_PP_GLOBAL forces it at any size); "lds_512" = the one-launch form in 512-thread
     blocks (UBD_PP_THREADS_512): the block shape the job has when it rides inside the stem kernel."""
-    from ubdvss_amd import segmap_manager
-    segmap_manager._reset_handles()          # the switches are read when a handle is created
+    from ubdvss_amd import _lib
+    _lib.reset_static_handles()          # the switches are read when a handle is created
     monkeypatch.delenv("UBD_PP_GLOBAL", raising=False)
     monkeypatch.delenv("UBD_PP_SPLIT", raising=False)
     monkeypatch.delenv("UBD_PP_SERIAL_TAIL", raising=False)
@@ -37,7 +37,7 @@ def front_end(request, monkeypatch):
         monkeypatch.setenv("UBD_PP_SPLIT", "1")
         monkeypatch.setenv("UBD_PP_SERIAL_TAIL", "1")
     yield request.param
-    segmap_manager._reset_handles()          # no handle created under a switch outlives the test
+    _lib.reset_static_handles()          # no handle created under a switch outlives the test
 
 
 def _model(ncls=0, cin=3):

@@ -225,8 +225,8 @@ def test_loss_alone_many_classes(n_cls, n, h, w):
 @pytest.fixture(params=["lds", "lds_split", "global"])
 def front_end(request, monkeypatch):
     """the code paths of tests/test_gpu_postprocess.py's fixture of the same name (the switches are read when a handle is created)"""
-    from ubdvss_amd import segmap_manager
-    segmap_manager._reset_handles()
+    from ubdvss_amd import _lib
+    _lib.reset_static_handles()
     for k in ("UBD_PP_GLOBAL", "UBD_PP_SPLIT", "UBD_PP_SERIAL_TAIL", "UBD_PP_THREADS_512"):
         monkeypatch.delenv(k, raising=False)
     if request.param == "global":
@@ -234,7 +234,7 @@ def front_end(request, monkeypatch):
     elif request.param == "lds_split":
         monkeypatch.setenv("UBD_PP_SPLIT", "1")
     yield request.param
-    segmap_manager._reset_handles()
+    _lib.reset_static_handles()
 
 
 @pytest.mark.parametrize("n_cls,n,h,w,seed", tc.VOTE_CASES)

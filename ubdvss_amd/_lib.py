@@ -2,6 +2,9 @@
 import ctypes
 import os
 
+import numpy as np
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UBD_LIB_PATH: another build of the same library (the variant builds of csrc/build.sh under tools/_ab/; the stamped diagnostic build is
 # loaded by tools/_diag.py, which sets LIB_PATH itself); never a fallback
@@ -146,6 +149,88 @@ def load():
 def check(rc, what):
     if rc != 0:
         raise RuntimeError(f"{what} failed (code {rc}): {load().ubd_last_error().decode()}")
+
+
+# the entry points whose last C parameter is `void *stream` (tests/test_lib_call_host.py holds the set to include/ubd.h)
+ON_STREAM = frozenset((
+    "ubd_forward", "ubd_forward_postprocess", "ubd_multiscale_gather", "ubd_multiscale_fuse", "ubd_multiscale_fuse_backward",
+    "ubd_forward_multiscale", "ubd_pack_weights", "ubd_dilated_layer", "ubd_postprocess", "ubd_loss", "ubd_train_step",
+    "ubd_train_step_multiscale", "ubd_adam_step", "ubd_epoch_accumulate", "ubd_build_label_maps", "ubd_build_label_maps_polygons",
+    "ubd_segmap_polygons", "ubd_resize_images", "ubd_warp_images", "ubd_extract_objects", "ubd_decode_patches",
+    "ubd_decode_text_patches", "ubd_decode_width_patches", "ubd_photometric_images", "ubd_noise_alpha_images", "ubd_evaluate_objects",
+    "ubd_evaluate_polygons", "ubd_evaluate_pixels", "ubd_score_objects", "ubd_rank_detections", "ubd_visualize_images",
+    "ubd_allreduce_grads", "ubd_broadcast_params"))
+
+
+def require_gpu(what):
+    """The refusal of every entry point that needs the device; returns the torch module, for the modules that do not import it themselves."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{what} needs an MI355X; there is no CPU fallback")
+    return torch
+
+
+def current_stream(device):
+    """the raw handle of ``device``'s current torch stream, for a caller that needs it beside the launch (a workspace key)"""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def launch(name, device, *args, stream=None):
+    """THE way to an entry point of ON_STREAM: ``name(*args, stream)`` with ``device`` -- the device of the tensors in ``args``
+    -- made current for the call, on that device's current torch stream, the return code checked on this thread
+    (ubd_last_error is thread-local).  ``stream``: the handle of that same stream (``current_stream`` / ``Model._stream``) when the
+    caller needed it before the call, for a workspace or packed-weights key.  Every step of forward, postprocess, train step and
+    Adam comes through here: one stream lookup, one device guard, one check, nothing else."""
+    if name not in ON_STREAM:
+        raise ValueError(f"{name} is not an entry point that takes a stream (_lib.ON_STREAM); checked entries without one go through _lib.call")
+    fn = getattr(load(), name)
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        check(fn(*args, stream), name)
+
+
+def call(name, *args, device=None):
+    """A checked entry point that takes no stream (ubd_create, ubd_comm_*, the *_tables_layout): ``name(*args)``, with
+    ``device`` current for the call when one is given.  The size queries and getters return no status: plain calls on ``load()``."""
+    if name in ON_STREAM:
+        raise ValueError(f"{name} takes a stream: it goes through _lib.launch")
+    fn = getattr(load(), name)
+    if device is None:
+        check(fn(*args), name)
+    else:
+        with torch.cuda.device(device):
+            check(fn(*args), name)
+
+
+_static_handles = {}    # (n_classes, str(device)) -> handle of the static entry points (losses.loss_and_grad, SegmapManager.postprocess)
+
+
+def static_handle(n_classes, device):
+    """The cached ``UbdConfig(1, n_classes, 1, UBD_F32)`` handle of ``device``, created with that device current."""
+    key = (n_classes, str(device))
+    h = _static_handles.get(key)
+    if h is None:
+        cfg = UbdConfig(1, n_classes, 1, UBD_F32)
+        h = ctypes.c_void_p()
+        call("ubd_create", ctypes.byref(cfg), ctypes.byref(h), device=device)
+        _static_handles[key] = h
+    return h
+
+
+def reset_static_handles():
+    """Destroys the cached handles, each once, and empties the cache (they read the UBD_* test switches when they are created)."""
+    lib = load()
+    while _static_handles:
+        lib.ubd_destroy(_static_handles.popitem()[1])
+
+
+def to_device(a, dtype, device, non_blocking=False):
+    """A tensor, or anything numpy takes as an array, as a contiguous tensor of the torch ``dtype`` on ``device``; a host array is
+    converted on the host, so the bytes of the result are what crosses."""
+    if isinstance(a, torch.Tensor):
+        return a.to(device=device, dtype=dtype, non_blocking=non_blocking).contiguous()
+    host = np.ascontiguousarray(np.asarray(a), dtype={torch.int32: np.int32, torch.float32: np.float32}[dtype])
+    return torch.from_numpy(host).to(device, non_blocking=non_blocking)
 
 
 class StreamWorkspaces:

@@ -700,7 +700,6 @@ class _View:
 def _warp_pass(jobs, c, device):
     """One ubd_warp_images call: jobs = [(view, mode, coeffs, (dst_w, dst_h))]; the views are replaced by packed views of one
     new device buffer."""
-    lib = _lib.load()
     starts, pos = [], 0
     for _, _, _, (dw, dh) in jobs:
         starts.append(pos)
@@ -717,10 +716,7 @@ def _warp_pass(jobs, c, device):
         d["dst_w"], d["dst_h"], d["mode"] = dw, dh, mode
         if coeffs is not None:
             d["coeffs"][:len(coeffs)] = coeffs
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_warp_images(ctypes.c_void_p(base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data, c, len(jobs),
-                                       stream), "ubd_warp_images")
+    _lib.launch("ubd_warp_images", device, ctypes.c_void_p(base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data, c, len(jobs))
     for k, (v, _, _, (dw, dh)) in enumerate(jobs):
         v.rebind(out.data_ptr() + starts[k], dw, dh, out)
 
@@ -774,7 +770,6 @@ def warp_views_on_device(views, plans, device):
 def _photometric_pass(jobs, c, device):
     """One ubd_photometric_images call: jobs = [(view, descriptor fields, in_place)].  In-place images (pointwise modes on pixels
     this module owns) keep their views; the others are written to one new device buffer and their views replaced."""
-    lib = _lib.load()
     starts, pos = [], 0
     for v, _, in_place in jobs:
         starts.append(None if in_place else pos)
@@ -793,10 +788,8 @@ def _photometric_pass(jobs, c, device):
         d["src_offset"], d["dst_offset"], d["w"], d["h"] = v.ptr - src_base, dsts[k] - dst_base, v.w, v.h
         d["mode"], d["flags"], d["seed"] = f["mode"], f["flags"], f["seed"]
         d["p"][:len(f["p"])] = f["p"]
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_photometric_images(ctypes.c_void_p(src_base), src_bytes, ctypes.c_void_p(dst_base), dst_bytes,
-                                              descs.ctypes.data, c, len(jobs), stream), "ubd_photometric_images")
+    _lib.launch("ubd_photometric_images", device, ctypes.c_void_p(src_base), src_bytes, ctypes.c_void_p(dst_base), dst_bytes,
+                descs.ctypes.data, c, len(jobs))
     for (v, _, _), st in zip(jobs, starts):
         if st is not None:
             v.rebind(out.data_ptr() + st, v.w, v.h, out)
@@ -816,7 +809,6 @@ def fill_noise_alpha_desc(d, f, table_base=0):
 def _noise_alpha_pass(jobs, c, device):
     """One ubd_noise_alpha_images call: jobs = [(view, descriptor fields, tables)].  The jobs' tables travel as one array in one
     pinned, stream-ordered transfer; every image is written to one new device buffer and its view replaced."""
-    lib = _lib.load()
     starts, pos = [], 0
     for v, _, _ in jobs:
         starts.append(pos)
@@ -839,10 +831,8 @@ def _noise_alpha_pass(jobs, c, device):
     pinned = torch.empty(tables.size, dtype=torch.int16, pin_memory=True)
     pinned.numpy()[:] = tables.view(np.int16)
     dev_tables = pinned.to(device, non_blocking=True)             # stream-ordered; the pinned block is recycled in stream order
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_noise_alpha_images(ctypes.c_void_p(src_base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data,
-                                              dev_tables.data_ptr(), dev_tables.numel(), c, len(jobs), stream), "ubd_noise_alpha_images")
+    _lib.launch("ubd_noise_alpha_images", device, ctypes.c_void_p(src_base), src_bytes, out.data_ptr(), out.numel(), descs.ctypes.data,
+                dev_tables.data_ptr(), dev_tables.numel(), c, len(jobs))
     for (v, _, _), st in zip(jobs, starts):
         v.rebind(out.data_ptr() + st, v.w, v.h, out)
 
@@ -887,8 +877,7 @@ def augment_arrays_on_device(arrays, plans, device=None):
     device tensors: the warp passes, then the photometric stages of ``plan.photometric`` (empty unless the plan was sampled with
     a ``photo_rng``; skipped for ``plan.original``), slot by slot.  An image without any pass is returned as a view of its
     source."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("augmentation on the device needs an MI355X; there is no CPU fallback")
+    _lib.require_gpu("augmentation on the device")
     from .segmap_manager import _stage_host
     device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
     if len(arrays) != len(plans):
@@ -923,8 +912,7 @@ class SegLinksImageAugmentation:
 
     def __init__(self, image, markup, net_config, rng=None, np_rng=None, plan=None, photo_rng=None, photo_extended=False,
                  photo_noise_alpha=False):
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegLinksImageAugmentation needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("SegLinksImageAugmentation")
         if image.mode not in ("L", "RGB"):
             raise ValueError(f"image mode must be 'L' or 'RGB', got {image.mode!r}")
         self.__net_config = net_config

@@ -50,17 +50,13 @@ def make_params(**params):
 
 def _device_arguments(what, patches, counts):
     """the checks and conversions the entry points share -> (contiguous patches, device counts, shape)"""
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{what} needs an MI355X; there is no CPU fallback")
+    _lib.require_gpu(what)
     if not (isinstance(patches, torch.Tensor) and patches.is_cuda and patches.dtype == torch.uint8 and patches.dim() == 5):
         raise ValueError("patches must be a uint8 device tensor (n, cap, patch_h, patch_w, c)")
     device = patches.device
     patches = patches.contiguous()
     n = int(patches.shape[0])
-    if isinstance(counts, torch.Tensor):
-        counts = counts.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
-    else:
-        counts = torch.from_numpy(np.ascontiguousarray(np.asarray(counts), dtype=np.int32)).to(device, non_blocking=True)
+    counts = _lib.to_device(counts, torch.int32, device, non_blocking=True)
     if tuple(counts.shape) != (n,):
         raise ValueError(f"counts must be ({n},), got {tuple(counts.shape)}")
     return patches, counts, tuple(int(v) for v in patches.shape)
@@ -71,16 +67,12 @@ def _launch(entry, patches, counts, params, row, dtype, fill_from=None):
     the current stream -> its (n, cap, row) device results of ``dtype``; the rows start as zeros, with 0xFF from element
     ``fill_from`` on if that is given, which is what an unused slot keeps"""
     patches, counts, (n, cap, ph, pw, c) = _device_arguments(entry[len("ubd_"):] + "_on_device", patches, counts)
-    lib = _lib.load()
     p = make_params(**params)
     device = patches.device
     results = torch.zeros((n, cap, row), dtype=dtype, device=device)
     if fill_from is not None:
         results[:, :, fill_from:] = 0xFF
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(getattr(lib, entry)(patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr(),
-                                       stream), entry)
+    _lib.launch(entry, device, patches.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p), results.data_ptr())
     return results
 
 

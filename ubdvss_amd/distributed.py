@@ -84,13 +84,12 @@ def attach_native_comm(model, fused=True, group=None, global_loss=False):
     process."""
     import ctypes
     from . import _lib
-    lib = _lib.load()
     w, r = world_size(group), rank(group)
     buf = (ctypes.c_char * _lib.UBD_UNIQUE_ID_BYTES)()
     err = None
     if r == 0:
         try:
-            _lib.check(lib.ubd_comm_unique_id(buf), "ubd_comm_unique_id")
+            _lib.call("ubd_comm_unique_id", buf)
         except Exception as e:                          # noqa: BLE001 -- re-raised below, on every rank
             err = e
     if w > 1:
@@ -106,9 +105,8 @@ def attach_native_comm(model, fused=True, group=None, global_loss=False):
             err = RuntimeError("attach_native_comm: rank 0 could not create the RCCL unique id")
     if err is not None:
         raise err
-    with torch.cuda.device(model.device):
-        flags = (_lib.UBD_COMM_FUSED if fused else 0) | (_lib.UBD_COMM_GLOBAL_LOSS if global_loss else 0)
-        _lib.check(lib.ubd_comm_init(model._h, buf, r, w, flags), "ubd_comm_init")
+    flags = (_lib.UBD_COMM_FUSED if fused else 0) | (_lib.UBD_COMM_GLOBAL_LOSS if global_loss else 0)
+    _lib.call("ubd_comm_init", model._h, buf, r, w, flags, device=model.device)
     model._native_comm = "fused" if fused else "explicit"
     model._global_loss = bool(global_loss)
     return w
@@ -120,9 +118,7 @@ def detach_native_comm(model):
     create its communicator EVERY rank must call this before falling back to torch.distributed's all-reduce -- otherwise the
     ranks that succeeded would block in RCCL calls the others never join (or sum the gradients twice)."""
     from . import _lib
-    lib = _lib.load()
-    with torch.cuda.device(model.device):
-        _lib.check(lib.ubd_comm_destroy(model._h), "ubd_comm_destroy")
+    _lib.call("ubd_comm_destroy", model._h, device=model.device)
     model._native_comm = None
     model._global_loss = False
 

@@ -20,6 +20,7 @@ polygon of a call has more (hulls read from segmentation maps, ``ubdvss_amd.mark
 ``ubd_evaluate_polygons``, which gives the same bits on common ground.  Not here: non-convex outlines as such.
 """
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -164,11 +165,7 @@ def check_ground_truth_polygon(coords, image_idx=0, object_idx=0, max_vertices=_
     return p
 
 
-def _require_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("ubdvss_amd.evaluation needs an MI355X: there is no CPU fallback")
-    return torch
+_require_gpu = functools.partial(_lib.require_gpu, "ubdvss_amd.evaluation")      # a name of its own: a host test replaces it
 
 
 def pack_ground_truth(gt_polygons, gt_classes=None, image_offset=0, n_classes=None):
@@ -240,23 +237,21 @@ def evaluate_objects(quads, classes, counts, gt_polygons, gt_classes, thresholds
                          f"(cap <= {_lib.UBD_EVAL_MAX_FOUND}, thresholds <= {_lib.UBD_EVAL_MAX_THRESHOLDS})")
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     rec = torch.empty((n, T, _REC_BYTES), dtype=torch.uint8, device=dev) if per_image else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
     head = (quads.data_ptr(), classes.data_ptr() if (classes is not None and C > 0) else None, counts.data_ptr(), n, cap,
             scales.data_ptr() if scales is not None else None, xy_d.data_ptr(), int(len(xy)), first_d.data_ptr(),
             cls_d.data_ptr() if cls_d is not None else None, image_first.ctypes.data, max_gt, thr.ctypes.data, T, C)
-    tail = (rec.data_ptr() if rec is not None else None, accumulator.data_ptr(), ws.data_ptr(), need, stream)
+    tail = (rec.data_ptr() if rec is not None else None, accumulator.data_ptr(), ws.data_ptr(), need)
     if polygons:
-        _lib.check(lib.ubd_evaluate_polygons(*head, most_verts, *tail), "ubd_evaluate_polygons")
+        _lib.launch("ubd_evaluate_polygons", dev, *head, most_verts, *tail)
     else:
-        _lib.check(lib.ubd_evaluate_objects(*head, *tail), "ubd_evaluate_objects")
+        _lib.launch("ubd_evaluate_objects", dev, *head, *tail)
     # the inputs and the workspace were allocated on this stream: the caching allocator reuses them in stream order
     if return_tables:
         off, stride = ctypes.c_int64(), ctypes.c_int64()
         if polygons:
-            _lib.check(lib.ubd_evaluate_polygons_tables_layout(n, max_gt, cap, T, C, most_verts, ctypes.byref(off), ctypes.byref(stride)),
-                       "ubd_evaluate_polygons_tables_layout")
+            _lib.call("ubd_evaluate_polygons_tables_layout", n, max_gt, cap, T, C, most_verts, ctypes.byref(off), ctypes.byref(stride))
         else:
-            _lib.check(lib.ubd_evaluate_tables_layout(n, max_gt, cap, T, C, ctypes.byref(off), ctypes.byref(stride)), "ubd_evaluate_tables_layout")
+            _lib.call("ubd_evaluate_tables_layout", n, max_gt, cap, T, C, ctypes.byref(off), ctypes.byref(stride))
         return rec, (ws, off.value, stride.value, max_gt)
     return rec
 
@@ -352,10 +347,9 @@ def evaluate_pixels(class_logits, labels, accumulator, want_mask=False, n_classe
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     rec = torch.empty((n, _PIX_REC_BYTES), dtype=torch.uint8, device=dev) if per_image else None
     mask = torch.empty((n, h, w), dtype=torch.int8, device=dev) if want_mask else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.ubd_evaluate_pixels(class_logits.data_ptr(), int(stride), C, labels.data_ptr(), n, h, w,
-                                       mask.data_ptr() if mask is not None else None, rec.data_ptr() if rec is not None else None,
-                                       accumulator.data_ptr(), ws.data_ptr(), need, stream), "ubd_evaluate_pixels")
+    _lib.launch("ubd_evaluate_pixels", dev, class_logits.data_ptr(), int(stride), C, labels.data_ptr(), n, h, w,
+                mask.data_ptr() if mask is not None else None, rec.data_ptr() if rec is not None else None,
+                accumulator.data_ptr(), ws.data_ptr(), need)
     # the inputs and the workspace were allocated on this stream: the caching allocator reuses them in stream order
     return rec, mask
 
@@ -416,7 +410,6 @@ def rank_detections(scores, counts, gt_polygons, tables, thresholds, rank_buffer
     gt_polygons: the per-image lists the evaluate call was given (only their lengths are used), or the lengths themselves.
     The rule is not the reference's 1-1 / 1-many / many-1 analysis.  Nothing is copied to the host."""
     torch = _require_gpu()
-    lib = _lib.load()
     ws, off, stride, max_gt = tables
     n, cap = int(scores.shape[0]), int(scores.shape[1])
     if scores.dtype != torch.float32 or counts.dtype != torch.int32 or int(counts.numel()) != n:
@@ -433,9 +426,8 @@ def rank_detections(scores, counts, gt_polygons, tables, thresholds, rank_buffer
     gt_d = torch.from_numpy(gt_counts).to(dev)
     scores, counts = scores.contiguous(), counts.contiguous()
     iou_ptr = ws.data_ptr() + int(off) + (max_gt + cap + max_gt * cap) * 8          # the IoU table follows the areas and the intersections
-    _lib.check(lib.ubd_rank_detections(scores.data_ptr(), counts.data_ptr(), n, cap, iou_ptr, int(stride), gt_d.data_ptr(),
-                                       thr.ctypes.data, len(thr), rank_buffer.data_ptr(), capacity,
-                                       torch.cuda.current_stream(dev).cuda_stream), "ubd_rank_detections")
+    _lib.launch("ubd_rank_detections", dev, scores.data_ptr(), counts.data_ptr(), n, cap, iou_ptr, int(stride), gt_d.data_ptr(),
+                thr.ctypes.data, len(thr), rank_buffer.data_ptr(), capacity)
     # gt_d was allocated on this stream: the caching allocator reuses it in stream order
 
 

@@ -5,9 +5,6 @@ reference; it evaluates the fused HIP loss kernel (weighted sigmoid-BCE with bat
 hard-negative top-k, plus masked softmax-CE in classification mode) on the MI355X.
 ``loss_and_grad`` additionally returns d loss / d y_pred (what TF autodiff would produce).
 """
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _lib
@@ -19,49 +16,29 @@ L_HARD_NEGATIVE_WEIGHT = 5.
 L_DETECTION_WEIGHT = 1.
 L_CLASSIFICATION_WEIGHT = 1.
 
-_handles = {}
+_handles = _lib._static_handles        # the cache under its earlier name here: callers written against that name keep working
 _workspaces = _lib.StreamWorkspaces()   # (device, stream) -> uint8 scratch reused between calls on that stream (grown on demand, LRU-bounded)
-
-
-def _handle(n_classes, device):
-    key = (n_classes, str(device))
-    if key not in _handles:
-        lib = _lib.load()
-        cfg = _lib.UbdConfig(1, n_classes, 1, _lib.UBD_F32)
-        h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.ubd_create(ctypes.byref(cfg), ctypes.byref(h)), "ubd_create")
-        _handles[key] = h
-    return _handles[key]
-
-
-def _as_device(a, dtype, device):
-    if isinstance(a, torch.Tensor):
-        return a.to(device=device, dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(device=device, dtype=dtype)
 
 
 def loss_and_grad(y_true, y_pred, want_grad=True):
     """y_true (N,h,w,1) or (N,h,w) labels 0..n_cls; y_pred (N,h,w,1+n_cls) logits.
     Returns (loss4 device tensor [total, detection, classification, k], dlogits or None)."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("ubdvss_amd.losses needs an MI355X; there is no CPU fallback")
+    _lib.require_gpu("ubdvss_amd.losses")
     lib = _lib.load()
     device = y_pred.device if isinstance(y_pred, torch.Tensor) and y_pred.is_cuda else torch.device(
         f"cuda:{torch.cuda.current_device()}")
-    yp = _as_device(y_pred, torch.float32, device)
+    yp = _lib.to_device(y_pred, torch.float32, device)
     n, h, w, k = yp.shape
-    yt = _as_device(y_true, torch.int32, device).reshape(n, h, w)
-    hd = _handle(k - 1, device)
+    yt = _lib.to_device(y_true, torch.int32, device).reshape(n, h, w)
+    hd = _lib.static_handle(k - 1, device)
     loss = torch.zeros(16, dtype=torch.float32, device=device)
     grad = torch.empty_like(yp) if want_grad else None
     nbytes = int(lib.ubd_loss_workspace_bytes(hd, n, h, w))
     # one scratch per (device, stream): calls on one stream are ordered, two streams never share header / histograms
-    raw_stream = torch.cuda.current_stream(device).cuda_stream
-    ws = _workspaces.get(device, raw_stream, nbytes)
-    stream = ctypes.c_void_p(raw_stream)
-    _lib.check(lib.ubd_loss(hd, yp.data_ptr(), yt.data_ptr(), n, h, w, loss.data_ptr(),
-                            grad.data_ptr() if grad is not None else None, ws.data_ptr(), ws.numel(), stream), "ubd_loss")
+    stream = _lib.current_stream(device)
+    ws = _workspaces.get(device, stream, nbytes)
+    _lib.launch("ubd_loss", device, hd, yp.data_ptr(), yt.data_ptr(), n, h, w, loss.data_ptr(),
+                grad.data_ptr() if grad is not None else None, ws.data_ptr(), ws.numel(), stream=stream)
     return loss, grad
 
 

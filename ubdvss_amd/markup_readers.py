@@ -10,7 +10,6 @@ Deviation: the reference drops hulls of one point and keeps hulls of two (a stra
 shapely when they are evaluated.  Here hulls with fewer than 3 vertices are dropped, and counted in a log line.
 """
 import collections
-import ctypes
 import logging
 import os
 
@@ -28,9 +27,7 @@ _MAX_VERTS = _lib.UBD_POLY_MAX_VERTS
 def _segmap_polygons_device(maps, device=None):
     """One ubd_segmap_polygons call: uint8 (n, h, w) array or tensor -> host int32 arrays verts (n, cap, 64, 2), nverts (n, cap),
     counts (n)."""
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("ubdvss_amd.markup_readers needs an MI355X: there is no CPU fallback")
+    torch = _lib.require_gpu("ubdvss_amd.markup_readers")
     lib = _lib.load()
     device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
     if not torch.is_tensor(maps):
@@ -47,10 +44,8 @@ def _segmap_polygons_device(maps, device=None):
     verts = torch.zeros((n, cap, _MAX_VERTS, 2), dtype=torch.int32, device=device)
     nverts = torch.zeros((n, cap), dtype=torch.int32, device=device)
     counts = torch.zeros((n,), dtype=torch.int32, device=device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_segmap_polygons(maps.data_ptr(), n, h, w, verts.data_ptr(), nverts.data_ptr(), counts.data_ptr(), cap,
-                                           ws.data_ptr(), need, stream), "ubd_segmap_polygons")
+    _lib.launch("ubd_segmap_polygons", device, maps.data_ptr(), n, h, w, verts.data_ptr(), nverts.data_ptr(), counts.data_ptr(), cap,
+                ws.data_ptr(), need)
     return verts.cpu().numpy(), nverts.cpu().numpy(), counts.cpu().numpy()
 
 

@@ -262,8 +262,7 @@ class ModelRunner:
         data_generators.py:133-140); per group (and per ``batch_size`` images of it) they are resized on the device
         (ubd_resize_images, Pillow's BICUBIC bit for bit) and fed as uint8 to ``predict_on_device`` (the NetConfig
         preprocessing fused into the first layer); the boxes are scaled back by the MetaInfo scales (``rescale``)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelRunner.predict_images needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("ModelRunner.predict_images")
         return self._predict_images(model, images, batch_size, None)[0]
 
     def predict_patches(self, model, images, patch_size=(64, 256), expand=1.0, batch_size=None):
@@ -274,8 +273,7 @@ class ModelRunner:
         resize and then the extraction, with the group's ``ResizeMeta`` scales.  Returns (found, patches): ``found`` is exactly
         ``predict_images``' result, ``patches[k]`` a uint8 host array (len(found[k]), patch_h, patch_w, c) in the order of
         ``found[k]`` (c = 3 unless every image of the group is grey).  One device-to-host copy of the patches per group."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelRunner.predict_patches needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("ModelRunner.predict_patches")
         return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)))
 
     def predict_decoded(self, model, images, patch_size=(64, 256), expand=1.25, batch_size=None, **params):
@@ -290,8 +288,7 @@ class ModelRunner:
         Bits 3 and 4 (``barcode_decoder.ITF``, ``CODE39``; 31 reads every family) add ``decode_width_patches_on_device`` in the
         same way: every requested kernel is launched before the first result is read, and ``decoded[k][j]`` is the retail record,
         else the ``DecodedText``, else the ``DecodedWidth``, else None.  Bits beyond 0..4 are a ValueError."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelRunner.predict_decoded needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("ModelRunner.predict_decoded")
         from .barcode_decoder import make_params
         symbologies = make_params(**params).symbologies     # an unknown keyword fails before any work
         if symbologies & ~31:

@@ -188,8 +188,7 @@ class Model:
     (numpy NHWC in, numpy logits out); ``predict_on_device`` keeps everything in HBM."""
 
     def __init__(self, net_config, dtype="float32", device=None, seed=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("ubdvss_amd.Model needs an MI355X (torch.cuda unavailable); there is no CPU fallback")
+        _lib.require_gpu("ubdvss_amd.Model")
         self._lib = _lib.load()
         self.net_config = net_config
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -199,8 +198,7 @@ class Model:
         self.dtype = dtype
         cfg = _lib.UbdConfig(self.c_in, self.n_classes, int(net_config.is_fml_compatible()), _DTYPES[dtype])
         handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.ubd_create(ctypes.byref(cfg), ctypes.byref(handle)), "ubd_create")
+        _lib.call("ubd_create", ctypes.byref(cfg), ctypes.byref(handle), device=self.device)
         self._h = handle
         n = self._lib.ubd_param_count(self._h)
         self.params = torch.zeros(n, dtype=torch.float32, device=self.device)
@@ -366,25 +364,23 @@ class Model:
         if key == self._packed_key or (_prepacked and self._packed_key is not None and key[:4] == self._packed_key[:4]):
             in_dtype |= _lib.UBD_IN_PREPACKED       # _prepacked: the caller (GraphedForward) has synchronised behind the call that packed
         self._packed_key = None
-        with torch.cuda.device(self.device):
-            if postprocess is None:
-                _lib.check(self._lib.ubd_forward(self._h, self.params.data_ptr(), images.data_ptr(), in_dtype, pre,
-                                                 n, hh, ww, out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                           "ubd_forward")
-            else:
-                pl = postprocess["logits"]
-                if not pl.is_contiguous() or pl.dtype != torch.float32 or pl.shape[3] != self.k_out:
-                    raise ValueError("postprocess job: logits must be a contiguous fp32 (N,h,w,K) tensor of this model")
-                pn, pmh, pmw, _ = pl.shape
-                bmap, quads, classes, counts = postprocess["outputs"]
-                cap = int(postprocess.get("cap", quads.shape[1]))
-                pws = self._workspace("_pp_ws", self._lib.ubd_postprocess_workspace_bytes(self._h, pn, pmh, pmw, cap))
-                _lib.check(self._lib.ubd_forward_postprocess(
-                    self._h, self.params.data_ptr(), images.data_ptr(), in_dtype, pre, n, hh, ww, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                    pl.data_ptr(), pn, pmh, pmw, float(postprocess["logit_threshold"]), int(postprocess["scale"]),
-                    float(postprocess["min_area"]), bmap.data_ptr() if bmap is not None else None, quads.data_ptr(),
-                    classes.data_ptr() if classes is not None else None, counts.data_ptr(), cap, pws.data_ptr(), pws.numel(), stream),
-                    "ubd_forward_postprocess")
+        if postprocess is None:
+            _lib.launch("ubd_forward", self.device, self._h, self.params.data_ptr(), images.data_ptr(), in_dtype, pre,
+                        n, hh, ww, out.data_ptr(), ws.data_ptr(), ws.numel(), stream=stream)
+        else:
+            pl = postprocess["logits"]
+            if not pl.is_contiguous() or pl.dtype != torch.float32 or pl.shape[3] != self.k_out:
+                raise ValueError("postprocess job: logits must be a contiguous fp32 (N,h,w,K) tensor of this model")
+            pn, pmh, pmw, _ = pl.shape
+            bmap, quads, classes, counts = postprocess["outputs"]
+            cap = int(postprocess.get("cap", quads.shape[1]))
+            pws = self._workspace("_pp_ws", self._lib.ubd_postprocess_workspace_bytes(self._h, pn, pmh, pmw, cap))
+            _lib.launch("ubd_forward_postprocess", self.device,
+                        self._h, self.params.data_ptr(), images.data_ptr(), in_dtype, pre, n, hh, ww, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                        pl.data_ptr(), pn, pmh, pmw, float(postprocess["logit_threshold"]), int(postprocess["scale"]),
+                        float(postprocess["min_area"]), bmap.data_ptr() if bmap is not None else None, quads.data_ptr(),
+                        classes.data_ptr() if classes is not None else None, counts.data_ptr(), cap, pws.data_ptr(), pws.numel(),
+                        stream=stream)
         self._packed_key = key
         return out
 
@@ -426,18 +422,15 @@ class Model:
         n, mh, mw, k = logits.shape
         if k != self.k_out:
             raise ValueError(f"logits have {k} channels, model has {self.k_out}")
-        dev = self.device
         if outputs is None:
             outputs = self.alloc_postprocess_outputs(n, mh, mw, cap, want_map)
         bmap, quads, classes, counts = outputs
         nbytes = self._lib.ubd_postprocess_workspace_bytes(self._h, n, mh, mw, cap)
         ws = self._workspace("_pp_ws", nbytes)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.ubd_postprocess(
-                self._h, logits.data_ptr(), n, mh, mw, float(logit_threshold), int(scale), float(min_area),
-                bmap.data_ptr() if bmap is not None else None, quads.data_ptr(),
-                classes.data_ptr() if classes is not None else None, counts.data_ptr(), cap,
-                ws.data_ptr(), ws.numel(), self._stream()), "ubd_postprocess")
+        _lib.launch("ubd_postprocess", self.device,
+                    self._h, logits.data_ptr(), n, mh, mw, float(logit_threshold), int(scale), float(min_area),
+                    bmap.data_ptr() if bmap is not None else None, quads.data_ptr(),
+                    classes.data_ptr() if classes is not None else None, counts.data_ptr(), cap, ws.data_ptr(), ws.numel())
         return bmap, quads, classes, counts
 
     def score_objects_on_device(self, logits, quads, counts, scale, out=None):
@@ -457,9 +450,8 @@ class Model:
         quads, counts = quads.contiguous(), counts.contiguous()
         if out is None:
             out = torch.empty((n, cap), dtype=torch.float32, device=logits.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.ubd_score_objects(logits.data_ptr(), k, quads.data_ptr(), counts.data_ptr(), n, mh, mw, cap, int(scale),
-                                                   out.data_ptr(), self._stream()), "ubd_score_objects")
+        _lib.launch("ubd_score_objects", self.device, logits.data_ptr(), k, quads.data_ptr(), counts.data_ptr(), n, mh, mw, cap, int(scale),
+                    out.data_ptr())
         return out
 
 
@@ -593,9 +585,8 @@ class MultiscaleModel:
         if key == self._ms_packed_key or (_prepacked and self._ms_packed_key is not None and key[:4] == self._ms_packed_key[:4]):
             in_dtype |= _lib.UBD_IN_PREPACKED
         self._ms_packed_key = None
-        with torch.cuda.device(b.device):
-            _lib.check(lib.ubd_forward_multiscale(b._h, b.params.data_ptr(), images.data_ptr(), in_dtype, pre, n, hh, ww, power,
-                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ubd_forward_multiscale")
+        _lib.launch("ubd_forward_multiscale", b.device, b._h, b.params.data_ptr(), images.data_ptr(), in_dtype, pre, n, hh, ww, power,
+                    out.data_ptr(), ws.data_ptr(), ws.numel(), stream=stream)
         self._ms_packed_key = key
         if postprocess is not None:
             b.postprocess_on_device(postprocess["logits"], postprocess["logit_threshold"], postprocess["scale"], postprocess["min_area"],

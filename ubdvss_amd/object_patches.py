@@ -15,16 +15,9 @@ from . import _lib
 from .segmap_manager import _image_source, _stage_sources
 
 
-def _to_device(a, dtype, device):
-    if isinstance(a, torch.Tensor):
-        return a.to(device=device, dtype=dtype, non_blocking=True).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=dtype)).to(device, non_blocking=True)
-
-
 def _extract_staged(stage, quads, counts, scales, patch_size, expand, return_quads, device, zero=True):
     """``ubd_extract_objects`` over the staged sources of ``segmap_manager._stage_sources``; quads (n, cap, 8) and counts (n)
     are int32 tensors on ``device``.  zero: slots that hold no object read as 0 (else they are left as allocated)."""
-    lib = _lib.load()
     base, offsets, hw, c, _ = stage
     n = len(offsets)
     if quads.dim() != 3 or quads.shape[0] != n or quads.shape[2] != 8 or tuple(counts.shape) != (n,):
@@ -41,12 +34,9 @@ def _extract_staged(stage, quads, counts, scales, patch_size, expand, return_qua
         scales_d = torch.from_numpy(np.array([[float(s[0]), float(s[1])] for s in scales], np.float64)).to(device, non_blocking=True)
     patches = (torch.zeros if zero else torch.empty)((n, cap, ph, pw, c), dtype=torch.uint8, device=device)
     pq = (torch.zeros if zero else torch.empty)((n, cap, 8), dtype=torch.int32, device=device) if return_quads else None
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_extract_objects(ctypes.c_void_p(base), src_bytes, offs_d.data_ptr(), hw_d.data_ptr(), c, quads.data_ptr(),
-                                           counts.data_ptr(), n, cap, None if scales_d is None else scales_d.data_ptr(), float(expand),
-                                           patches.data_ptr(), ph, pw, None if pq is None else pq.data_ptr(), stream),
-                   "ubd_extract_objects")
+    _lib.launch("ubd_extract_objects", device, ctypes.c_void_p(base), src_bytes, offs_d.data_ptr(), hw_d.data_ptr(), c, quads.data_ptr(),
+                counts.data_ptr(), n, cap, None if scales_d is None else scales_d.data_ptr(), float(expand),
+                patches.data_ptr(), ph, pw, None if pq is None else pq.data_ptr())
     return (patches, pq) if return_quads else patches
 
 
@@ -62,8 +52,7 @@ def extract_objects_on_device(sources, quads, counts, scales=None, patch_size=(6
     Returns the uint8 device tensor (n, cap, patch_h, patch_w, c), zero in the slots that hold no object; with ``return_quads``
     also the int32 (n, cap, 8) corners NW, NE, SE, SW of every patch in source coordinates (rescaled, before expansion).
     Nothing is read back: the call enqueues on the current stream and returns."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("extract_objects_on_device needs an MI355X; there is no CPU fallback")
+    _lib.require_gpu("extract_objects_on_device")
     if isinstance(quads, torch.Tensor) and quads.is_cuda:
         device = quads.device
     else:
@@ -71,6 +60,6 @@ def extract_objects_on_device(sources, quads, counts, scales=None, patch_size=(6
     srcs = [_image_source(im, device) for im in sources]
     if not srcs:
         raise ValueError("no images")
-    quads = _to_device(quads, torch.int32 if isinstance(quads, torch.Tensor) else np.int32, device)
-    counts = _to_device(counts, torch.int32 if isinstance(counts, torch.Tensor) else np.int32, device)
+    quads = _lib.to_device(quads, torch.int32, device, non_blocking=True)
+    counts = _lib.to_device(counts, torch.int32, device, non_blocking=True)
     return _extract_staged(_stage_sources(srcs, device), quads, counts, scales, patch_size, expand, return_quads, device)

@@ -15,34 +15,8 @@ from PIL import Image, ImageDraw
 from . import _lib
 from .data_markup import ObjectMarkup, ClassifiedObjectMarkup
 
-_handles = {}
+_reset_handles = _lib.reset_static_handles      # the reset under its earlier name here: callers written against that name keep working
 _workspaces = _lib.StreamWorkspaces()   # (device, stream) -> uint8 tensor: the static entry points reuse their scratch between calls (LRU-bounded)
-
-
-def _workspace(device, nbytes):
-    """Device scratch of at least nbytes, kept per (device, current stream): calls on one stream are ordered, two streams
-    never share a scratch (grown when a bigger request comes; never shrunk)."""
-    return _workspaces.get(device, torch.cuda.current_stream(device).cuda_stream, nbytes)
-
-
-def _reset_handles():
-    """Destroys the cached C-ABI handles (they read the UBD_* test switches when they are created)."""
-    lib = _lib.load()
-    for h in _handles.values():
-        lib.ubd_destroy(h)
-    _handles.clear()
-
-
-def _handle(n_classes, device):
-    key = (n_classes, str(device))
-    if key not in _handles:
-        lib = _lib.load()
-        cfg = _lib.UbdConfig(1, n_classes, 1, _lib.UBD_F32)
-        h = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.ubd_create(ctypes.byref(cfg), ctypes.byref(h)), "ubd_create")
-        _handles[key] = h
-    return _handles[key]
 
 
 # per image: the scales of the reference's MetaInfo (data_generators.py:42-55, :189), original / rescaled, read by ModelRunner.rescale
@@ -119,13 +93,10 @@ def _stage_sources(srcs, device):
 
 def _resize_staged(stage, new_h, new_w, dst_c, device):
     """ubd_resize_images of every staged source into one (N, new_h, new_w, dst_c) tensor."""
-    lib = _lib.load()
     base, offsets, hw, src_c, _ = stage
     out = torch.empty((len(offsets), new_h, new_w, dst_c), dtype=torch.uint8, device=device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(lib.ubd_resize_images(ctypes.c_void_p(base), offsets.ctypes.data, hw.ctypes.data, src_c, len(offsets),
-                                         out.data_ptr(), new_h, new_w, dst_c, stream), "ubd_resize_images")
+    _lib.launch("ubd_resize_images", device, ctypes.c_void_p(base), offsets.ctypes.data, hw.ctypes.data, src_c, len(offsets),
+                out.data_ptr(), new_h, new_w, dst_c)
     return out
 
 
@@ -139,8 +110,7 @@ class SegmapManager:
     def postprocess(seg_map, seg_map_class_logits=None, scale=1, min_area_threshold=5, max_objects=1024):
         """seg_map: (h,w,1) or (h,w) array of {0,1}; seg_map_class_logits: (h,w,n_cls) or None.
         Returns list[ObjectMarkup] / list[ClassifiedObjectMarkup] like the reference."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegmapManager.postprocess needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("SegmapManager.postprocess")
         lib = _lib.load()
         device = torch.device(f"cuda:{torch.cuda.current_device()}")
         m = np.asarray(seg_map)
@@ -153,16 +123,16 @@ class SegmapManager:
         if n_cls:
             lg[0, :, :, 1:] = np.asarray(seg_map_class_logits, np.float32)
         lgt = torch.from_numpy(lg).to(device)
-        hd = _handle(n_cls, device)
+        hd = _lib.static_handle(n_cls, device)
         cap = max_objects
         quads = torch.empty((1, cap, 8), dtype=torch.int32, device=device)      # the library writes the count and the list's first entries
         classes = torch.empty((1, cap), dtype=torch.int32, device=device)
         counts = torch.empty((1,), dtype=torch.int32, device=device)
-        ws = _workspace(device, lib.ubd_postprocess_workspace_bytes(hd, 1, h, w, cap))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(lib.ubd_postprocess(hd, lgt.data_ptr(), 1, h, w, 0.5, int(scale), float(min_area_threshold),
-                                       None, quads.data_ptr(), classes.data_ptr(), counts.data_ptr(), cap,
-                                       ws.data_ptr(), ws.numel(), stream), "ubd_postprocess")
+        # one scratch per (device, stream): calls on one stream are ordered, two streams never share one (grown on demand, never shrunk)
+        stream = _lib.current_stream(device)
+        ws = _workspaces.get(device, stream, lib.ubd_postprocess_workspace_bytes(hd, 1, h, w, cap))
+        _lib.launch("ubd_postprocess", device, hd, lgt.data_ptr(), 1, h, w, 0.5, int(scale), float(min_area_threshold),
+                    None, quads.data_ptr(), classes.data_ptr(), counts.data_ptr(), cap, ws.data_ptr(), ws.numel(), stream=stream)
         n = int(counts.cpu()[0])
         if n > cap:
             raise RuntimeError(f"more than max_objects={cap} objects found ({n})")
@@ -219,9 +189,7 @@ class SegmapManager:
         Returns an int32 device tensor (N, height/scale, width/scale) -- the y_true layout of the loss / train step.
         Degenerate quads whose OPPOSITE corners coincide on the map (a point or a folded segment -- a labelling error) are drawn
         like every other quad and logged; ``strict_markup=True`` refuses them instead (see ``_check_folded_quads``)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegmapManager.build_segmentation_maps_on_device needs an MI355X; there is no CPU fallback")
-        lib = _lib.load()
+        _lib.require_gpu("SegmapManager.build_segmentation_maps_on_device")
         device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         width, height = image_size
         if width % scale or height % scale:
@@ -257,18 +225,14 @@ class SegmapManager:
         quads = np.ascontiguousarray(verts[:, :, :8])
         SegmapManager._check_folded_quads(quads, counts, scale, strict_markup, nverts == 4)
         labels = torch.empty((n, height // scale, width // scale), dtype=torch.int32, device=device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         if not polygons:
             qd, vd, cd = (torch.from_numpy(a).to(device) for a in (quads, values, counts))
-            with torch.cuda.device(device):
-                _lib.check(lib.ubd_build_label_maps(qd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, height // scale, width // scale,
-                                                    int(scale), labels.data_ptr(), stream), "ubd_build_label_maps")
+            _lib.launch("ubd_build_label_maps", device, qd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, height // scale, width // scale,
+                        int(scale), labels.data_ptr())
             return labels
         pd, nd, vd, cd = (torch.from_numpy(a).to(device) for a in (verts, nverts, values, counts))
-        with torch.cuda.device(device):
-            _lib.check(lib.ubd_build_label_maps_polygons(pd.data_ptr(), nd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, max_verts,
-                                                         height // scale, width // scale, int(scale), labels.data_ptr(), stream),
-                       "ubd_build_label_maps_polygons")
+        _lib.launch("ubd_build_label_maps_polygons", device, pd.data_ptr(), nd.data_ptr(), vd.data_ptr(), cd.data_ptr(), n, cap, max_verts,
+                    height // scale, width // scale, int(scale), labels.data_ptr())
         return labels
 
     @staticmethod
@@ -355,8 +319,7 @@ class SegmapManager:
     def _rescale_images_staged(images, net_config, device, max_side=None):
         """_rescale_images that also hands back the staged sources (``_stage_sources``) it resized: the raw frames as they lie
         in device memory, for a second reader (ModelRunner.predict_patches cuts the found objects out of them)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegmapManager.rescale_images_on_device needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("SegmapManager.rescale_images_on_device")
         device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         srcs = [_image_source(im, device) for im in images]
         if not srcs:
@@ -376,8 +339,7 @@ class SegmapManager:
         returns (uint8 images (N, h, w, c_in) of ``rescale_images_on_device``, int32 label maps (N, h/scale, w/scale) of
         ``build_segmentation_maps_on_device``, the markups scaled by (new_w / w, new_h / h) exactly as
         ``_rescale_image_and_markup`` scales them).  Images as in ``rescale_images_on_device``."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegmapManager.prepare_batch_on_device needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("SegmapManager.prepare_batch_on_device")
         if len(images) != len(markups):
             raise ValueError("one markup per image is required")
         x, sizes = SegmapManager._rescale_images(images, net_config, device)
@@ -406,8 +368,7 @@ class SegmapManager:
         draws MedianBlur, AddToHueAndSaturation and ElasticTransformation (off: they stay recorded no-ops); ``photo_noise_alpha``: likewise for
         SimplexNoiseAlpha and FrequencyNoiseAlpha -- with both flags the whole stage of the reference runs.  What of that stage is built, what is not, and that parity with imgaug /
         OpenCV is unpinned: ubdvss_amd/augmentation.py.  Images as in ``rescale_images_on_device``."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("SegmapManager.prepare_batches_on_device needs an MI355X; there is no CPU fallback")
+        _lib.require_gpu("SegmapManager.prepare_batches_on_device")
         from . import augmentation
         if len(images) != len(markups):
             raise ValueError("one markup per image is required")

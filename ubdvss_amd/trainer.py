@@ -15,7 +15,6 @@ A ``MultiscaleModel`` is trained through the multi-scale graph (train.py fits wh
 steps are ``ubd_train_step_multiscale``, its validation steps the multi-scale forward, so ``loss`` and ``val_loss`` belong to one model.
 With a native communicator the multi-scale step needs the explicit mode (``attach_native_comm(model, fused=False)``).
 """
-import ctypes
 import logging
 
 import numpy as np
@@ -66,9 +65,7 @@ class Trainer:
 
     def broadcast_weights(self, src=0):
         if getattr(self.model, "_native_comm", None):           # the handle's own RCCL communicator (ubd_broadcast_params)
-            with torch.cuda.device(self.model.device):
-                _lib.check(self._lib.ubd_broadcast_params(self.model._h, self.model.params.data_ptr(), self.model.params.numel(),
-                                                          src, self.model._stream()), "ubd_broadcast_params")
+            _lib.launch("ubd_broadcast_params", self.model.device, self.model._h, self.model.params.data_ptr(), self.model.params.numel(), src)
         else:
             if self._pg is not False:
                 distributed.broadcast_parameters(self.model.params, src=src, group=self._pg)
@@ -102,26 +99,21 @@ class Trainer:
             nbytes = self._lib.ubd_train_multiscale_workspace_bytes(mdl._h, in_dtype, n, hh, ww, power)
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=mdl.device)
-        with torch.cuda.device(mdl.device):
-            if power is None:
-                _lib.check(self._lib.ubd_train_step(mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
-                                                    targets.data_ptr(), n, hh, ww, self.grads.data_ptr(),
-                                                    self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                    mdl._stream()), "ubd_train_step")
-            else:
-                _lib.check(self._lib.ubd_train_step_multiscale(mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
-                                                               targets.data_ptr(), n, hh, ww, power, self.grads.data_ptr(),
-                                                               self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                               mdl._stream()), "ubd_train_step_multiscale")
+        if power is None:
+            _lib.launch("ubd_train_step", mdl.device, mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
+                        targets.data_ptr(), n, hh, ww, self.grads.data_ptr(),
+                        self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel())
+        else:
+            _lib.launch("ubd_train_step_multiscale", mdl.device, mdl._h, mdl.params.data_ptr(), images.data_ptr(), in_dtype, pre,
+                        targets.data_ptr(), n, hh, ww, power, self.grads.data_ptr(),
+                        self.loss.data_ptr(), self._ws.data_ptr(), self._ws.numel())
 
     def apply_gradients(self):
         native = getattr(self.model, "_native_comm", None)
         if native:                                              # C-ABI collective: fused into ubd_train_step, or explicit here
             world = self._lib.ubd_comm_world(self.model._h)
             if native == "explicit":
-                with torch.cuda.device(self.model.device):
-                    _lib.check(self._lib.ubd_allreduce_grads(self.model._h, self.grads.data_ptr(), self.grads.numel(),
-                                                             self.model._stream()), "ubd_allreduce_grads")
+                _lib.launch("ubd_allreduce_grads", self.model.device, self.model._h, self.grads.data_ptr(), self.grads.numel())
             # per-replica losses are averaged; the batch-global loss (UBD_COMM_GLOBAL_LOSS) is ONE objective whose parameter
             # gradient is the sum of the ranks' contributions
             grad_scale = 1.0 if getattr(self.model, "_global_loss", False) else 1.0 / world
@@ -131,10 +123,8 @@ class Trainer:
             grad_scale = distributed.allreduce_gradients(self.grads, group=self._pg)
         self.iterations += 1
         o = self.opt
-        with torch.cuda.device(self.model.device):
-            _lib.check(self._lib.ubd_adam_step(self.model.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                               self.v.data_ptr(), self.grads.numel(), self.iterations, o.lr, o.beta_1,
-                                               o.beta_2, o.epsilon, grad_scale, self.model._stream()), "ubd_adam_step")
+        _lib.launch("ubd_adam_step", self.model.device, self.model.params.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+                    self.v.data_ptr(), self.grads.numel(), self.iterations, o.lr, o.beta_1, o.beta_2, o.epsilon, grad_scale)
         self.model.invalidate_packed_weights()    # parameters changed behind torch's version counter
 
     def train_step_on_device(self, images, targets):
@@ -172,9 +162,7 @@ class Trainer:
         return images.to(dev, non_blocking=True), targets.to(device=dev, dtype=torch.int32, non_blocking=True)
 
     def _accumulate(self, loss, n_images, row):
-        with torch.cuda.device(self.model.device):
-            _lib.check(self._lib.ubd_epoch_accumulate(loss.data_ptr(), int(n_images), self._epoch_acc[row].data_ptr(),
-                                                      self.model._stream()), "ubd_epoch_accumulate")
+        _lib.launch("ubd_epoch_accumulate", self.model.device, loss.data_ptr(), int(n_images), self._epoch_acc[row].data_ptr())
 
     def test_step_on_device(self, images, targets):
         """Keras' test-mode step: the inference forward pass and the loss without its gradient.  Leaves the 16 floats in the
@@ -186,9 +174,8 @@ class Trainer:
         nbytes = int(self._lib.ubd_loss_workspace_bytes(mdl._h, n, mh, mw))
         if self._loss_ws is None or self._loss_ws.numel() < nbytes:
             self._loss_ws = torch.empty(nbytes, dtype=torch.uint8, device=mdl.device)
-        with torch.cuda.device(mdl.device):
-            _lib.check(self._lib.ubd_loss(mdl._h, logits.data_ptr(), targets.data_ptr(), n, mh, mw, self._val_loss.data_ptr(), None,
-                                          self._loss_ws.data_ptr(), self._loss_ws.numel(), mdl._stream()), "ubd_loss")
+        _lib.launch("ubd_loss", mdl.device, mdl._h, logits.data_ptr(), targets.data_ptr(), n, mh, mw, self._val_loss.data_ptr(), None,
+                    self._loss_ws.data_ptr(), self._loss_ws.numel())
         return self._val_loss
 
     def _run_steps(self, generator, steps, row, train):

@@ -14,13 +14,6 @@ from . import _lib
 from .net import PreprocessingType
 
 
-def _require_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("ubdvss_amd.visualizations needs an MI355X: there is no CPU fallback")
-    return torch
-
-
 def _pre_code(preprocessing):
     if preprocessing is None or preprocessing in (PreprocessingType.NONE, _lib.UBD_PRE_NONE, "none"):
         return _lib.UBD_PRE_NONE
@@ -43,8 +36,7 @@ def _map(torch, t, n, dtype, device, what):
 def _draw(images, preprocessing=None, gt=None, seg=None, found=None, cls=None):
     """One ubd_visualize_images call on the current stream; a source that is None is not drawn.  gt / seg: int32 maps whose
     positive entries are drawn, found: (quads, counts) int32, cls: int8 mask.  Returns {key: (N, H, W, 3) uint8 tensor}."""
-    torch = _require_gpu()
-    lib = _lib.load()
+    torch = _lib.require_gpu("ubdvss_amd.visualizations")
     if not torch.is_tensor(images) or not images.is_cuda:
         raise ValueError("images must be a device tensor (the numpy entry points upload them: compute_visualizations, draw_bboxes, ...)")
     if images.dim() == 3:
@@ -84,11 +76,10 @@ def _draw(images, preprocessing=None, gt=None, seg=None, found=None, cls=None):
 
     def ptr(t):
         return t.data_ptr() if t is not None else None
-    _lib.check(lib.ubd_visualize_images(
-        images.data_ptr(), in_dtype, _pre_code(preprocessing), n, hh, ww, c, int(mh), int(mw),
+    _lib.launch(
+        "ubd_visualize_images", dev, images.data_ptr(), in_dtype, _pre_code(preprocessing), n, hh, ww, c, int(mh), int(mw),
         ptr(maps.get("gt")), ptr(maps.get("seg_map")), ptr(quads), ptr(counts), cap, ptr(maps.get("classification_gt")),
-        ptr(out.get("gt")), ptr(out.get("seg_map")), ptr(out.get("postprocessed")), ptr(out.get("classification_gt")),
-        torch.cuda.current_stream(dev).cuda_stream), "ubd_visualize_images")
+        ptr(out.get("gt")), ptr(out.get("seg_map")), ptr(out.get("postprocessed")), ptr(out.get("classification_gt")))
     # the inputs were allocated (or are used) on this stream: the caching allocator reuses them in stream order
     return out
 
@@ -143,7 +134,7 @@ class Visualizer:
         One kernel launch; nothing leaves the device.  ``images`` must be a device tensor (ValueError otherwise).  The maps,
         the mask and the found objects are expected on the device too; a host array or CPU tensor among them is accepted
         and costs one upload each (``ModelRunner.run`` passes numpy label maps this way)."""
-        torch = _require_gpu()
+        torch = _lib.require_gpu("ubdvss_amd.visualizations")
         return _draw(images, preprocessing, gt=_positive(torch, gt_segmap, 0.5), seg=_positive(torch, predicted_segmap, 0.5),
                      found=_found_pair(found_objects), cls=pixel_classification_mask)
 
@@ -152,7 +143,7 @@ class Visualizer:
         """visualizations.py:20-49 with numpy in and numpy out: ``images`` are the original pictures (uint8, or floats that are
         cast as ``astype(np.uint8)`` after the denorm ``preprocessing`` names), ``found_objects`` lists of markup records per image.
         One transfer each way.  Returns a dict of (N, H, W, 3) uint8 arrays (indexable per image like the reference's lists)."""
-        torch = _require_gpu()
+        torch = _lib.require_gpu("ubdvss_amd.visualizations")
         x = _device_images(torch, images)
         quads, counts = _pack_markup(torch, found_objects)
         out = Visualizer.compute_visualizations_on_device(x, gt_segmap, predicted_segmap, (quads, counts), pixel_classification_mask,
@@ -164,7 +155,7 @@ class Visualizer:
     @staticmethod
     def visualize_segmentation_maps(images, targets, threshold=0.5):
         """visualizations.py:52-68: green where target > threshold; (N, H, W, 3) uint8 array"""
-        torch = _require_gpu()
+        torch = _lib.require_gpu("ubdvss_amd.visualizations")
         if len(images) != len(targets):
             raise AssertionError("one target per image is required")
         return _draw(_device_images(torch, images), gt=_positive(torch, targets, threshold))["gt"].cpu().numpy()
@@ -177,7 +168,7 @@ class Visualizer:
     @staticmethod
     def visualize_classification_masks(images, targets):
         """visualizations.py:71-79: green where the mask is 1, red where it is -1"""
-        torch = _require_gpu()
+        torch = _lib.require_gpu("ubdvss_amd.visualizations")
         if len(images) != len(targets):
             raise AssertionError("one target per image is required")
         if not torch.is_tensor(targets):
@@ -193,7 +184,7 @@ class Visualizer:
     @staticmethod
     def draw_bboxes(images, image_markups):
         """visualizations.py:94-105: every markup quad filled green at image resolution"""
-        torch = _require_gpu()
+        torch = _lib.require_gpu("ubdvss_amd.visualizations")
         if len(images) != len(image_markups):
             raise AssertionError("one markup list per image is required")
         return _draw(_device_images(torch, images), found=_pack_markup(torch, image_markups))["postprocessed"].cpu().numpy()
