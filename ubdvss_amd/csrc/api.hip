@@ -85,6 +85,7 @@ static const env_switch ENV_SWITCHES[] = {
     SW("UBD_STEM", fuse_stem, "fused", UBD_STEM_FUSED23), SW("UBD_STEM", fuse_force, "fused", 1),
     SW("UBD_STEM", fuse_stem, "fused123", UBD_STEM_FUSED123), SW("UBD_STEM", fuse_force, "fused123", 1),
     SW("UBD_STEM", fuse_stem, "unfused", UBD_STEM_SEPARATE),
+    SW("UBD_STEM123_SCHED", stem123_serial, "serial", 1),
     SW("UBD_TEST_NUM_CUS", num_cus, NUMBER, 0),
     SW("UBD_DILBWD", split_dilbwd, "split", 1), SW("UBD_DILBWD", no_pair_dilbwd, "pair8", 1),
     SW("UBD_SEPBWD", split_sepbwd32, "split", 1),

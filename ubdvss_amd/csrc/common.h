@@ -29,6 +29,7 @@ struct ubd_handle {
     // ONCE, in ubd_create, never in a launch path; a value that is not named here is ignored.
     int pp_lds_attr_set;      // pp_front_lds_kernel's dynamic-LDS limit has been raised on this handle's device
     int stem_cold_tail;       // UBD_STEM_COLD_TAIL=rows: tail rows of a job pass of the strip-walking stem (ubd_plan_stem clips it; 0: none -- the reference side of tests/test_gpu_stem_cold_tail.py); -1 (unset): the plan's default
+    int stem123_serial;       // UBD_STEM123_SCHED=serial: every row unit of phase A of the one-kernel fp32 stem (stem123.h) reads its six weight pieces from LDS in front of its MFMAs (the schedule before the pieces were held in registers for the phase, and the reference side of tests/test_gpu_stem_pipelined.py); 0 (default): read once per tile; the same bits
     int fuse_force;           // UBD_STEM named a fused variant explicitly: use it at any launch size
     int split_headbwd;        // UBD_HEADBWD=split: bf16 train step with classes: head data gradient and head weight gradient as two kernels (diagnostics / tests)
     int no_pair_dilbwd;       // UBD_DILBWD=pair8: narrow sub-grids (dilation 16 on 128-wide maps) keep the 8-wide tiles instead of pairs in 16-wide ones (diagnostics / tests)

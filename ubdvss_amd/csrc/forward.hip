@@ -756,11 +756,13 @@ static void launch_stem123(const ubd_handle *h, const float *params, const void 
     ubd_dispatch_input(h->cfg.c_in, u8, [&](auto cin, auto in_u8) {
         auto launch = [&](auto pl) {
             ubd_dispatch_bool(!COLD && tail_rows > 0, [&](auto tail) {       // a pass without a tail runs the instance that has the strip walk alone
-                if constexpr (COLD && decltype(tail)::value) return;
-                else hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD, decltype(tail)::value>),
-                                        dim3(grid), dim3(s23_cfg::NT), 0, st,
-                                        images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p, tail_rows
-                                        UBD_STAMP_ARG(COLD ? "" : "stem123"));      // the stamp indices are the strip walk's
+                ubd_dispatch_bool(h->stem123_serial == 0, [&](auto pipe) {    // phase A with L2's weight pieces held in registers, or (UBD_STEM123_SCHED=serial) read by every unit
+                    if constexpr (COLD && decltype(tail)::value) return;
+                    else hipLaunchKernelGGL((stem123_kernel<decltype(cin)::value, decltype(in_u8)::value, decltype(pl)::value, COLD, decltype(tail)::value, decltype(pipe)::value>),
+                                            dim3(grid), dim3(s23_cfg::NT), 0, st,
+                                            images, a3, sf0, b0, sf1, b1, sf2, b2, n, H, W, H2, W2, H4, W4, sc, sh, ticket, pj, a3_l2p, tail_rows
+                                            UBD_STAMP_ARG(COLD ? "" : "stem123"));      // the stamp indices are the strip walk's
+                });
             });
         };
         if constexpr (decltype(in_u8)::value == 0) { if (plain) return launch(ubd_int<1>{}); }

@@ -79,7 +79,9 @@ template <bool CW> struct s123_tpos { static constexpr bool cold = CW; int tx, t
 // TAIL: the instance a job pass with tail_rows > 0 launches.  The second instance of the tile loop costs the strip loop registers (spilled
 // VGPRs of the RGB instances: 17 -> 22 fp32 by LDS-DMA, 29 register-fed fp32, 30 uint8; grey: 17 as before; +3.8 us per pass at
 // 32 x 512 x 512 with both loops in every instance), so passes without a tail keep the kernel that has the strip walk alone.
-template <int CIN, int IN_U8, int PLAIN, bool COLD = false, bool TAIL = false>
+// WREG: phase A holds L2's weight pieces in registers (at the phase, below); false (UBD_STEM123_SCHED=serial): every unit reads its six
+// pieces in front of its MFMAs, the schedule before -- the same bits, and the reference side of tests/test_gpu_stem_pipelined.py.
+template <int CIN, int IN_U8, int PLAIN, bool COLD = false, bool TAIL = false, bool WREG = true>
 __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__restrict__ xin, float *__restrict__ y,
                                                                 const float *__restrict__ frag1, const float *__restrict__ bias1,
                                                                 const float *__restrict__ frag2, const float *__restrict__ bias2,
@@ -142,20 +144,24 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
     // filled below (ds_read_b128 per piece and N tile), and six of the nine piece products per N tile chained into accumulators
     // that hold the bias: U3 P1, U2 P2, U2 P1, U1 P3, U1 P2, U1 P1 -- grouped by weight piece, so that only one piece of the
     // weights (8 registers) is live at a time.  The large product is last: rounded once.  The two tiles' chains alternate (no back-to-back dependent pair).
-    auto pw_split = [&](const unsigned *tab, f32x4 v4, f32x2 v2, f32x4 &acc0, f32x4 &acc1) {
-        const u32x4 *w = (const u32x4 *)tab + lane;
+    // piece(k): piece 1 + k % 3 of N tile k / 3 -- read from the table where it is used (pw_split), or held in registers (phase A, WREG).
+    auto pw_pieces = [&](auto piece, f32x4 v4, f32x2 v2, f32x4 &acc0, f32x4 &acc1) {
         const f32x4 r4 = resid(v4), t4 = resid(r4);
         const f32x2 r2 = resid(v2), t2 = resid(r2);
         const u32x4 P1 = pack6(v4, v2), P2 = pack6(r4, r2), P3 = pack6(t4, t2);
-        u32x4 U0 = w[2 * 64], U1 = w[5 * 64];                                        // piece 3 of N tiles 0, 1
+        u32x4 U0 = piece(2), U1 = piece(5);                                          // piece 3 of N tiles 0, 1
         acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
-        U0 = w[1 * 64]; U1 = w[4 * 64];                                              // piece 2
+        U0 = piece(1); U1 = piece(4);                                                // piece 2
         acc0 = mfma16(U0, P2, acc0); acc1 = mfma16(U1, P2, acc1);
         acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
-        U0 = w[0]; U1 = w[3 * 64];                                                   // piece 1
+        U0 = piece(0); U1 = piece(3);                                                // piece 1
         acc0 = mfma16(U0, P3, acc0); acc1 = mfma16(U1, P3, acc1);
         acc0 = mfma16(U0, P2, acc0); acc1 = mfma16(U1, P2, acc1);
         acc0 = mfma16(U0, P1, acc0); acc1 = mfma16(U1, P1, acc1);
+    };
+    auto pw_split = [&](const unsigned *tab, f32x4 v4, f32x2 v2, f32x4 &acc0, f32x4 &acc1) {
+        const u32x4 *w = (const u32x4 *)tab + lane;
+        pw_pieces([&](int k) { return w[k * 64]; }, v4, v2, acc0, acc1);
     };
     // L1's eleven per-lane values (lane (i, q): input channel q, zero weights for q >= C_in) sit in an LDS table and are
     // re-read at the start of every phase 0b: kept in VGPRs across phase A they cost 11 spilled registers
@@ -532,6 +538,17 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
             // ---- phase A: L2 on positions (0..8, 1..32)
             const bool mask_needed = (R0 < 0) || (R0 + C::LR > H2) || (C0 + C::LC > W2);
             {
+                // WREG: L2's six weight pieces are read once per tile, with the first rows, and stay in registers for the phase (24; the phase
+                // has them to spare: the kernel's register peak is in phases 0b / B) -- a wave's two or three units then read no weights, and
+                // no unit's MFMAs wait for an LDS read issued directly in front of them.
+                // The uint8 RGB instance with both walks has no 24 registers to spare (three more reloads per tile): it holds piece 1 only,
+                // which the last six MFMAs of a unit take, and reads pieces 3 and 2 per unit.
+                constexpr bool WREG_ALL = !(IN_U8 && CIN == 3 && TAIL);
+                auto held = [](int k) { return WREG && (WREG_ALL || k == 0 || k == 3); };
+                const u32x4 *wtab = (const u32x4 *)pws + lane;
+                u32x4 wreg[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) if (held(k)) wreg[k] = wtab[k * 64];
                 float dwv[3][6];
 #pragma unroll
                 for (int o = 0; o < 3; ++o)
@@ -565,7 +582,10 @@ __global__ __launch_bounds__(s23_cfg::NT, 1) void stem123_kernel(const void *__r
                         if (yy >= 2) {
                             const int o = yy - 2;
                             f32x4 acc0 = b2A, acc1 = b2B;
-                            pw_split(pws, (f32x4){dwv[o][0], dwv[o][1], dwv[o][2], dwv[o][3]}, (f32x2){dwv[o][4], dwv[o][5]}, acc0, acc1);
+                            const f32x4 d4 = {dwv[o][0], dwv[o][1], dwv[o][2], dwv[o][3]};
+                            const f32x2 d2 = {dwv[o][4], dwv[o][5]};
+                            if constexpr (WREG) pw_pieces([&](int k) { return held(k) ? wreg[k] : wtab[k * 64]; }, d4, d2, acc0, acc1);
+                            else pw_split(pws, d4, d2, acc0, acc1);
                             float cap = __builtin_inff();
                             if (mask_needed) {
                                 const bool ok = (unsigned)(C0 + pos) < (unsigned)W2 && (unsigned)(R0 + rb + o) < (unsigned)H2;
