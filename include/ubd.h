@@ -389,18 +389,18 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
                         const int32_t *quads, const int32_t *counts, int n, int cap, const double *scales, double expand,
                         uint8_t *patches, int patch_h, int patch_w, int32_t *patch_quads, void *stream);
 
-/* --- decoding of the object patches: EAN-13 / UPC-A / EAN-8 ------------------------
+/* --- decoding of the object patches: EAN-13 / UPC-A / EAN-8 / UPC-E -----------------
  * The stage behind ubd_extract_objects: the digits of the retail symbol in every patch, read where the patches lie, so that
  * 64 bytes per object cross to the host instead of the patch.  One family, defined by the public EAN/UPC tables: EAN-13, UPC-A
- * (an EAN-13 whose first digit is 0) and EAN-8; `symbologies` is a mask whose bits are numbered over all families: bit 2,
+ * (an EAN-13 whose first digit is 0), EAN-8 and UPC-E; `symbologies` is a mask whose bits are numbered over all families: bit 2,
  * Code 128, has a result row of its own and is read by ubd_decode_text_patches below, not here.  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy restatement
  * tests/decode_oracle.py is matched bit for bit.
  *   patches (n, cap, patch_h, patch_w, channels) uint8 and counts (n) int32: DEVICE pointers, exactly as ubd_extract_objects
  *     writes and reads them; slots j >= min(counts[i], cap) are not read and their result rows are NOT written.
  *   params: HOST pointer, read before the call returns.
- *   results: DEVICE int32 (n, cap, 16): [0] symbology: 0 none, 13 or 8; [1] votes; [2] direction mask: bit 0 read left to
+ *   results: DEVICE int32 (n, cap, 16): [0] symbology: 0 none, 13, 8 or 6 (UPC-E); [1] votes; [2] direction mask: bit 0 read left to
  *     right, bit 1 read right to left (the patch is the half-turned one); [3..15] the digits, an EAN-8 fills eight and the rest
- *     is -1.  For "none" every digit is -1 and votes and mask are 0.
+ *     is -1; a UPC-E fills eight as well: number system, d1..d6, check digit.  For "none" every digit is -1 and votes and mask are 0.
  * Per patch:
  *   luma: the byte (1 channel) or (19595 R + 38470 G + 7471 B + 0x8000) >> 16 (3 channels: Pillow's convert('L')).
  *   scan lines k = 0..S-1: centre row r_k = ((2k + 1) * patch_h) / (2S); p[x] = the luma sum over the rows [r_k - b, r_k + b]
@@ -422,6 +422,19 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
  *     LGGLLG LGGGLL LGLGLG LGLGGL LGGLGL; any other word rejects), then six of {R}.  EAN-8: four of {L}, four of {R}.
  *   checksums: EAN-13 (10 - (d0 + d2 + .. + d10 + 3 (d1 + d3 + .. + d11)) % 10) % 10 == d12;
  *     EAN-8 (10 - (3 (d0 + d2 + d4 + d6) + d1 + d3 + d5) % 10) % 10 == d7.
+ *   UPC-E (bit 6): start guard of 3 runs, six characters of {L, G}, end guard of 6 runs (a space first): 33 runs, 51 modules.
+ *     Candidate: a light-to-dark edge i with 33 runs behind it, St = e[i + 33] - e[i].  The light run q before edge i must
+ *     satisfy 51 q >= QZ * St, the one after the last run 51 q >= max(QZ, 5) * St (a missing edge passes).  The five modules
+ *     hold whatever QZ says: start guard, six L / G characters, centre guard and the first bar of the right half of an EAN-13
+ *     have the shape of a UPC-E, and its parity word can be one of the twenty below (first digit 1, LLGLGG, is the word 0B of
+ *     number system 1); as many UPC-E votes as EAN-13 votes would turn a good EAN-13 into "none".  No run inside an EAN symbol
+ *     is wider than 4 modules, so the run behind that first bar fails the test.  Every run w of the two guards must satisfy
+ *     (2 * 51 * w + St) / (2 St) == 1.  The six characters are read by the rule above.  Parity word: a set bit = G, the first
+ *     character in the top bit; for number system 0 and the check digits 0..9 the words are 38 34 32 31 2C 26 23 2A 29 25
+ *     (hexadecimal), number system 1 has their 6-bit complements, any other word rejects.  The digits d1..d6 stand for the
+ *     UPC-A number NS a1..a10: d6 in 0..2: d1 d2 d6 0 0 0 0 d3 d4 d5; d6 = 3: d1 d2 d3 0 0 0 0 0 d4 d5; d6 = 4: d1 d2 d3 d4 0 0 0
+ *     0 0 d5; d6 in 5..9: d1 d2 d3 d4 d5 0 0 0 0 d6; and (10 - (3 (NS + a2 + a4 + a6 + a8 + a10) + a1 + a3 + a5 + a7 + a9) % 10)
+ *     % 10 must equal the check digit the parity word gave.  0 123456 5 is valid: 0 12345 00006 has the check digit 5.
  *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
  *     (symbology, digits).  The payload with the most votes wins, its mask is the OR of the directions that voted for it; fewer
  *     than min_votes, or another payload with as many votes: none.
@@ -429,9 +442,13 @@ int ubd_extract_objects(const uint8_t *src, size_t src_bytes, const int64_t *src
  * pointer, n >= 1, cap >= 1, n * cap < 2^31, patch_w 32..1024, patch_h 1..1024, channels 1 or 3, and the ranges below.
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 typedef struct ubd_decode_params {
-    int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8: ubd_decode_patches takes 1..3; bit 2 Code 128:
-                                        ubd_decode_text_patches takes 4; bit 3 ITF, bit 4 Code 39: ubd_decode_width_patches
-                                        takes 8, 16 or 24.  The bits are numbered over all families */
+    int32_t symbologies;             /* bit 0 EAN-13 (UPC-A included), bit 1 EAN-8, bit 6 UPC-E: ubd_decode_patches takes any
+                                        non-empty subset of 1 | 2 | 64; bit 2 Code 128, bit 7 Code 93: ubd_decode_text_patches
+                                        takes 4, 128 or 132; bit 3 ITF, bit 4 Code 39, bit 8 Codabar: ubd_decode_width_patches
+                                        takes any non-empty subset of 8 | 16 | 256.  The bits are numbered over all families.
+                                        Bit 5 (32) is skipped: it was held back as the first bit no family reads when bits
+                                        0..4 were given out, callers and tests rely on every layer refusing it, and so the
+                                        three symbologies that came later took 6..8 and 32 stays unassigned */
     int32_t scan_rows;               /* S, 1..32        default 8  */
     int32_t band;                    /* b, 0..8         default 1  */
     int32_t window;                  /* R, 1..64        default 16 */
@@ -442,13 +459,14 @@ typedef struct ubd_decode_params {
 int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                        const ubd_decode_params *params, int32_t *results, void *stream);
 
-/* --- decoding of the object patches: Code 128 / GS1-128 ------------------------------
+/* --- decoding of the object patches: Code 128 / GS1-128 / Code 93 ---------------------
  * The second family behind ubd_extract_objects: the text of the Code 128 symbol in every patch, 128 bytes per object.  The
  * contract is that of ubd_decode_patches (device patches and counts as ubd_extract_objects writes them, params a HOST pointer
  * read before the call returns, slots j >= min(counts[i], cap) neither read nor written), the params struct is the same, and
- * `symbologies` must be 4 (bit 2).  Integer arithmetic only (every division floors, every dividend is non-negative); the numpy
- * restatement tests/text_decode_oracle.py is matched bit for bit.
- *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 128, or 0 for none; [1] votes; [2] direction mask (bit 0 read
+ * `symbologies` must be 4 (bit 2, Code 128), 128 (bit 7, Code 93) or 132 (both).  Integer arithmetic only (every division
+ * floors, every dividend is non-negative); the numpy restatements tests/text_decode_oracle.py (Code 128) and
+ * tests/extra_decode_oracle.py (Code 93 and the two together) are matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 128, or 0 for none (a Code 93 row is laid out below); [1] votes; [2] direction mask (bit 0 read
  *     left to right, bit 1 read right to left: the patch is the half-turned one); [3] T, the number of text elements; [4] flags,
  *     bit 0: the first data character is FNC1 (GS1-128); [5] D, the number of data symbol characters; [6] the start value
  *     (103 / 104 / 105); [7] the check value; [8 .. 8 + T) the text elements; the rest 0xFF.  For "none" bytes 0..7 are 0 and
@@ -477,29 +495,50 @@ int ubd_decode_patches(const uint8_t *patches, const int32_t *counts, int n, int
  *     4. at the stop edge j+7 must exist and the last bar b = e_(j+7) - e_(j+6) satisfy (22 b + S) / (2 S) == 2; if edge j+8
  *        exists: 11 (e_(j+8) - e_(j+7)) >= QZ * S;
  *     5. the values are start, d_1..d_D, check: D >= 1 and (start + sum k d_k) mod 103 == check.
- *   votes: per (line, direction) only the valid candidate with the lowest start index counts, one vote for its whole value
- *     sequence (sequences are compared in full).  The sequence with the most votes wins, its mask is the OR of the directions
+ *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
+ *     (symbology, whole value sequence), compared in full.  The sequence with the most votes wins, its mask is the OR of the directions
  *     that voted for it; fewer than min_votes, or another sequence with as many votes: none.
  *   text of the winner: the set in force comes from the start value (A, B, C).  In set C the values 0..99 are two digit
  *     characters, 100 switches to B, 101 to A, 102 is FNC1.  In sets A and B: 0..95 are ASCII (A: 0..63 -> 32..95, 64..95 ->
  *     0..31; B: 0..95 -> 32..127), 96 FNC3, 97 FNC2, 98 Shift (the next one data character is read in the other of A and B; a
  *     Shift as the last data character is dropped, a shifted Shift is a Shift again), 99 switches to C, 100 is Code B in A and
  *     FNC4 in B, 101 is FNC4 in A and Code A in B, 102 FNC1.  D <= 60 bounds T at 120.
+ *   Code 93 (bit 7) character: six runs w0..w5 (a bar first) of sum S, nine modules; E_k = (18 (w_k + w_(k+1)) + S) / (2 S) for
+ *     k = 0..3, each in 2..5; the pattern n0..n5 is the one of the table with n_k + n_(k+1) == E_k for all four k (the 48 keys
+ *     are distinct); with V = n0 + n2 + n4 it must satisfy 2 |9 (w0 + w2 + w4) - S V| < 3 S (the table holds 48 of the 56
+ *     six-run compositions of 9).  Table, run widths for the values 0..47:
+ *     131112 111213 111312 111411 121113 121212 121311 111114 131211 141111 211113 211212 211311 221112 221211 231111 112113
+ *     112212 112311 122112 132111 111123 111222 111321 121122 131121 212112 212211 211122 211221 221121 222111 112122 112221
+ *     122121 123111 121131 311112 311211 321111 112131 113121 211131 121221 312111 311121 122211 111141
+ *     0..9 are the digits, 10..35 A..Z, 36..42 - . space $ / + %, 43..46 the shifts ($) (%) (/) (+), 47 is start / stop.
+ *   Code 93 candidate at a light-to-dark edge i:
+ *     1. the character at i (edges i..i+6) is 47; S_0 is its width;
+ *     2. if i >= 1: 9 (e_i - e_(i-1)) >= QZ * S_0;
+ *     3. the characters at j = i + 6, i + 12, ..: the edges j..j+6 must exist, 3 S_prev <= 4 S <= 5 S_prev, and the character
+ *        must decode; 47 is the stop, every other value counts; a 63rd value before a stop rejects the candidate;
+ *     4. at the stop edge j+7 must exist and the termination bar b = e_(j+7) - e_(j+6) satisfy (18 b + S) / (2 S) == 1; if edge
+ *        j+8 exists: 9 (e_(j+8) - e_(j+7)) >= QZ * S;
+ *     5. the values are d_1..d_D, C, K with 1 <= D <= 60; C == (sum of d_k * weight) mod 47 with the weights 1..20 cycling from
+ *        the right (d_D weighs 1), and K == the same sum over d_1..d_D, C with the weights 1..15.  "TEST93" has C = 41 (+), K = 6.
+ *     Read backwards a Code 93 begins with its termination bar, which starts no character: it votes in one direction.
+ *   Code 93 result row: [0] 93; [1] votes; [2] direction mask; [3] T = D; [4] 0; [5] D; [6] C; [7] K; [8 .. 8 + D) one element
+ *     per data value: the ASCII code for 0..42, 0xE1..0xE4 for the shifts 43..46 (shift pairs are not interpreted); the rest 0xFF.
  * Limits (non-zero return, ubd_last_error begins with "ubd_decode_text_patches", nothing launched, nothing written): those of
  * ubd_decode_patches (no null pointer, n >= 1, cap >= 1, n * cap < 2^31, patch_w 32..1024, patch_h 1..1024, channels 1 or 3,
- * the ranges of ubd_decode_params), symbologies == 4, results aligned to 4 bytes.
+ * the ranges of ubd_decode_params), symbologies 4, 128 or 132, results aligned to 4 bytes.
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                             const ubd_decode_params *params, uint8_t *results, void *stream);
 
-/* --- decoding of the object patches: Interleaved 2 of 5 (ITF) / Code 39 ---------------
+/* --- decoding of the object patches: Interleaved 2 of 5 (ITF) / Code 39 / Codabar -----
  * The third family behind ubd_extract_objects: the two-width codes, in which every bar and every space is either narrow or
- * wide: the digits of an ITF symbol (ITF-14 included) or the characters of a Code 39 symbol in every patch, 128 bytes per
- * object.  The contract is that of ubd_decode_text_patches (device patches and counts as ubd_extract_objects writes them, params
+ * wide: the digits of an ITF symbol (ITF-14 included) or the characters of a Code 39 or Codabar symbol in every patch, 128
+ * bytes per object.  The contract is that of ubd_decode_text_patches (device patches and counts as ubd_extract_objects writes them, params
  * a HOST pointer read before the call returns, slots j >= min(counts[i], cap) neither read nor written), the params struct is
- * the same, and `symbologies` must be 8 (bit 3, ITF), 16 (bit 4, Code 39) or 24 (both).  Integer arithmetic only, and no rule
- * divides; the numpy restatement tests/width_decode_oracle.py is matched bit for bit.
- *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 25 (ITF) or 39 (Code 39), or 0 for none; [1] votes; [2]
+ * the same, and `symbologies` must be a non-empty subset of 8 (bit 3, ITF), 16 (bit 4, Code 39) and 256 (bit 8, Codabar).
+ * Integer arithmetic only, and no rule divides; the numpy restatements tests/width_decode_oracle.py (ITF, Code 39) and
+ * tests/extra_decode_oracle.py (Codabar and the three together) are matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 25 (ITF), 39 (Code 39) or 27 (Codabar), or 0 for none; [1] votes; [2]
  *     direction mask (bit 0 read left to right, bit 1 read right to left: the patch is the half-turned one); [3] T, the number of
  *     text elements; [4] flags, bit 0: the optional check character holds (below; informational, it never rejects); [5..7] 0;
  *     [8 .. 8 + T) the ASCII codes of the elements; the rest 0xFF.  For "none" bytes 0..7 are 0 and bytes 8..127 are 0xFF.
@@ -538,11 +577,30 @@ int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n
  *     The T elements are the data characters as ASCII; pairs of Full ASCII are not interpreted.  Flag bit 0 (the modulo-43
  *     check character): T >= 2 and (the sum of the first T-1 values) % 43 == the last value; "CODE 39" sums to 113, its check
  *     character is R (27).
+ *   Codabar (bit 8) character: seven runs (a bar first).  The four bars are one group and the three spaces another, classified
+ *     separately as those of an ITF pair are, with one rule beside the group rule: a group whose greatest run is less than
+ *     1.5 times its least (2 hi < 3 lo) has no wide run and is valid.  (First proposal: the seven runs as one group, as a Code 39
+ *     character's nine are.  The acceptance set moved it: at a narrow run of 2 pixels and a ratio of 2, blurred, the wide bars
+ *     of : / . + come out at 3.8 pixels and their narrow spaces at 2.8, which one group cannot tell apart.)  The pattern is the
+ *     mask of the wide runs, the first run in the top bit; for 0123456789-$:/.+ABCD the masks are 03 06 09 60 12 42 21 24 30 48
+ *     0C 18 45 51 54 15 1A 29 0B 0E (hexadecimal); any other mask is no character.  A character's value is its index in that
+ *     list.  N is the sum of its narrow runs and c their number (5 for the values 0..11, 4 for the others), S its width.
+ *   Codabar candidate at a light-to-dark edge i:
+ *     1. the character at i (edges i..i+7) is one of A B C D;
+ *     2. if i >= 1: 4 (e_i - e_(i-1)) >= QZ * N;
+ *     3. characters at j = i + 8, i + 16, ..: the edges j..j+7 must exist; the gap g = e_j - e_(j-1) must satisfy
+ *        N_prev <= 2 c_prev g (half a mean narrow run) and 2 g <= S_prev; the character must decode; character widths differ
+ *        inside a symbol, so neighbours are compared by their mean narrow runs: 3 N_prev c <= 4 N c_prev <= 5 N_prev c.  One of
+ *        A B C D is the stop, every other character is data; a 61st data character rejects the candidate, and so does a stop
+ *        behind none;
+ *     4. if edge j+8 exists behind the stop: 4 (e_(j+8) - e_(j+7)) >= QZ * N of the stop.
+ *     The T elements are all characters, start and stop included, as ASCII.  Flag bit 0: the sum of all T values is 0 modulo 16
+ *     (informational).  No start pattern read backwards (2C 4A 68 38) is in the table, so a symbol votes in one direction.
  *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
  *     (symbology, all elements), compared in full.  The payload with the most votes wins, its mask is the OR of the directions
  *     that voted for it; fewer than min_votes, or another payload with as many votes: none.
  * Limits (non-zero return, ubd_last_error begins with "ubd_decode_width_patches", nothing launched, nothing written): those
- * of ubd_decode_text_patches, with symbologies 8, 16 or 24.
+ * of ubd_decode_text_patches, with symbologies a non-empty subset of 8 | 16 | 256.
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 int ubd_decode_width_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                              const ubd_decode_params *params, uint8_t *results, void *stream);

@@ -11,7 +11,12 @@ own family decoded to what was drawn (the other family's must all read as none).
 The two-width kernel is timed twice: on those patches, which hold nothing of its family (the cost of looking), and on a workload
 of its own of the same shape (``width_workload``: in turn an ITF of six to ten digits and a Code 39 of two to four characters,
 2 pixels per narrow run, wide runs of 5, the same noise, every other one half-turned).
-Usage: python tools/bench_decode_text.py [--iters 200] [--calls 20]
+With --extra, three more pairs of lines follow: UPC-E (bit 6), Code 93 (bit 7) and Codabar (bit 8), each read by its family's
+kernel under its own bit alone, once on a workload of its own symbols of the same shape (``extra_workload``: UPC-E and Code 93 of
+five to seven characters at 2 pixels per module, Codabar of four to eight data characters at 2 pixels per narrow run and wide
+runs of 5) and once on the first workload, where it finds none.  The lines without --extra are unchanged, so that a library from
+before these symbologies can be timed beside this one.
+Usage: python tools/bench_decode_text.py [--iters 200] [--calls 20] [--extra]
 """
 import argparse
 import ctypes
@@ -29,6 +34,7 @@ import decode_cases as dc  # noqa: E402
 import text_decode_cases as tc  # noqa: E402
 import text_decode_oracle as to  # noqa: E402
 import width_decode_cases as wc  # noqa: E402
+import extra_decode_cases as xc  # noqa: E402
 from ubdvss_amd import _lib, barcode_decoder  # noqa: E402
 
 ALPHABET = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz-/.+"
@@ -81,6 +87,31 @@ def width_workload(n=32, cap=4, ph=64, pw=256, seed=2):
     return patches, drawn
 
 
+def extra_workload(kind, n=32, cap=4, ph=64, pw=256, seed=3):
+    """kind 'upce' / 'code93' / 'codabar' -> (patches (n, cap, ph, pw, 3), drawn (n, cap): the text a record must show)"""
+    rng = np.random.default_rng(seed)
+    patches = np.zeros((n, cap, ph, pw, 3), np.uint8)
+    drawn = np.empty((n, cap), object)
+    for i in range(n):
+        for j in range(cap):
+            if kind == "upce":
+                eight = xc.upce_digits(int(rng.integers(0, 2)), [int(d) for d in rng.integers(0, 10, 6)])
+                drawn[i, j], mods, px = "".join(map(str, eight)), xc.upce_modules(eight), 2
+            elif kind == "code93":
+                drawn[i, j] = "".join(xc.C93_ALPHABET[int(k)] for k in rng.integers(0, 43, int(rng.integers(5, 8))))
+                mods, px = xc.c93_modules(xc.c93_values(drawn[i, j])), 2
+            else:
+                data = "".join("0123456789-$:/.+"[int(k)] for k in rng.integers(0, 16, int(rng.integers(4, 9))))
+                drawn[i, j] = "ABCD"[int(rng.integers(0, 4))] + data + "ABCD"[int(rng.integers(0, 4))]
+                mods, px = xc.cbr_modules(drawn[i, j], 2, 5), 1
+            row = tc.flat_row_modules([mods], px, pw, (pw - px * len(mods)) // 2).astype(np.float64)
+            grey = np.clip(np.rint(row[None, :] + rng.normal(0, 6.0, (ph, pw))), 0, 255).astype(np.uint8)
+            if j % 2:
+                grey = grey[::-1, ::-1]
+            patches[i, j] = grey[:, :, None]
+    return patches, drawn
+
+
 def time_calls(call, iters, calls):
     for _ in range(5):
         call()
@@ -101,6 +132,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--calls", type=int, default=20, help="calls per timed window")
+    ap.add_argument("--extra", action="store_true", help="also UPC-E, Code 93 and Codabar, each under its own bit")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.load()
@@ -151,6 +183,28 @@ def main():
                           "us_p90": round(float(np.percentile(times, 90)), 1), "objects": n * cap, "own_family": len(own),
                           "decoded_correctly": int(correct), "other_family_read": int(stray),
                           "objects_per_s": round(n * cap / us * 1e6)}), flush=True)
+    if not args.extra:
+        return
+    for kind, bit, entry, out, to_records in (
+            ("upce", barcode_decoder.UPCE, "ubd_decode_patches", retail, barcode_decoder.results_to_records),
+            ("code93", barcode_decoder.CODE93, "ubd_decode_text_patches", text, barcode_decoder.text_results_to_records),
+            ("codabar", barcode_decoder.CODABAR, "ubd_decode_width_patches", width, barcode_decoder.width_results_to_records)):
+        host_kind, drawn_kind = extra_workload(kind, n, cap, ph, pw)
+        kind_patches = torch.from_numpy(host_kind).cuda()
+        p_kind = barcode_decoder.make_params(symbologies=bit)
+        for which, name in ((kind_patches, "own_workload"), (patches, "first_workload")):
+            def call(which=which):
+                _lib.check(getattr(lib, entry)(which.data_ptr(), counts.data_ptr(), n, cap, ph, pw, c, ctypes.byref(p_kind), out.data_ptr(),
+                                               stream), entry)
+            times = time_calls(call, args.iters, args.calls)
+            got = to_records(out, counts)
+            read = sum(got[i][j] is not None for i, j in slots)
+            correct = sum(got[i][j] is not None and got[i][j].text == drawn_kind[i, j] for i, j in slots) if name == "own_workload" else 0
+            us = float(np.median(times))
+            print(json.dumps({"leg": f"{entry}_{kind}_bit{bit}_{name}_n{n}_cap{cap}_{ph}x{pw}x{c}", "iters": args.iters,
+                              "calls_per_window": args.calls, "us_median": round(us, 1), "us_min": round(float(np.min(times)), 1),
+                              "us_p90": round(float(np.percentile(times, 90)), 1), "objects": n * cap, "read": int(read),
+                              "decoded_correctly": int(correct), "objects_per_s": round(n * cap / us * 1e6)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,9 @@ A patch may be the half-turned one (object_patches.py): both reading directions 
 The text of Code 128 / GS1-128 symbols is a second kernel with a result row of its own (``ubd_decode_text_patches``, 128 bytes
 per object; tests/text_decode_oracle.py): ``decode_text_patches_on_device`` and ``text_results_to_records``.  The two-width codes,
 ITF and Code 39, are a third (``ubd_decode_width_patches``, 128 bytes per object; tests/width_decode_oracle.py):
-``decode_width_patches_on_device`` and ``width_results_to_records``."""
+``decode_width_patches_on_device`` and ``width_results_to_records``.  UPC-E, Code 93 and Codabar are further symbologies of the
+three kernels (bits 6, 7 and 8; tests/extra_decode_oracle.py).  Beside the records stand three host helpers for what the device
+leaves uninterpreted: ``upce_to_upca``, ``full_ascii`` (the shift pairs of Code 39 and Code 93) and ``code32_to_digits``."""
 import collections
 import ctypes
 
@@ -17,25 +19,31 @@ from . import _lib
 EAN13, EAN8 = 1, 2                                       # bits of ``symbologies``
 CODE128 = 4                                              # bit 2: read by ubd_decode_text_patches, not by ubd_decode_patches
 ITF, CODE39 = 8, 16                                      # bits 3 and 4: read by ubd_decode_width_patches
+UPCE, CODE93, CODABAR = 64, 128, 256                     # bits 6, 7, 8: read by the retail, the text and the two-width entry point; bit 5 is unassigned
+ALL_SYMBOLOGIES = 479
 DEFAULT_PARAMS = dict(symbologies=EAN13 | EAN8, scan_rows=8, band=1, window=16, contrast=24, quiet=3, min_votes=2)
 RESULT_INTS = 16
 TEXT_RESULT_BYTES = 128
 WIDTH_RESULT_BYTES = 128
 FNC1, FNC2, FNC3, FNC4 = 0xF1, 0xF2, 0xF3, 0xF4          # text elements of a Code 128 result beside the ASCII codes 0..127
+SHIFT1, SHIFT2, SHIFT3, SHIFT4 = 0xE1, 0xE2, 0xE3, 0xE4  # text elements of a Code 93 result: the shifts ($) (%) (/) (+)
 
 DecodedBarcode = collections.namedtuple("DecodedBarcode", ["symbology", "text", "votes", "upside_down", "is_upc_a"])
-DecodedBarcode.__doc__ = """One decoded object.  symbology: 'EAN-13' or 'EAN-8'; text: all its digits, the check digit included;
+DecodedBarcode.__doc__ = """One decoded object.  symbology: 'EAN-13', 'EAN-8' or 'UPC-E'; text: all its digits, the check digit included
+(of a UPC-E the eight: number system, six digits, check digit; ``upce_to_upca`` gives its UPC-A number);
 votes: the (scan line, direction) readings that agreed; upside_down: the patch was read right to left only (it is the half-turned
 one); is_upc_a: an EAN-13 whose first digit is 0 (its UPC-A number is text[1:])."""
 
 DecodedText = collections.namedtuple("DecodedText", ["symbology", "text", "votes", "upside_down", "gs1", "elements"])
-DecodedText.__doc__ = """One decoded Code 128 object.  symbology: 'Code 128'; text: its ASCII elements as a str, a leading FNC1 dropped
+DecodedText.__doc__ = """One decoded Code 128 or Code 93 object.  symbology: 'Code 128' or 'Code 93' (of a Code 93 text holds the data
+characters, a shift as '\\xe1'..'\\xe4' for ($) (%) (/) (+), which ``full_ascii`` resolves; gs1 is False); text: its ASCII elements as a str, a leading FNC1 dropped
 (it sets gs1), any later FNC1 as '\\x1d', FNC2..FNC4 left out; votes and upside_down as in DecodedBarcode; gs1: the first data
 character is FNC1 (GS1-128); elements: every text element as a tuple of integers, ASCII codes 0..127 and 0xF1..0xF4 for FNC1..FNC4."""
 
 DecodedWidth = collections.namedtuple("DecodedWidth", ["symbology", "text", "votes", "upside_down", "checked"])
-DecodedWidth.__doc__ = """One decoded two-width object.  symbology: 'ITF' or 'Code 39'; text: its digits or characters (of a Code 39
-the data between the two '*'; Full ASCII pairs are left as they are); votes and upside_down as in DecodedBarcode; checked: the
+DecodedWidth.__doc__ = """One decoded two-width object.  symbology: 'ITF', 'Code 39' or 'Codabar'; text: its digits or characters (of a Code 39
+the data between the two '*'; Full ASCII pairs are left as they are; of a Codabar every character, its start and stop A..D included,
+and checked says that all their values sum to 0 modulo 16); votes and upside_down as in DecodedBarcode; checked: the
 last element is the optional check character of the rest (GS1's modulo 10 for ITF, modulo 43 for Code 39) -- it stays in text."""
 
 
@@ -87,7 +95,7 @@ def decode_patches_on_device(patches, counts, **params):
 
 def decode_text_patches_on_device(patches, counts, **params):
     """``patches`` and ``counts`` as for ``decode_patches_on_device``; ``params`` the same keywords, ``symbologies`` defaulting to
-    CODE128 (the only value ``ubd_decode_text_patches`` takes).  Returns the uint8 device tensor (n, cap, 128) of
+    CODE128 (``ubd_decode_text_patches`` takes CODE128, CODE93 or both; a Code 93 row is [93, votes, mask, D, 0, D, C, K, D elements]).  Returns the uint8 device tensor (n, cap, 128) of
     ``ubd_decode_text_patches``: [128 or 0, votes, direction mask, T, flags, D, start value, check value, T text elements, 0xFF..];
     rows of slots that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream;
     nothing is read back."""
@@ -97,7 +105,7 @@ def decode_text_patches_on_device(patches, counts, **params):
 
 def decode_width_patches_on_device(patches, counts, **params):
     """``patches`` and ``counts`` as for ``decode_patches_on_device``; ``params`` the same keywords, ``symbologies`` defaulting to
-    ITF | CODE39 (``ubd_decode_width_patches`` takes 8, 16 or 24).  Returns the uint8 device tensor (n, cap, 128) of
+    ITF | CODE39 (``ubd_decode_width_patches`` takes any of ITF, CODE39, CODABAR; byte 0 of a Codabar row is 27).  Returns the uint8 device tensor (n, cap, 128) of
     ``ubd_decode_width_patches``: [25, 39 or 0, votes, direction mask, T, flags, 0, 0, 0, T ASCII codes, 0xFF..]; rows of slots
     that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream; nothing is read back."""
     return _launch("ubd_decode_width_patches", patches, counts, dict({"symbologies": ITF | CODE39}, **params), WIDTH_RESULT_BYTES,
@@ -116,6 +124,8 @@ def _text_record(row):
     if code == 0:
         return None
     elements = tuple(int(v) for v in row[8:8 + t])
+    if code == 93:
+        return DecodedText("Code 93", "".join(chr(v) for v in elements), votes, mask == 2, False, elements)
     gs1 = bool(flags & 1)
     text = "".join("\x1d" if v == FNC1 else chr(v) for v in elements[1 if gs1 else 0:] if v < 128 or v == FNC1)
     return DecodedText("Code 128", text, votes, mask == 2, gs1, elements)
@@ -125,15 +135,15 @@ def _width_record(row):
     code, votes, mask, t, flags = (int(v) for v in row[:5])
     if code == 0:
         return None
-    return DecodedWidth("ITF" if code == 25 else "Code 39", "".join(chr(int(v)) for v in row[8:8 + t]), votes, mask == 2, bool(flags & 1))
+    return DecodedWidth({25: "ITF", 39: "Code 39", 27: "Codabar"}[code], "".join(chr(int(v)) for v in row[8:8 + t]), votes, mask == 2, bool(flags & 1))
 
 
 def _retail_record(row):
     code, votes, mask = (int(v) for v in row[:3])
     if code == 0:
         return None
-    text = "".join(str(int(d)) for d in row[3:3 + code])
-    return DecodedBarcode("EAN-13" if code == 13 else "EAN-8", text, votes, mask == 2, code == 13 and text[0] == "0")
+    text = "".join(str(int(d)) for d in row[3:3 + (8 if code == 6 else code)])
+    return DecodedBarcode({13: "EAN-13", 8: "EAN-8", 6: "UPC-E"}[code], text, votes, mask == 2, code == 13 and text[0] == "0")
 
 
 def text_results_to_records(results, counts):
@@ -152,3 +162,92 @@ def results_to_records(results, counts):
     """(n, cap, 16) results (device tensor or array) and counts (n) -> per image a list of min(counts[i], cap) entries, a
     ``DecodedBarcode`` or None where nothing was read"""
     return _records(results, counts, _retail_record)
+
+
+def upce_to_upca(text):
+    """the eight digits of a UPC-E (number system, six digits, check digit; ``DecodedBarcode.text``) or its six middle digits with
+    number system 0 -> the twelve digits of the UPC-A number it stands for, the check digit computed.  ValueError for anything else."""
+    text = str(text)
+    if not text.isdigit() or len(text) not in (6, 8) or (len(text) == 8 and text[0] not in "01"):
+        raise ValueError(f"a UPC-E is six digits, or number system 0 / 1, six digits and a check digit; got {text!r}")
+    ns, d = (text[0], text[1:7]) if len(text) == 8 else ("0", text)
+    if d[5] in "012":
+        body = d[0:2] + d[5] + "0000" + d[2:5]
+    elif d[5] == "3":
+        body = d[0:3] + "00000" + d[3:5]
+    elif d[5] == "4":
+        body = d[0:4] + "00000" + d[4]
+    else:
+        body = d[0:5] + "0000" + d[5]
+    eleven = ns + body
+    check = (10 - (3 * sum(int(c) for c in eleven[0::2]) + sum(int(c) for c in eleven[1::2])) % 10) % 10
+    if len(text) == 8 and int(text[7]) != check:
+        raise ValueError(f"the check digit of {text!r} should be {check}")
+    return eleven + str(check)
+
+
+_C39_SHIFTS = "$%/+"                                     # the four shift characters of Code 39 in the order of Code 93's SHIFT1..SHIFT4
+_PERCENT = {**{chr(65 + k): chr(27 + k) for k in range(5)}, **{chr(70 + k): chr(59 + k) for k in range(5)},
+            **{chr(75 + k): chr(91 + k) for k in range(5)}, **{chr(80 + k): chr(123 + k) for k in range(5)},
+            "U": "\x00", "V": "@", "W": "`", "X": "\x7f", "Y": "\x7f", "Z": "\x7f"}
+
+
+def full_ascii(text_or_elements):
+    """The Full ASCII reading of a Code 39 text (``DecodedWidth.text``: the pairs $A %A /A +A are written with the data characters
+    $ % / +) or of a Code 93 (``DecodedText.text`` or ``.elements``: the shifts are SHIFT1..SHIFT4, '\\xe1'..'\\xe4').  $A..$Z are
+    the control characters 1..26, %A..%E 27..31, %F..%J ; < = > ?, %K..%O [ \\ ] ^ _, %P..%T { | } ~ DEL, %U NUL, %V @, %W `,
+    %X..%Z DEL, /A../O ! .. /, /Z :, +A..+Z a..z.  In a str without SHIFT elements every $ % / + is a shift (Code 39); with
+    elements, or a str that holds '\\xe1'..'\\xe4', only those are.  Returns the str, or None on an invalid pair."""
+    items = [ord(c) for c in text_or_elements] if isinstance(text_or_elements, str) else [int(v) for v in text_or_elements]
+    code93 = not isinstance(text_or_elements, str) or any(SHIFT1 <= v <= SHIFT4 for v in items)
+    out, k = [], 0
+    while k < len(items):
+        v = items[k]
+        shift = v - SHIFT1 if SHIFT1 <= v <= SHIFT4 else _C39_SHIFTS.find(chr(v)) if not code93 and v < 128 else -1
+        if shift < 0:
+            if v >= 128:
+                return None
+            out.append(chr(v))
+            k += 1
+            continue
+        if k + 1 >= len(items) or not 65 <= items[k + 1] <= 90:
+            return None
+        letter = chr(items[k + 1])
+        if shift == 0:
+            out.append(chr(ord(letter) - 64))
+        elif shift == 1:
+            out.append(_PERCENT[letter])
+        elif shift == 2:
+            if letter <= "O":
+                out.append(chr(ord(letter) - 32))
+            elif letter == "Z":
+                out.append(":")
+            else:
+                return None
+        else:
+            out.append(letter.lower())
+        k += 2
+    return "".join(out)
+
+
+_CODE32 = "0123456789BCDFGHJKLMNPQRSTUVWXYZ"            # base 32 without the vowels
+
+
+def code32_to_digits(text):
+    """Code 32, the Italian pharmacode carried by a Code 39 of six characters: ``DecodedWidth.text`` -> its nine digits (eight and
+    a check digit, printed behind an 'A'), or None where the text is no Code 32: another length or alphabet, a value of nine
+    digits or more, or a check digit that does not hold (every second digit doubled, the digits of the products summed, modulo 10)."""
+    text = str(text)
+    if len(text) != 6 or any(c not in _CODE32 for c in text):
+        return None
+    value = 0
+    for c in text:
+        value = value * 32 + _CODE32.index(c)
+    if value >= 10 ** 9:
+        return None
+    digits = f"{value:09d}"
+    total = 0
+    for k, c in enumerate(digits[:8]):
+        v = int(c) * (2 if k % 2 else 1)
+        total += v // 10 + v % 10
+    return digits if total % 10 == int(digits[8]) else None

@@ -1,5 +1,5 @@
-// The part of the patch decoders that does not know a symbology.  decode.hip (EAN-13 / UPC-A / EAN-8), decode_text.hip
-// (Code 128) and decode_width.hip (ITF, Code 39) include it and add a policy struct each (what a policy holds is listed at
+// The part of the patch decoders that does not know a symbology.  decode.hip (EAN-13 / UPC-A / EAN-8 / UPC-E), decode_text.hip
+// (Code 128, Code 93) and decode_width.hip (ITF, Code 39, Codabar) include it and add a policy struct each (what a policy holds is listed at
 // dc_decode_kernel).  Here are
 //   the scan front end: the profile of a scan line, its local threshold and its sub-pixel edges, as the rules at
 //     ubd_decode_patches in include/ubd.h define them (dc_scan_line), and the edge list as one reading direction sees it (DcLine);
@@ -140,7 +140,7 @@ static __device__ __forceinline__ int dc_winner(const int32_t *tally, int nv, in
 //   Word                                the type the result rows are stored as;  ROW_WORDS: their number per row
 //   SYMS                                the symbologies a direction of a line is searched for.  Vote slot (k * 2 + dir) * SYMS + sym
 //                                       belongs to (line k, direction dir, symbology sym): 2 * SYMS slots per line, and
-//                                       bit log2(SYMS) of a slot's index is its direction
+//                                       (index / SYMS) & 1 is a slot's direction, index % SYMS its symbology
 //   SLOT_BYTES                          the bytes of a vote slot, a multiple of 8; the vote table is the front of dc_smem
 //   OFF_TALLY, TABLE_BYTES              where the tally's int32 per slot lies, and the bytes of all tables in front of the lines
 //   setup(tid)                          fills the family's tables; a barrier in it is uniform (every thread calls it)
@@ -232,7 +232,7 @@ static int dc_decode(const char *who, const uint8_t *patches, const int32_t *cou
                 P.min_votes);
     UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "%s: n * cap = %d * %d is not below 2^31", who, n, cap);
     const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
-    const size_t lds = Sym::TABLE_BYTES + dc_lines_bytes(patch_w);              // <= 9376 + 49152 bytes
+    const size_t lds = Sym::TABLE_BYTES + dc_lines_bytes(patch_w);              // <= 13856 + 49152 bytes
     typename Sym::Word *rows = (typename Sym::Word *)results;
     if (channels == 3)
         hipLaunchKernelGGL((dc_decode_kernel<3, Sym>), grid, block, lds, (hipStream_t)stream, patches, counts, cap, patch_h, patch_w, P, rows);

@@ -1,8 +1,9 @@
-// Decoding of the object patches, second family: the text of a Code 128 / GS1-128 symbol out of every upright patch that
+// Decoding of the object patches, second family: the text of a Code 128 / GS1-128 or Code 93 symbol out of every upright patch that
 // ubd_extract_objects wrote, on the device, so that 128 bytes per object cross to the host instead of the patch.  The rules are
 // written out at ubd_decode_text_patches in include/ubd.h and restated, from the rules and not from this file, by the numpy
 // oracle tests/text_decode_oracle.py, which this kernel matches bit for bit (tests/test_gpu_text_decode.py).  The patterns, the
-// code sets and the modulo-103 check are those of the public Code 128 specification (ISO/IEC 15417).
+// code sets and the modulo-103 check are those of the public Code 128 specification (ISO/IEC 15417); the 48 patterns of Code 93
+// and its two modulo-47 check characters are those of its public specification (AIM USS-93).
 //
 // Integer arithmetic only, and every intermediate fits an int32 at the limits (patch_w <= 1024, quiet <= 16).  Edges, runs and
 // sums of runs are < 2^18 (decode_scan.h), so
@@ -10,7 +11,9 @@
 //     twice their difference < 2^23; widths of neighbours: 5 S_prev < 2^21; stop bar: 22 b < 2^23;
 //   quiet zone: 11 q < 2^22 and QZ * S <= 16 * 2^18 = 2^22;
 //   check: start + sum k d_k over at most 61 values (the check value is taken out again at the stop)
-//     <= 105 + 102 * (61 * 62 / 2) = 192987.
+//     <= 105 + 102 * (61 * 62 / 2) = 192987;
+//   Code 93: characters 18 (w + w') < 2^23 and 9 S < 2^22, bar sum 9 (w0 + w2 + w4) < 2^22 and S V <= 6 * 2^18; termination bar 18 b
+//     < 2^23; quiet zone 9 q < 2^22; checks: at most 61 values <= 46 of weight <= 20, <= 56120.
 // No division is left: the floors of the character, stop-bar and quiet-zone rules are taken by comparing products.
 //
 // Shape: that of decode_scan.h, which holds the kernel (dc_decode_kernel: prologue, rounds, search, tally, winner rule) and the
@@ -22,19 +25,21 @@
 // last value are enough to accept it); the lane that votes decodes the characters once more and writes count and values into the
 // 64-byte vote slot of (line, direction).  The tally compares whole slots (16 dwords; the count in byte 0 and zeroes behind the
 // values make equal slots equal payloads).  Thread 0 expands the winner's text into a 128-byte row in LDS, which leaves as 32
-// dword stores.
-// LDS: 4096 (votes) + 256 (tally) + 2592 (key table) + 128 (row) + at most 49152 (lines) = 56224 bytes.
+// dword stores.  Code 93 is the second symbology of a line: its 48 patterns go to a table of 4^4 entries beside the first (its
+// distances are 2..5), and a lane that finds start, characters, stop, termination bar and quiet zones in place walks the
+// characters a second time for the two check sums, whose weights count from the right and so need the length first.
+// LDS: 8192 (votes) + 512 (tally) + 2592 + 512 (key tables) + 128 (row) + at most 49152 (lines) = 61088 bytes; the mask 4 runs an
+// instance of the kernel that searches Code 128 alone, with 4096 + 256 + 2592 + 128 + at most 49152 = 56224 bytes.
 #include "decode_scan.h"
 
-#define TX_MAX_VOTES (2 * DC_MAX_ROWS)          // slots (line, direction)
 #define TX_SLOT 64                              // bytes of a vote slot: [0] the number of values, [1..] the values, then zeroes
+                                                // (Code 93: the start value 47, data, C and K; a Code 128 begins with 103..105)
 #define TX_MAX_VALUES 62                        // start + 60 data + check
 #define TX_KEYS 1296                            // 6^4
 #define TX_ROW 128                              // bytes of a result row
-#define TX_OFF_TALLY (TX_MAX_VOTES * TX_SLOT)
-#define TX_OFF_KEYS (TX_OFF_TALLY + TX_MAX_VOTES * 4)
-#define TX_OFF_ROW (TX_OFF_KEYS + TX_KEYS * 2)
-#define TX_TABLE_BYTES (TX_OFF_ROW + TX_ROW)    // 7072, a multiple of 16
+#define TX_KEYS93 256                           // 4^4
+#define TX_STAR93 47                            // start and stop of a Code 93
+#define TX_MAX_VALUES93 62                      // 60 data, C and K
 #define TX_START_A 103
 #define TX_STOP 106
 
@@ -50,6 +55,13 @@ __constant__ uint32_t tx_patterns[107] = {
     0x122411, 0x142112, 0x142211, 0x241211, 0x221114, 0x413111, 0x241112, 0x134111, 0x111242, 0x121142, 0x121241, 0x114212,
     0x124112, 0x124211, 0x411212, 0x421112, 0x421211, 0x212141, 0x214121, 0x412121, 0x111143, 0x111341, 0x131141, 0x114113,
     0x114311, 0x411113, 0x411311, 0x113141, 0x114131, 0x311141, 0x411131, 0x211412, 0x211214, 0x211232, 0x233111};
+
+// Code 93: run widths for the values 0..47 the same way: the digits, A..Z, - . space $ / + %, the shifts ($) (%) (/) (+), start / stop
+__constant__ uint32_t tx_patterns93[48] = {
+    0x131112, 0x111213, 0x111312, 0x111411, 0x121113, 0x121212, 0x121311, 0x111114, 0x131211, 0x141111, 0x211113, 0x211212,
+    0x211311, 0x221112, 0x221211, 0x231111, 0x112113, 0x112212, 0x112311, 0x122112, 0x132111, 0x111123, 0x111222, 0x111321,
+    0x121122, 0x131121, 0x212112, 0x212211, 0x211122, 0x211221, 0x221121, 0x222111, 0x112122, 0x112221, 0x122121, 0x123111,
+    0x121131, 0x311112, 0x311211, 0x321111, 0x112131, 0x113121, 0x211131, 0x121221, 0x312111, 0x311121, 0x122211, 0x111141};
 
 // floor((22 a + s) / (2 s)) - 2 without a division: the floor is >= m exactly when 22 a >= (2m - 1) s; -1: outside 2..7
 static __device__ __forceinline__ int tx_distance(int a, int s)
@@ -70,6 +82,30 @@ static __device__ __forceinline__ int tx_character(const int (&e)[7], const uint
     const int entry = keys[((d0 * 6 + d1) * 6 + d2) * 6 + d3];
     if (entry == 0xFFFF) return -1;
     int off = 11 * ((e[1] - e[0]) + (e[3] - e[2]) + (e[5] - e[4])) - s * (entry >> 8);
+    off = off < 0 ? -off : off;
+    if (2 * off >= 3 * s) return -1;
+    return entry & 0xFF;
+}
+
+// Code 93: floor((18 a + s) / (2 s)) - 2 the same way; -1: outside 2..5
+static __device__ __forceinline__ int tx_distance93(int a, int s)
+{
+    const int t = 18 * a;
+    if (t < 3 * s || t >= 11 * s) return -1;
+    return (t >= 5 * s) + (t >= 7 * s) + (t >= 9 * s);
+}
+
+// One Code 93 character of six runs between the edges e[0..6]: its value 0..47, or -1.
+static __device__ __forceinline__ int tx_character93(const int (&e)[7], const uint16_t *keys)
+{
+    const int s = e[6] - e[0];
+    if (s <= 0) return -1;
+    const int d0 = tx_distance93(e[2] - e[0], s), d1 = tx_distance93(e[3] - e[1], s), d2 = tx_distance93(e[4] - e[2], s),
+              d3 = tx_distance93(e[5] - e[3], s);
+    if ((d0 | d1 | d2 | d3) < 0) return -1;
+    const int entry = keys[((d0 * 4 + d1) * 4 + d2) * 4 + d3];
+    if (entry == 0xFFFF) return -1;
+    int off = 9 * ((e[1] - e[0]) + (e[3] - e[2]) + (e[5] - e[4])) - s * (entry >> 8);
     off = off < 0 ? -off : off;
     if (2 * off >= 3 * s) return -1;
     return entry & 0xFF;
@@ -115,6 +151,47 @@ static __device__ int tx_candidate(const DcLine &L, int i, int quiet, const uint
     return sum % 103 == last ? cnt : 0;
 }
 
+// The Code 93 candidate that starts at edge i: the number of its values behind the start (data, C, K: 3..62), or 0.
+static __device__ int tx_candidate93(const DcLine &L, int i, int quiet, const uint16_t *keys)
+{
+    if (!dc_light_to_dark(L, i) || i + 6 >= L.n) return 0;
+    int e[7];
+    tx_load(L, i, e);
+    if (tx_character93(e, keys) != TX_STAR93) return 0;
+    int sp = e[6] - e[0];
+    if (i >= 1 && 9 * (e[0] - dc_edge(L, i - 1)) < quiet * sp) return 0;
+    int cnt = 0, s, j = i + 6;
+    for (;; j += 6) {
+        if (j + 6 >= L.n) return 0;
+        tx_load(L, j, e);
+        s = e[6] - e[0];
+        if (4 * s < 3 * sp || 4 * s > 5 * sp) return 0;
+        const int v = tx_character93(e, keys);
+        if (v < 0) return 0;
+        if (v == TX_STAR93) break;
+        if (cnt == TX_MAX_VALUES93) return 0;
+        ++cnt;
+        sp = s;
+    }
+    if (j + 7 >= L.n) return 0;
+    const int e7 = dc_edge(L, j + 7), bar = 18 * (e7 - e[6]);
+    if (bar < s || bar >= 3 * s) return 0;                                      // (18 b + S) / (2 S) == 1
+    if (j + 8 < L.n && 9 * (dc_edge(L, j + 8) - e7) < quiet * s) return 0;
+    if (cnt < 3) return 0;
+    // C over the data, weights 1..20 cycling from the right; K over the data and C, weights 1..15
+    const int D = cnt - 2;
+    int c_sum = 0, k_sum = 0, c_val = 0, k_val = 0;
+    for (int c = 0; c < cnt; ++c) {
+        tx_load(L, i + 6 + 6 * c, e);
+        const int v = tx_character93(e, keys);
+        if (c < D) c_sum += v * ((D - 1 - c) % 20 + 1);
+        if (c <= D) k_sum += v * ((D - c) % 15 + 1);
+        if (c == D) c_val = v;
+        k_val = v;
+    }
+    return c_sum % 47 == c_val && k_sum % 47 == k_val ? cnt : 0;
+}
+
 // The values of the valid candidate at edge i into its vote slot (zeroed before round 0).
 static __device__ void tx_write_values(const DcLine &L, int i, int cnt, const uint16_t *keys, uint8_t *slot)
 {
@@ -123,6 +200,16 @@ static __device__ void tx_write_values(const DcLine &L, int i, int cnt, const ui
         int e[7];
         tx_load(L, i + 6 * c, e);
         slot[1 + c] = (uint8_t)tx_character(e, keys);
+    }
+}
+
+static __device__ void tx_write_values93(const DcLine &L, int i, int cnt, const uint16_t *keys, uint8_t *slot)
+{
+    slot[0] = (uint8_t)(cnt + 1);
+    for (int c = 0; c <= cnt; ++c) {                                            // cnt <= 62: bytes 1..63
+        int e[7];
+        tx_load(L, i + 6 * c, e);
+        slot[1 + c] = (uint8_t)tx_character93(e, keys);
     }
 }
 
@@ -162,19 +249,26 @@ static __device__ __forceinline__ bool tx_same(const uint32_t *a, const uint32_t
     return same;
 }
 
-// The policy of dc_decode_kernel (decode_scan.h).  LDS tables: the vote table, the tally, the key table and the result row.
+// The policy of dc_decode_kernel (decode_scan.h).  LDS tables: the vote table, the tally, the key table(s) and the result row.
+// C93: the mask holds bit 7 and a line is searched for a second symbology.  The mask 4 runs the instance of one, whose code
+// and tables (7072 bytes) are those from before Code 93: with both in the one kernel the mask 4 took 4 us more a call.
+template <bool C93>
 struct TxText {
     typedef uint32_t Word;
-    static constexpr int ROW_WORDS = TX_ROW / 4, SYMS = 1, SLOT_BYTES = TX_SLOT, OFF_TALLY = TX_OFF_TALLY, TABLE_BYTES = TX_TABLE_BYTES;
+    static constexpr int SYMS = C93 ? 2 : 1, MAX_VOTES = 2 * SYMS * DC_MAX_ROWS;                  // slots (line, direction, symbology)
+    static constexpr int OFF_TALLY = MAX_VOTES * TX_SLOT, OFF_KEYS = OFF_TALLY + MAX_VOTES * 4, OFF_KEYS93 = OFF_KEYS + TX_KEYS * 2;
+    static constexpr int OFF_ROW = OFF_KEYS93 + (C93 ? TX_KEYS93 * 2 : 0), TABLE_BYTES = OFF_ROW + TX_ROW;   // 11936 or 7072, multiples of 16
+    static constexpr int ROW_WORDS = TX_ROW / 4, SLOT_BYTES = TX_SLOT;
 
     static __device__ __forceinline__ uint32_t *votes(int u) { return (uint32_t *)dc_smem + u * (TX_SLOT / 4); }
-    static __device__ __forceinline__ uint16_t *keys() { return (uint16_t *)(dc_smem + TX_OFF_KEYS); }
-    static __device__ __forceinline__ uint32_t *lds_row() { return (uint32_t *)(dc_smem + TX_OFF_ROW); }
+    static __device__ __forceinline__ uint16_t *keys() { return (uint16_t *)(dc_smem + OFF_KEYS); }
+    static __device__ __forceinline__ uint16_t *keys93() { return (uint16_t *)(dc_smem + OFF_KEYS93); }
+    static __device__ __forceinline__ uint32_t *lds_row() { return (uint32_t *)(dc_smem + OFF_ROW); }
 
-    // the key table of the 107 patterns and the row of "none"
+    // the key tables of the 107 and the 48 patterns (one behind the other) and the row of "none"
     static __device__ __forceinline__ void setup(int tid)
     {
-        for (int t = tid; t < TX_KEYS / 2; t += DC_THREADS) ((uint32_t *)keys())[t] = 0xFFFFFFFFu;
+        for (int t = tid; t < (TX_KEYS + (C93 ? TX_KEYS93 : 0)) / 2; t += DC_THREADS) ((uint32_t *)keys())[t] = 0xFFFFFFFFu;
         if (tid < TX_ROW / 4) lds_row()[tid] = tid < 2 ? 0u : 0xFFFFFFFFu;
         __syncthreads();
         if (tid < 107) {
@@ -184,14 +278,30 @@ struct TxText {
             for (int k = 0; k < 6; ++k) n[k] = (int)((p >> (4 * (5 - k))) & 15u);
             const int key = (((n[0] + n[1] - 2) * 6 + (n[1] + n[2] - 2)) * 6 + (n[2] + n[3] - 2)) * 6 + (n[3] + n[4] - 2);   // sums of two widths: 2..7 for these patterns
             keys()[key] = (uint16_t)(tid | (n[0] + n[2] + n[4]) << 8);
+        } else if (C93 && tid >= 128 && tid < 128 + 48) {
+            const uint32_t p = tx_patterns93[tid - 128];
+            int n[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) n[k] = (int)((p >> (4 * (5 - k))) & 15u);
+            const int key = (((n[0] + n[1] - 2) * 4 + (n[1] + n[2] - 2)) * 4 + (n[2] + n[3] - 2)) * 4 + (n[3] + n[4] - 2);   // sums of two widths: 2..5 for these patterns
+            keys93()[key] = (uint16_t)((tid - 128) | (n[0] + n[2] + n[4]) << 8);
         }
     }
-    static __device__ __forceinline__ int starts(const ubd_decode_params &, int, int n_edges)
+    static __device__ __forceinline__ int starts(const ubd_decode_params &P, int sym, int n_edges)
     {
-        return n_edges - 25;                                                    // start, one data, check and stop take the edges i .. i + 25
+        // Code 128: start, one data, check and stop take the edges i .. i + 25 (bit 2); Code 93: start, one data, C, K and stop i .. i + 31 (bit 7)
+        if (!C93) return n_edges - 25;
+        return sym ? n_edges - 31 : (P.symbologies & 4 ? n_edges - 25 : 0);
     }
-    static __device__ __forceinline__ int candidate(const DcLine &L, int i, int, int quiet) { return tx_candidate(L, i, quiet, keys()); }
-    static __device__ __forceinline__ void vote(const DcLine &L, int i, int cnt, int slot) { tx_write_values(L, i, cnt, keys(), (uint8_t *)votes(slot)); }
+    static __device__ __forceinline__ int candidate(const DcLine &L, int i, int sym, int quiet)
+    {
+        return C93 && sym ? tx_candidate93(L, i, quiet, keys93()) : tx_candidate(L, i, quiet, keys());
+    }
+    static __device__ __forceinline__ void vote(const DcLine &L, int i, int cnt, int slot)
+    {
+        if (C93 && (slot & 1)) tx_write_values93(L, i, cnt, keys93(), (uint8_t *)votes(slot));   // the slot's lowest bit is its symbology
+        else tx_write_values(L, i, cnt, keys(), (uint8_t *)votes(slot));
+    }
     static __device__ __forceinline__ bool empty(int u) { return (votes(u)[0] & 0xFFu) == 0; }
     static __device__ __forceinline__ bool same(int u, int v) { return tx_same(votes(u), votes(v)); }
 
@@ -200,19 +310,32 @@ struct TxText {
     {
         if (tid == 0) {
             int best;
-            const int at = dc_winner<TxText>(tally, nv, min_votes, best);
+            const int at = dc_winner<TxText<C93>>(tally, nv, min_votes, best);
             if (at >= 0) {
                 const uint8_t *win = (const uint8_t *)votes(at);
                 uint8_t *bytes = (uint8_t *)lds_row();
                 const int cnt = win[0];
-                bytes[0] = 128;
                 bytes[1] = (uint8_t)best;                                       // <= 2 * 32
                 bytes[2] = (uint8_t)(tally[at] >> 16);
-                bytes[3] = (uint8_t)tx_expand(win, bytes + 8);                  // T <= 120: bytes 8..127
-                bytes[4] = win[2] == 102 ? 1 : 0;                               // the first data character is FNC1
-                bytes[5] = (uint8_t)(cnt - 2);
-                bytes[6] = win[1];
-                bytes[7] = win[cnt];
+                if (C93 && win[1] == TX_STAR93) {                                      // Code 93: an element per data value, the shifts as 0xE1..0xE4
+                    const int D = cnt - 3;
+                    bytes[0] = 93;
+                    bytes[3] = bytes[5] = (uint8_t)D;                           // <= 60: bytes 8..67
+                    bytes[4] = 0;
+                    bytes[6] = win[cnt - 1];
+                    bytes[7] = win[cnt];
+                    for (int k = 0; k < D; ++k) {
+                        const int v = win[2 + k];
+                        bytes[8 + k] = (uint8_t)(v < 10 ? 48 + v : v < 36 ? 55 + v : v < 43 ? "-. $/+%"[v - 36] : 0xE1 + v - 43);
+                    }
+                } else {
+                    bytes[0] = 128;
+                    bytes[3] = (uint8_t)tx_expand(win, bytes + 8);              // T <= 120: bytes 8..127
+                    bytes[4] = win[2] == 102 ? 1 : 0;                           // the first data character is FNC1
+                    bytes[5] = (uint8_t)(cnt - 2);
+                    bytes[6] = win[1];
+                    bytes[7] = win[cnt];
+                }
             }
         }
         __syncthreads();                                                        // uniform: every thread of the workgroup is here
@@ -226,7 +349,9 @@ struct TxText {
     }
     static int check_symbologies(const char *who, int symbologies)
     {
-        UBD_REQUIRE(symbologies == 4, "%s: symbologies must be 4 (bit 2 Code 128; bits 0 and 1 are ubd_decode_patches'), got %d", who, symbologies);
+        UBD_REQUIRE(symbologies == 4 || symbologies == 128 || symbologies == 132,
+                    "%s: symbologies must be 4, 128 or 132 (bit 2 Code 128, bit 7 Code 93; the other bits are the other two entry points'), got %d", who,
+                    symbologies);
         return 0;
     }
 };
@@ -234,5 +359,7 @@ struct TxText {
 extern "C" int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                                        const ubd_decode_params *params, uint8_t *results, void *stream)
 {
-    return dc_decode<TxText>("ubd_decode_text_patches", patches, counts, n, cap, patch_h, patch_w, channels, params, results, stream);
+    if (params && (params->symbologies & 128))
+        return dc_decode<TxText<true>>("ubd_decode_text_patches", patches, counts, n, cap, patch_h, patch_w, channels, params, results, stream);
+    return dc_decode<TxText<false>>("ubd_decode_text_patches", patches, counts, n, cap, patch_h, patch_w, channels, params, results, stream);
 }
