@@ -4,7 +4,8 @@
 // Every fp32 value v is the exact sum of three bf16 values obtained by truncation,
 //     v = v1 + v2 + v3,   v1 = hi16(v),  v2 = hi16(v - v1),  v3 = hi16(v - v1 - v2)       (8 + 8 + 8 = 24 significand bits),
 // so a product of two fp32 values is the sum of nine bf16 x bf16 products (each exact in fp32).  The six with i + j <= 4 are kept;
-// the three dropped ones are <= 2^-24 of the product -- the size of the rounding of an fp32 multiply.  K = 24 channels fit one
+// the three dropped ones are <= 2^-24 of the product -- the size of the rounding of an fp32 multiply.  WHICH six are kept is pinned for the
+// stem by tests/test_gpu_exact32.py: bit equality on inputs on which each kept product is live and each dropped one zero (tests/exact_cases.py).  K = 24 channels fit one
 // K = 32 step: lane (m, q) holds the k-slots 0..5 of k-group q = channels 4q .. 4q+3, 16+2q, 17+2q (slots 6, 7 zero).
 // All arithmetic is plain C++ on vector types (no inline asm): hipcc's scheduler and hazard recogniser see every instruction
 // (wino6.hip records what an asm v_add_f32 next to an MFMA result did).
