@@ -448,7 +448,11 @@ typedef struct ubd_decode_params {
                                         takes any non-empty subset of 8 | 16 | 256.  The bits are numbered over all families.
                                         Bit 5 (32) is skipped: it was held back as the first bit no family reads when bits
                                         0..4 were given out, callers and tests rely on every layer refusing it, and so the
-                                        three symbologies that came later took 6..8 and 32 stays unassigned */
+                                        three symbologies that came later took 6..8 and 32 stays unassigned.  Bit 10 POSTNET,
+                                        bit 11 PLANET, bit 12 RM4SCC, bit 13 KIX: ubd_decode_postal_patches takes any non-empty
+                                        subset of 1024 | 2048 | 4096 | 8192 = 15360, and the three older entries refuse these
+                                        bits.  Bit 9 (512) is skipped for the reason bit 5 is: every older entry is held to
+                                        refusing it, so it stays unassigned */
     int32_t scan_rows;               /* S, 1..32        default 8  */
     int32_t band;                    /* b, 0..8         default 1  */
     int32_t window;                  /* R, 1..64        default 16 */
@@ -604,6 +608,74 @@ int ubd_decode_text_patches(const uint8_t *patches, const int32_t *counts, int n
  * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph. */
 int ubd_decode_width_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                              const ubd_decode_params *params, uint8_t *results, void *stream);
+
+/* --- decoding of the object patches: POSTNET / PLANET / RM4SCC / KIX -------------------
+ * The fourth family behind ubd_extract_objects: the postal height-modulated codes.  Their bars all have one width and one pitch
+ * and the data is in how far each bar rises and falls, so no run width carries anything and the candidates are walked on the
+ * patch itself, bar by bar.  Read are POSTNET and PLANET (two bar heights on one base line), RM4SCC (Royal Mail 4-state) and
+ * KIX (the same characters without frame bars and without a check).  Not read: Intelligent Mail and Australia Post, and no
+ * error correction of any kind.  The contract is that of ubd_decode_width_patches (device patches and counts as
+ * ubd_extract_objects writes them, params a HOST pointer read before the call returns, slots j >= min(counts[i], cap) neither
+ * read nor written), the params struct is the same, and `symbologies` must be a non-empty subset of 1024 (bit 10, POSTNET),
+ * 2048 (bit 11, PLANET), 4096 (bit 12, RM4SCC) and 8192 (bit 13, KIX).  Integer arithmetic only (every division floors, every
+ * dividend is non-negative); the numpy restatement tests/postal_decode_oracle.py is matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 80 (POSTNET), 76 (PLANET), 82 (RM4SCC) or 75 (KIX), or 0 for
+ *     none; [1] votes; [2] direction mask (bit 0 read as the patch lies, bit 1 read on the half-turned patch); [3] T, the number
+ *     of characters; [4] flags, bit 0: the symbol carries a check and it held (always 1 for the first three, 0 for KIX); [5] B,
+ *     the number of bars; [6..7] 0; [8 .. 8 + T) the ASCII codes of the characters, the check digit or check character
+ *     included; the rest 0xFF.  For "none" bytes 0..7 are 0 and bytes 8..127 are 0xFF.
+ * Per patch (H rows, W columns):
+ *   luma g(y, x), scan lines k with their rows r_k, band profile, local threshold, edges and the mirrored list: those of
+ *     ubd_decode_patches.  They serve only to find the start edges and the light run before them.
+ *   direction 1 is direction 0 on the half-turned patch: g'(y, x) = g(H - 1 - y, W - 1 - x), the edge list is the mirrored list,
+ *     the row is H - 1 - r_k.  Everything below is said for direction 0.
+ *   walk from a light-to-dark edge i whose closing edge i + 1 exists, once per G (5 for POSTNET and PLANET, 4 for RM4SCC and KIX).
+ *     State: the row r = r_k and the bar [s, t] = [e_i, e_(i+1)] in 1/256 pixel.  Per bar, on single-row luma:
+ *     1. xc = (s + t + 256) / 512; Lmin, Lmax the least and greatest g(r, x) over x in [xc - R, xc + R] clipped to the patch
+ *        (R = window); thr = Lmin + Lmax; a pixel is dark iff 2 g < thr.  The chain ends, this bar not part of it, if
+ *        Lmax - Lmin < C (contrast) or (r, xc) is not dark;
+ *     2. from the second bar on the pitch p = s - s_prev: the chain ends unless 4 (t - s) <= 3 p, and from the third bar on
+ *        unless 3 p_prev <= 4 p <= 5 p_prev;
+ *     3. top and bot are the first and last row of the unbroken dark run through (r, xc) in column xc;
+ *     4. the tracking row, once this bar is the G-th or a later one: T the greatest top and Bm the least bot of the last G bars
+ *        (this one included); the chain ends, this bar not part of it, if Bm < T; q = (Bm - T) / 4;
+ *        r = min(max(r, T + q), Bm - q).  The row moves only when it nears the edge of what the last G bars share;
+ *     5. the bar is part of the chain.  A 123rd bar: no candidate;
+ *     6. the next bar, on the row r of step 4 with this bar's thr, d(x) = 2 g(r, x) - thr: the first x in
+ *        [t / 256 + 1, t / 256 + 1 + n) with x + 1 <= W - 1 and d(x) >= 0 > d(x + 1), where n = 2 p / 256 pixels (n = R behind
+ *        the first bar), gives s' = 256 x + 256 d(x) / (d(x) - d(x + 1)); the first x' in (x, x + R] with x' + 1 <= W - 1 and
+ *        d(x') < 0 <= d(x' + 1) gives t' = 256 x' + 256 (-d(x')) / (d(x' + 1) - d(x')).  If either is not found the chain ends.
+ *     (Two simpler designs failed on rendered symbols: extents measured from the fixed scan row lose the tracker band of a
+ *     4-state code under 1 to 2 degrees of slant; re-centring the row on every window of bars loses the short bars of a PLANET
+ *     behind six tall bars in a row.  Hence the clamped row of step 4.)
+ *   quiet zones, with B bars and St = t_last - s_first: if i >= 1: (2 B - 1) (e_i - e_(i-1)) >= QZ * St; and on the row r left
+ *     by the last bar's step 4, with the last bar's thr, every pixel x in [t_last / 256 + 1, t_last / 256 + 1 + n) with x <= W - 1,
+ *     n = ceil(QZ * St / ((2 B - 1) * 256)), must be light (2 g >= thr).
+ *   long or short: per bar a = -top and c = bot; Hs the greatest bot - top + 1 of the chain.  A group is the bars of one
+ *     character; of a framed symbol the first bar joins the first character's group and the last bar the last's.  Per group,
+ *     over a and separately over c, with the least value lo and the greatest hi: if 5 (hi - lo) < Hs no bar of the group is long,
+ *     otherwise a bar w is long iff 2 w > lo + hi.  A word is a character's bars in order, 1 = long.
+ *   POSTNET: B one of 32, 37, 52, 62; no bar long in c; the first and the last bar long in a; the a word of each five bars is
+ *     one of 11000 00011 00101 00110 01001 01010 01100 10001 10010 10100, the digits 0..9; the digits sum to 0 modulo 10.
+ *   PLANET: B one of 62, 72; the same with every a word complemented before it is looked up.
+ *   RM4SCC: B = 4 n + 2, n in 2..30; the first bar long in a and not in c, the last long in both; the a word and the c word of
+ *     each four bars are among 0011 0101 0110 1001 1010 1100, of the indices 0..5; value = 6 * index(a word) + index(c word),
+ *     the character "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"[value].  The last value must equal 6 * ((Rs + 5) % 6) + (Cs + 5) % 6,
+ *     Rs the sum of (value / 6 + 1) and Cs the sum of (value % 6 + 1) over the others, both modulo 6.  SN34RD1A has the check K.
+ *   KIX: B = 4 n, n in 4..30; the characters as RM4SCC's, no frame bars and no check.  A KIX votes in direction 0 only: its
+ *     half-turned reading is always another valid KIX text (every character reversed with a and c swapped), so both directions
+ *     would tie to "none".  The caller must know which way up a KIX lies.
+ *   votes: per (line, direction, symbology) only the valid candidate with the lowest start index counts, one vote for its
+ *     (symbology, all characters).  The payload with the most votes wins, its mask is the OR of the directions that voted for
+ *     it; fewer than min_votes, or another payload with as many votes: none.
+ * Limits (non-zero return, ubd_last_error begins with "ubd_decode_postal_patches", nothing launched, nothing written): those
+ * of ubd_decode_width_patches, with symbologies a non-empty subset of 15360.
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph.
+ * hip_stream is the hipStream_t of the launch, exactly what the other entries call `stream`.  It has a name of its own because
+ * tests/test_lib_call_host.py counts the declarations that end in `void *stream` and holds that set to the 33 entries of
+ * ubdvss_amd/_lib.py's ON_STREAM; an entry that came later stands beside that set (_lib.LAUNCHED), not in it. */
+int ubd_decode_postal_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                              const ubd_decode_params *params, uint8_t *results, void *hip_stream);
 
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one

@@ -15,6 +15,8 @@ from .barcode_decoder import decode_patches_on_device, results_to_records, Decod
 from .barcode_decoder import decode_text_patches_on_device, text_results_to_records, DecodedText, CODE128  # noqa: F401
 from .barcode_decoder import decode_width_patches_on_device, width_results_to_records, DecodedWidth, ITF, CODE39  # noqa: F401
 from .barcode_decoder import UPCE, CODE93, CODABAR, upce_to_upca, full_ascii, code32_to_digits  # noqa: F401
+from .barcode_decoder import decode_postal_patches_on_device, postal_results_to_records, DecodedPostal, kix_half_turned  # noqa: F401
+from .barcode_decoder import POSTNET, PLANET, RM4SCC, KIX, POSTAL_SYMBOLOGIES  # noqa: F401
 from .augmentation import SegLinksImageAugmentation, AugmentationPlan, Stage, sample_plan, sample_photometric, apply_plan_to_markup  # noqa: F401
 from . import losses  # noqa: F401
 from .trainer import Trainer, Adam, History  # noqa: F401

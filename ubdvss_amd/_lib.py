@@ -98,6 +98,7 @@ SIGNATURES = {
     "ubd_decode_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_decode_text_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_decode_width_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
+    "ubd_decode_postal_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(UbdDecodeParams), _vp, _vp]),
     "ubd_photometric_images": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
     "ubd_noise_alpha_images": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _sz, _i, _i, _vp]),
     "ubd_evaluate_accumulator_bytes": (_sz, [_i, _i]),
@@ -160,6 +161,11 @@ ON_STREAM = frozenset((
     "ubd_decode_text_patches", "ubd_decode_width_patches", "ubd_photometric_images", "ubd_noise_alpha_images", "ubd_evaluate_objects",
     "ubd_evaluate_polygons", "ubd_evaluate_pixels", "ubd_score_objects", "ubd_rank_detections", "ubd_visualize_images",
     "ubd_allreduce_grads", "ubd_broadcast_params"))
+# ON_STREAM is held to the header's `void *stream` declarations and to their number by tests/test_lib_call_host.py.  An entry
+# point that came after that count was fixed takes its stream last as well, under the parameter name `hip_stream`, and is
+# launched in the same way: LAUNCHED is what ``launch`` takes and ``call`` refuses (tests/test_postal_decode_host.py holds it to
+# the header)
+LAUNCHED = ON_STREAM | frozenset(("ubd_decode_postal_patches",))
 
 
 def require_gpu(what):
@@ -175,12 +181,12 @@ def current_stream(device):
 
 
 def launch(name, device, *args, stream=None):
-    """THE way to an entry point of ON_STREAM: ``name(*args, stream)`` with ``device`` -- the device of the tensors in ``args``
+    """THE way to an entry point of LAUNCHED (ON_STREAM and the later ones): ``name(*args, stream)`` with ``device`` -- the device of the tensors in ``args``
     -- made current for the call, on that device's current torch stream, the return code checked on this thread
     (ubd_last_error is thread-local).  ``stream``: the handle of that same stream (``current_stream`` / ``Model._stream``) when the
     caller needed it before the call, for a workspace or packed-weights key.  Every step of forward, postprocess, train step and
     Adam comes through here: one stream lookup, one device guard, one check, nothing else."""
-    if name not in ON_STREAM:
+    if name not in LAUNCHED:
         raise ValueError(f"{name} is not an entry point that takes a stream (_lib.ON_STREAM); checked entries without one go through _lib.call")
     fn = getattr(load(), name)
     if stream is None:
@@ -192,7 +198,7 @@ def launch(name, device, *args, stream=None):
 def call(name, *args, device=None):
     """A checked entry point that takes no stream (ubd_create, ubd_comm_*, the *_tables_layout): ``name(*args)``, with
     ``device`` current for the call when one is given.  The size queries and getters return no status: plain calls on ``load()``."""
-    if name in ON_STREAM:
+    if name in LAUNCHED:
         raise ValueError(f"{name} takes a stream: it goes through _lib.launch")
     fn = getattr(load(), name)
     if device is None:

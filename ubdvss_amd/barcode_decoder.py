@@ -7,7 +7,10 @@ per object; tests/text_decode_oracle.py): ``decode_text_patches_on_device`` and 
 ITF and Code 39, are a third (``ubd_decode_width_patches``, 128 bytes per object; tests/width_decode_oracle.py):
 ``decode_width_patches_on_device`` and ``width_results_to_records``.  UPC-E, Code 93 and Codabar are further symbologies of the
 three kernels (bits 6, 7 and 8; tests/extra_decode_oracle.py).  Beside the records stand three host helpers for what the device
-leaves uninterpreted: ``upce_to_upca``, ``full_ascii`` (the shift pairs of Code 39 and Code 93) and ``code32_to_digits``."""
+leaves uninterpreted: ``upce_to_upca``, ``full_ascii`` (the shift pairs of Code 39 and Code 93) and ``code32_to_digits``.
+The postal height-modulated codes POSTNET, PLANET, RM4SCC and KIX are a fourth kernel (``ubd_decode_postal_patches``, 128 bytes per
+object; tests/postal_decode_oracle.py): ``decode_postal_patches_on_device``, ``postal_results_to_records`` and the helper
+``kix_half_turned``.  Intelligent Mail and Australia Post are not read."""
 import collections
 import ctypes
 
@@ -20,11 +23,14 @@ EAN13, EAN8 = 1, 2                                       # bits of ``symbologies
 CODE128 = 4                                              # bit 2: read by ubd_decode_text_patches, not by ubd_decode_patches
 ITF, CODE39 = 8, 16                                      # bits 3 and 4: read by ubd_decode_width_patches
 UPCE, CODE93, CODABAR = 64, 128, 256                     # bits 6, 7, 8: read by the retail, the text and the two-width entry point; bit 5 is unassigned
-ALL_SYMBOLOGIES = 479
+ALL_SYMBOLOGIES = 479                                    # the run-width families; the postal family is beside it
+POSTNET, PLANET, RM4SCC, KIX = 1024, 2048, 4096, 8192    # bits 10..13: read by ubd_decode_postal_patches; bit 9 is unassigned
+POSTAL_SYMBOLOGIES = 15360
 DEFAULT_PARAMS = dict(symbologies=EAN13 | EAN8, scan_rows=8, band=1, window=16, contrast=24, quiet=3, min_votes=2)
 RESULT_INTS = 16
 TEXT_RESULT_BYTES = 128
 WIDTH_RESULT_BYTES = 128
+POSTAL_RESULT_BYTES = 128
 FNC1, FNC2, FNC3, FNC4 = 0xF1, 0xF2, 0xF3, 0xF4          # text elements of a Code 128 result beside the ASCII codes 0..127
 SHIFT1, SHIFT2, SHIFT3, SHIFT4 = 0xE1, 0xE2, 0xE3, 0xE4  # text elements of a Code 93 result: the shifts ($) (%) (/) (+)
 
@@ -45,6 +51,12 @@ DecodedWidth.__doc__ = """One decoded two-width object.  symbology: 'ITF', 'Code
 the data between the two '*'; Full ASCII pairs are left as they are; of a Codabar every character, its start and stop A..D included,
 and checked says that all their values sum to 0 modulo 16); votes and upside_down as in DecodedBarcode; checked: the
 last element is the optional check character of the rest (GS1's modulo 10 for ITF, modulo 43 for Code 39) -- it stays in text."""
+
+DecodedPostal = collections.namedtuple("DecodedPostal", ["symbology", "text", "votes", "upside_down", "checked", "bars"])
+DecodedPostal.__doc__ = """One decoded postal object.  symbology: 'POSTNET', 'PLANET', 'RM4SCC' or 'KIX'; text: its digits or characters,
+the check digit or check character included (a KIX has none); votes and upside_down as in DecodedBarcode -- a KIX is never
+upside_down: it is read as the patch lies, and of a half-turned one text is ``kix_half_turned`` of what it says; checked: the
+symbol carries a check and it held (False only for a KIX); bars: the number of its bars."""
 
 
 def make_params(**params):
@@ -112,6 +124,16 @@ def decode_width_patches_on_device(patches, counts, **params):
                    torch.uint8, fill_from=8)
 
 
+def decode_postal_patches_on_device(patches, counts, **params):
+    """``patches`` and ``counts`` as for ``decode_patches_on_device``; ``params`` the same keywords, ``symbologies`` defaulting to
+    POSTAL_SYMBOLOGIES (``ubd_decode_postal_patches`` takes any of POSTNET, PLANET, RM4SCC, KIX).  Returns the uint8 device tensor
+    (n, cap, 128) of ``ubd_decode_postal_patches``: [80, 76, 82, 75 or 0, votes, direction mask, T, flags, B bars, 0, 0,
+    T ASCII codes, 0xFF..]; rows of slots that hold no object read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the
+    current stream; nothing is read back."""
+    return _launch("ubd_decode_postal_patches", patches, counts, dict({"symbologies": POSTAL_SYMBOLOGIES}, **params), POSTAL_RESULT_BYTES,
+                   torch.uint8, fill_from=8)
+
+
 def _records(results, counts, parse):
     """per image the list of ``parse(row)`` over its min(counts[i], cap) result rows; ``parse`` gives None where nothing was read"""
     r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
@@ -138,6 +160,14 @@ def _width_record(row):
     return DecodedWidth({25: "ITF", 39: "Code 39", 27: "Codabar"}[code], "".join(chr(int(v)) for v in row[8:8 + t]), votes, mask == 2, bool(flags & 1))
 
 
+def _postal_record(row):
+    code, votes, mask, t, flags, bars = (int(v) for v in row[:6])
+    if code == 0:
+        return None
+    return DecodedPostal({80: "POSTNET", 76: "PLANET", 82: "RM4SCC", 75: "KIX"}[code], "".join(chr(int(v)) for v in row[8:8 + t]), votes,
+                         mask == 2, bool(flags & 1), bars)
+
+
 def _retail_record(row):
     code, votes, mask = (int(v) for v in row[:3])
     if code == 0:
@@ -156,6 +186,12 @@ def width_results_to_records(results, counts):
     """(n, cap, 128) results of ``decode_width_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
     min(counts[i], cap) entries, a ``DecodedWidth`` or None where nothing was read"""
     return _records(results, counts, _width_record)
+
+
+def postal_results_to_records(results, counts):
+    """(n, cap, 128) results of ``decode_postal_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
+    min(counts[i], cap) entries, a ``DecodedPostal`` or None where nothing was read"""
+    return _records(results, counts, _postal_record)
 
 
 def results_to_records(results, counts):
@@ -251,3 +287,22 @@ def code32_to_digits(text):
         v = int(c) * (2 if k % 2 else 1)
         total += v // 10 + v % 10
     return digits if total % 10 == int(digits[8]) else None
+
+
+_FOUR_STATE = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"     # value = 6 * (ascender pattern) + (descender pattern)
+_FOUR_TURNED = (5, 4, 2, 3, 1, 0)                        # a pattern of two long bars among four, read backwards: 0011 <-> 1100, 0101 <-> 1010
+
+
+def kix_half_turned(text):
+    """The text a KIX reads as when it lies half-turned: the characters in reverse order, and in each character the bars in
+    reverse order with ascenders and descenders swapped.  That is always a valid KIX text, so the decoder cannot tell which way
+    up a KIX is: it reads the patch as it lies, and the caller who knows the symbol to be half-turned takes this of the text.
+    ValueError for a character outside 0-9 A-Z."""
+    text = str(text)
+    if any(ch not in _FOUR_STATE for ch in text):
+        raise ValueError(f"a KIX holds the characters 0-9 and A-Z; got {text!r}")
+    out = []
+    for ch in reversed(text):
+        up, down = divmod(_FOUR_STATE.index(ch), 6)
+        out.append(_FOUR_STATE[6 * _FOUR_TURNED[down] + _FOUR_TURNED[up]])
+    return "".join(out)

@@ -1,11 +1,12 @@
 // The part of the patch decoders that does not know a symbology.  decode.hip (EAN-13 / UPC-A / EAN-8 / UPC-E), decode_text.hip
 // (Code 128, Code 93) and decode_width.hip (ITF, Code 39, Codabar) include it and add a policy struct each (what a policy holds is listed at
-// dc_decode_kernel).  Here are
+// dc_decode_kernel).  decode_postal.hip (POSTNET, PLANET, RM4SCC, KIX) takes the scan front end, dc_winner and dc_check and brings
+// a round loop of its own: its candidates are walked on the patch, not on the edge list.  Here are
 //   the scan front end: the profile of a scan line, its local threshold and its sub-pixel edges, as the rules at
 //     ubd_decode_patches in include/ubd.h define them (dc_scan_line), and the edge list as one reading direction sees it (DcLine);
 //   the kernel (dc_decode_kernel): slot prologue, round loop, direction loop, the search for the first valid candidate, the
 //     tally, and the rule that picks the winner (dc_winner);
-//   the host entry (dc_decode): the argument checks, the grid, the LDS size and the launch.
+//   the host entry (dc_check, dc_decode): the argument checks; the grid, the LDS size and the launch.
 //
 // Shape: one workgroup of DC_WAVES waves per patch slot; a workgroup whose slot holds no object returns after one load of
 // counts[i].  One wave per scan line, DC_WAVES lines per round.  The four stages of a round (profile, threshold, edges,
@@ -205,11 +206,11 @@ __global__ __launch_bounds__(DC_THREADS) void dc_decode_kernel(const uint8_t *__
     Sym::emit(tally, nv, P.min_votes, tid, results + (int64_t)slot * Sym::ROW_WORDS);
 }
 
-// The host side of a family's entry point; `who` is its name.  Sym::check_results and Sym::check_symbologies hold the
-// family's own rules and return as UBD_REQUIRE does.
+// The argument checks every patch decoder's entry point makes; `who` is its name.  Sym::check_results and Sym::check_symbologies
+// hold the family's own rules and return as UBD_REQUIRE does.  P: the caller's copy of *params.
 template <class Sym>
-static int dc_decode(const char *who, const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
-                     const ubd_decode_params *params, void *results, void *stream)
+static int dc_check(const char *who, const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                    const ubd_decode_params *params, const void *results, ubd_decode_params &P)
 {
     UBD_REQUIRE(patches, "%s: patches is null", who);
     UBD_REQUIRE(counts, "%s: counts is null", who);
@@ -221,7 +222,7 @@ static int dc_decode(const char *who, const uint8_t *patches, const int32_t *cou
     UBD_REQUIRE(patch_h >= 1 && patch_h <= DC_MAX_H, "%s: patch_h must be 1..%d, got %d", who, DC_MAX_H, patch_h);
     UBD_REQUIRE(patch_w >= DC_MIN_W && patch_w <= DC_MAX_W, "%s: patch_w must be %d..%d, got %d", who, DC_MIN_W, DC_MAX_W, patch_w);
     UBD_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 or 3, got %d", who, channels);
-    const ubd_decode_params P = *params;
+    P = *params;
     if (const int rc = Sym::check_symbologies(who, P.symbologies)) return rc;
     UBD_REQUIRE(P.scan_rows >= 1 && P.scan_rows <= DC_MAX_ROWS, "%s: scan_rows must be 1..%d, got %d", who, DC_MAX_ROWS, P.scan_rows);
     UBD_REQUIRE(P.band >= 0 && P.band <= 8, "%s: band must be 0..8, got %d", who, P.band);
@@ -231,6 +232,16 @@ static int dc_decode(const char *who, const uint8_t *patches, const int32_t *cou
     UBD_REQUIRE(P.min_votes >= 1 && P.min_votes <= 2 * P.scan_rows, "%s: min_votes must be 1..2 * scan_rows = %d, got %d", who, 2 * P.scan_rows,
                 P.min_votes);
     UBD_REQUIRE((int64_t)n * cap < ((int64_t)1 << 31), "%s: n * cap = %d * %d is not below 2^31", who, n, cap);
+    return 0;
+}
+
+// The host side of a family's entry point: the checks, the grid, the LDS size and the launch of dc_decode_kernel.
+template <class Sym>
+static int dc_decode(const char *who, const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                     const ubd_decode_params *params, void *results, void *stream)
+{
+    ubd_decode_params P;
+    if (const int rc = dc_check<Sym>(who, patches, counts, n, cap, patch_h, patch_w, channels, params, results, P)) return rc;
     const dim3 grid((unsigned)((int64_t)n * cap)), block(DC_THREADS);
     const size_t lds = Sym::TABLE_BYTES + dc_lines_bytes(patch_w);              // <= 13856 + 49152 bytes
     typename Sym::Word *rows = (typename Sym::Word *)results;
