@@ -452,7 +452,9 @@ typedef struct ubd_decode_params {
                                         bit 11 PLANET, bit 12 RM4SCC, bit 13 KIX: ubd_decode_postal_patches takes any non-empty
                                         subset of 1024 | 2048 | 4096 | 8192 = 15360, and the three older entries refuse these
                                         bits.  Bit 9 (512) is skipped for the reason bit 5 is: every older entry is held to
-                                        refusing it, so it stays unassigned */
+                                        refusing it, so it stays unassigned.  Bit 15 (32768) Data Matrix:
+                                        ubd_decode_matrix_patches takes exactly 32768, and the four older entries refuse it.
+                                        Bit 14 (16384) is skipped as bits 5 and 9 are */
     int32_t scan_rows;               /* S, 1..32        default 8  */
     int32_t band;                    /* b, 0..8         default 1  */
     int32_t window;                  /* R, 1..64        default 16 */
@@ -676,6 +678,78 @@ int ubd_decode_width_patches(const uint8_t *patches, const int32_t *counts, int 
  * ubdvss_amd/_lib.py's ON_STREAM; an entry that came later stands beside that set (_lib.LAUNCHED), not in it. */
 int ubd_decode_postal_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
                               const ubd_decode_params *params, uint8_t *results, void *hip_stream);
+
+/* --- decoding of the object patches: Data Matrix (ECC 200, 10 x 10 to 26 x 26) ---------
+ * The fifth family behind ubd_extract_objects and the first 2-D one: the Data Matrix symbol that stands roughly upright (any of
+ * the four quarter turns, a few degrees of slant) and alone in its patch.  It is the one entry with error correction: one
+ * Reed-Solomon block per symbol.  Read are the nine square sizes 10, 12 .. 26 of ECC 200 and the ASCII encodation.  Not read:
+ * rectangular sizes, sizes from 32 x 32 up, the C40 / Text / X12 / EDIFACT / Base 256 schemes, macros, ECI and structured append
+ * (they come back as raw codewords), ECC 000-140, mirrored or light-on-dark symbols.  The contract is that of
+ * ubd_decode_postal_patches (device patches and counts as ubd_extract_objects writes them, params a HOST pointer read before
+ * the call returns, slots j >= min(counts[i], cap) neither read nor written), the params struct is the same, and `symbologies`
+ * must be exactly 32768 (bit 15).  Bit 14 (16384) is skipped for the reason bits 5 and 9 are: every older layer is held to
+ * refusing it.  The four older entries refuse bit 15.  Of the params, band, window and contrast are used; scan_rows, quiet and
+ * min_votes are checked against their usual ranges and otherwise UNUSED (there are no scan lines and no votes here).  Integer
+ * arithmetic only; `/` below floors (dividends may be negative), `>>` is an arithmetic shift; the numpy restatement
+ * tests/matrix_decode_oracle.py is matched bit for bit.
+ *   results: DEVICE uint8 (n, cap, 128), aligned to 4 bytes: [0] 68 ('D'), or 0 for none; [1] n, the modules per side, 10..26;
+ *     [2] the quarter turns 0..3 (counter-clockwise) by which the patch shows the symbol turned; [3] T, the number of text
+ *     elements; [4] flags, bit 0: FNC1 in first position (GS1), bit 1: the text is incomplete (a codeword outside the ASCII
+ *     encodation ended it); [5] the codewords Reed-Solomon corrected; [6] the finder mismatches of the hypothesis that stood;
+ *     [7] U, the number of raw codewords; [8 .. 8 + T) the elements (bytes: Latin-1); [8 + T .. 8 + T + U) the raw data
+ *     codewords; the rest 0xFF.  For "none" bytes 0..7 are 0 and bytes 8..127 are 0xFF.
+ * Per patch (H rows, W columns), with b = band, m = (2 b + 1)^2, R = window, C = contrast:
+ *   1. dark map: luma g(y, x) as in ubd_decode_patches.  s(y, x) = the sum of g over the (2 b + 1)^2 neighbourhood, coordinates
+ *      clamped to the patch; lo, hi = the least and greatest s over the square [x - R, x + R] x [y - R, y + R] clipped to the
+ *      patch; d = 2 m g(y, x) - lo - hi; where hi - lo < C m, d = max(d, 1).  A pixel is dark iff d < -C m.  (The raw pixel
+ *      against the smoothed extremes: a smoothed pixel loses isolated modules at 3 pixels a module.  The margin -C m: the
+ *      extremes of a 33 x 33 window of noise pass a flatness test made for 33 samples, and without it a ring of speckle at
+ *      distance R around the symbol breaks step 2.)
+ *   2. box: cd(x), rd(y) the dark pixels per column and row; x0, x1 the first and last column with cd >= max(1, max(cd) / 4),
+ *      y0, y1 likewise from rd.  None found, or a side x1 - x0 + 1 or y1 - y0 + 1 under 20 pixels: none.
+ *   3. side lines: left(y) = the first dark x in columns x0..x1 of row y, right(y) = the last such x plus 1, for y in y0..y1;
+ *      top(x), bottom(x) the same down column x over rows y0..y1; a row or column without a dark pixel in the box is skipped.
+ *      A side's extent [a0, a1] is y0..y1 (left, right) or x0..x1 (top, bottom), L = a1 - a0 + 1, and its two segments are
+ *      [a0 + L / 16, a0 + L / 2 - 1] and [a1 - L / 2 + 1, a1 - L / 16].  Fewer than 4 values in a segment: none.  Each segment
+ *      [s0, s1] gives an anchor in 1/16 pixel: along the side c = 8 (s0 + s1 + 1); across it p = 16 v, v the k-th smallest
+ *      (left, top) or k-th largest (right, bottom) of the segment's `count` values, k = count / 4, counted from 0.  (A quartile
+ *      lands on the outer edge of a dashed side as of a solid one and ignores stray pixels.)  The side's line through its
+ *      anchors (c1, p1), (c2, p2): line(c) = p1 + ((p2 - p1) (c - c1)) / (c2 - c1), clamped to -32768..32767 (so that every
+ *      product fits an int32).
+ *   4. corners in 1/16 pixel, for (top, left), (top, right), (bottom, left), (bottom, right): y = horizontal(8 (x0 + x1 + 1));
+ *      then three times x = vertical(y), y = horizontal(x).
+ *   5. sample of module (r, c) of an n x n grid, N = 2 n, u = 2 c + 1, v = 2 r + 1: X = ((N - u)(N - v) TL + u (N - v) TR +
+ *      (N - u) v BL + u v BR) / N^2 per coordinate; the pixel (X >> 4, Y >> 4) clamped to the patch; the module is dark iff that
+ *      pixel is.
+ *   6. finder: for n = 10, 12 .. 26 the 4 n - 4 border modules are sampled, and for each turn t = 0..3 the mismatches against the
+ *      turned canonical border are counted.  Module (r, c) of the grid lies in the symbol at (r, c), (c, n - 1 - r),
+ *      (n - 1 - r, n - 1 - c), (n - 1 - c, r) for t = 0, 1, 2, 3.  The canonical border: column 0 and row n - 1 dark; else row 0
+ *      dark at even columns; else column n - 1 dark at odd rows.  The hypothesis (n, t) with the fewest mismatches `miss` of the
+ *      36 stands only if 8 miss <= 4 n - 4 and every other hypothesis has more.  Else none.
+ *   7. codewords: the n x n grid is sampled and written where each module lies in the symbol; the placement of ISO/IEC 16022
+ *      Annex F is walked on the (n - 2) x (n - 2) mapping matrix inside the border (the Utah shape with its two wrap rules, the
+ *      four corner cases at their standard trigger positions, the fixed corner left out), bit 1 the most significant.
+ *      Data / check codewords: 10: 3 / 5, 12: 5 / 7, 14: 8 / 10, 16: 12 / 12, 18: 18 / 14, 20: 22 / 18, 22: 30 / 20,
+ *      24: 36 / 24, 26: 44 / 28 (each pair sums to (n - 2)^2 / 8).
+ *   8. Reed-Solomon over GF(256) with the polynomial 0x12D, alpha = 2, e check codewords, the first codeword the highest power:
+ *      S_j = r(alpha^j), j = 1..e.  All zero: nothing to correct.  Otherwise Berlekamp-Massey, the Chien search over the
+ *      codeword positions and Forney's values; at most e / 2 errors, the number of roots found must equal the locator's degree,
+ *      and the corrected word's syndromes must vanish.  Anything else: none.  ("123456" is 142 164 186 with the check codewords
+ *      114 25 5 88 102.)
+ *   9. text of the data codewords: 1..128 the element cw - 1; 130..229 two digit elements; 235 followed by a codeword 1..128:
+ *      the element of that codeword + 127 (upper shift); 129 ends the data; 232 in first position sets flag bit 0, later it is
+ *      the element 0x1D.  Any other codeword (a 235 without such a follower included) sets flag bit 1 and ends the text: it and
+ *      the data codewords behind it are the U raw bytes.
+ * Limits (non-zero return, ubd_last_error begins with "ubd_decode_matrix_patches", nothing launched, nothing written): no null
+ * pointer, results aligned to 4 bytes, n >= 1, cap >= 1, n * cap < 2^31, patch_h and patch_w 32..128, channels 1 or 3,
+ * symbologies 32768, band 0..2, window 1..64, contrast 0..255, and scan_rows, quiet, min_votes in the ranges of
+ * ubd_decode_params.  (band <= 2 and sides <= 128 keep the workgroup within 64 KB of LDS.)
+ * One launch; no host synchronisation, no allocation, no handle, capturable in a HIP graph.
+ * launch_stream is the hipStream_t of the launch, what the other entries call `stream` or `hip_stream`.  Its name matches neither
+ * of the two patterns by which tests/test_lib_call_host.py and tests/test_postal_decode_host.py count the older declarations;
+ * ubdvss_amd/_lib.py keeps such an entry in LAUNCHED_LATER (tests/test_matrix_decode_host.py holds that set to this header). */
+int ubd_decode_matrix_patches(const uint8_t *patches, const int32_t *counts, int n, int cap, int patch_h, int patch_w, int channels,
+                              const ubd_decode_params *params, uint8_t *results, void *launch_stream);
 
 /* --- photometric augmentation ---------------------------------------------------
  * The built part of the reference's imgaug stage (augmentation.py:276-332: all of it but the two noise-alpha operations), one

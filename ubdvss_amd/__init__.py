@@ -17,6 +17,8 @@ from .barcode_decoder import decode_width_patches_on_device, width_results_to_re
 from .barcode_decoder import UPCE, CODE93, CODABAR, upce_to_upca, full_ascii, code32_to_digits  # noqa: F401
 from .barcode_decoder import decode_postal_patches_on_device, postal_results_to_records, DecodedPostal, kix_half_turned  # noqa: F401
 from .barcode_decoder import POSTNET, PLANET, RM4SCC, KIX, POSTAL_SYMBOLOGIES  # noqa: F401
+from .barcode_decoder import decode_matrix_patches_on_device, matrix_results_to_records, DecodedMatrix  # noqa: F401
+from .barcode_decoder import DATAMATRIX, MATRIX_SYMBOLOGIES  # noqa: F401
 from .augmentation import SegLinksImageAugmentation, AugmentationPlan, Stage, sample_plan, sample_photometric, apply_plan_to_markup  # noqa: F401
 from . import losses  # noqa: F401
 from .trainer import Trainer, Adam, History  # noqa: F401

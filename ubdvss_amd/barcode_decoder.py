@@ -10,7 +10,10 @@ three kernels (bits 6, 7 and 8; tests/extra_decode_oracle.py).  Beside the recor
 leaves uninterpreted: ``upce_to_upca``, ``full_ascii`` (the shift pairs of Code 39 and Code 93) and ``code32_to_digits``.
 The postal height-modulated codes POSTNET, PLANET, RM4SCC and KIX are a fourth kernel (``ubd_decode_postal_patches``, 128 bytes per
 object; tests/postal_decode_oracle.py): ``decode_postal_patches_on_device``, ``postal_results_to_records`` and the helper
-``kix_half_turned``.  Intelligent Mail and Australia Post are not read."""
+``kix_half_turned``.  Intelligent Mail and Australia Post are not read.
+Data Matrix (ECC 200, the square sizes 10 x 10 to 26 x 26, Reed-Solomon corrected) is a fifth kernel (``ubd_decode_matrix_patches``,
+128 bytes per object; tests/matrix_decode_oracle.py): ``decode_matrix_patches_on_device`` and ``matrix_results_to_records``.  It
+wants square patches of at most 128 x 128.  The other 2-D codes are not read."""
 import collections
 import ctypes
 
@@ -26,11 +29,14 @@ UPCE, CODE93, CODABAR = 64, 128, 256                     # bits 6, 7, 8: read by
 ALL_SYMBOLOGIES = 479                                    # the run-width families; the postal family is beside it
 POSTNET, PLANET, RM4SCC, KIX = 1024, 2048, 4096, 8192    # bits 10..13: read by ubd_decode_postal_patches; bit 9 is unassigned
 POSTAL_SYMBOLOGIES = 15360
+DATAMATRIX = 32768                                       # bit 15: read by ubd_decode_matrix_patches; bit 14 is unassigned
+MATRIX_SYMBOLOGIES = DATAMATRIX
 DEFAULT_PARAMS = dict(symbologies=EAN13 | EAN8, scan_rows=8, band=1, window=16, contrast=24, quiet=3, min_votes=2)
 RESULT_INTS = 16
 TEXT_RESULT_BYTES = 128
 WIDTH_RESULT_BYTES = 128
 POSTAL_RESULT_BYTES = 128
+MATRIX_RESULT_BYTES = 128
 FNC1, FNC2, FNC3, FNC4 = 0xF1, 0xF2, 0xF3, 0xF4          # text elements of a Code 128 result beside the ASCII codes 0..127
 SHIFT1, SHIFT2, SHIFT3, SHIFT4 = 0xE1, 0xE2, 0xE3, 0xE4  # text elements of a Code 93 result: the shifts ($) (%) (/) (+)
 
@@ -57,6 +63,13 @@ DecodedPostal.__doc__ = """One decoded postal object.  symbology: 'POSTNET', 'PL
 the check digit or check character included (a KIX has none); votes and upside_down as in DecodedBarcode -- a KIX is never
 upside_down: it is read as the patch lies, and of a half-turned one text is ``kix_half_turned`` of what it says; checked: the
 symbol carries a check and it held (False only for a KIX); bars: the number of its bars."""
+
+DecodedMatrix = collections.namedtuple("DecodedMatrix", ["symbology", "text", "size", "turns", "corrected", "gs1", "complete", "raw"])
+DecodedMatrix.__doc__ = """One decoded Data Matrix object.  symbology: 'Data Matrix'; text: its elements as a str, each byte decoded as
+Latin-1 (a FNC1 behind the first position is '\\x1d'); size: the modules per side, 10..26; turns: the quarter turns (counter-clockwise)
+by which the patch shows the symbol turned; corrected: the codewords Reed-Solomon corrected; gs1: FNC1 stands in first position;
+complete: the whole data was text -- False where a codeword outside the ASCII encodation (a latch to C40, Text, X12, EDIFACT or
+Base 256, a macro, ECI, structured append) ended it; raw: that codeword and the data codewords behind it, as bytes (b'' if complete)."""
 
 
 def make_params(**params):
@@ -134,6 +147,17 @@ def decode_postal_patches_on_device(patches, counts, **params):
                    torch.uint8, fill_from=8)
 
 
+def decode_matrix_patches_on_device(patches, counts, **params):
+    """``patches`` and ``counts`` as for ``decode_patches_on_device``, the patch sides 32..128 (a square symbol wants a square
+    patch: extract with ``patch_size=(128, 128)``); ``params`` the same keywords, ``symbologies`` defaulting to DATAMATRIX, the only
+    value ``ubd_decode_matrix_patches`` takes; band is 0..2 here, and scan_rows, quiet and min_votes are checked but unused.
+    Returns the uint8 device tensor (n, cap, 128) of ``ubd_decode_matrix_patches``: [68 or 0, modules per side, quarter turns, T,
+    flags, corrected codewords, finder mismatches, U, T text elements, U raw codewords, 0xFF..]; rows of slots that hold no object
+    read as "none": bytes 0..7 zero, the rest 0xFF.  One launch on the current stream; nothing is read back."""
+    return _launch("ubd_decode_matrix_patches", patches, counts, dict({"symbologies": DATAMATRIX}, **params), MATRIX_RESULT_BYTES,
+                   torch.uint8, fill_from=8)
+
+
 def _records(results, counts, parse):
     """per image the list of ``parse(row)`` over its min(counts[i], cap) result rows; ``parse`` gives None where nothing was read"""
     r = results.cpu().numpy() if isinstance(results, torch.Tensor) else np.asarray(results)
@@ -168,6 +192,14 @@ def _postal_record(row):
                          mask == 2, bool(flags & 1), bars)
 
 
+def _matrix_record(row):
+    code, size, turns, t, flags, corrected, _, u = (int(v) for v in row[:8])
+    if code == 0:
+        return None
+    return DecodedMatrix("Data Matrix", bytes(int(v) for v in row[8:8 + t]).decode("latin-1"), size, turns, corrected, bool(flags & 1),
+                         not flags & 2, bytes(int(v) for v in row[8 + t:8 + t + u]))
+
+
 def _retail_record(row):
     code, votes, mask = (int(v) for v in row[:3])
     if code == 0:
@@ -192,6 +224,12 @@ def postal_results_to_records(results, counts):
     """(n, cap, 128) results of ``decode_postal_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
     min(counts[i], cap) entries, a ``DecodedPostal`` or None where nothing was read"""
     return _records(results, counts, _postal_record)
+
+
+def matrix_results_to_records(results, counts):
+    """(n, cap, 128) results of ``decode_matrix_patches_on_device`` (device tensor or array) and counts (n) -> per image a list of
+    min(counts[i], cap) entries, a ``DecodedMatrix`` or None where nothing was read"""
+    return _records(results, counts, _matrix_record)
 
 
 def results_to_records(results, counts):

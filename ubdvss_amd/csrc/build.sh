@@ -23,7 +23,7 @@ for f in sorted(glob.glob("*.hip") + glob.glob("*.h")):
 print(h.hexdigest()[:16])
 PY
 )
-UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp extract decode decode_text decode_width decode_postal photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale score"
+UNITS="api forward fwd16 wino wino6 postprocess loss backward bwd32 bwd16 train comm raster resize warp extract decode decode_text decode_width decode_postal decode_matrix photometric noise_alpha evaluate evaluate_pixels visualize epoch_stats multiscale score"
 unit_flags() {   # the flags a unit needs beside $FLAGS, in every mode
   case $1 in
     api) echo "-DUBD_BUILD_ID=\"$BUILD_ID\"" ;;           # carries the fingerprint of ALL kernel sources

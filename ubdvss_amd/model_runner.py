@@ -291,14 +291,20 @@ class ModelRunner:
         further symbologies of the retail, the text and the two-width kernel, so 479 reads every run-width code.  Bits 10..13
         (``POSTNET``, ``PLANET``, ``RM4SCC``, ``KIX``; ``POSTAL_SYMBOLOGIES`` = 15360) add ``decode_postal_patches_on_device`` in
         the same way, one more launch and one more read of (n, fullest list, 128) bytes per group: a ``DecodedPostal`` is taken
-        where the older families gave None, and 479 | 15360 reads everything.  Bits 5 and 9 are unassigned: they and every bit
-        beyond 13 are a ValueError."""
+        where the older families gave None, and 479 | 15360 reads every linear code.  Bit 15 (``DATAMATRIX`` = 32768) adds
+        ``decode_matrix_patches_on_device`` in the same way, a fifth launch before any read: a ``DecodedMatrix`` is taken where
+        the older families gave None.  A Data Matrix is square and its kernel takes patch sides of 32..128, so a call with bit 15
+        wants ``patch_size=(128, 128)`` (a ValueError beyond 128); a mask without the bit launches and reads what it did before.
+        Bits 5, 9 and 14 are unassigned: they and every bit beyond 15 are a ValueError."""
         _lib.require_gpu("ModelRunner.predict_decoded")
         from .barcode_decoder import make_params
         symbologies = make_params(**params).symbologies     # an unknown keyword fails before any work
-        if symbologies & ~(479 | 15360):
-            raise ValueError(f"symbologies {symbologies}: bits 0..4, 6..8 and 10..13 (EAN-13, EAN-8, Code 128, ITF, Code 39; UPC-E, Code 93, "
-                             "Codabar; POSTNET, PLANET, RM4SCC, KIX) are the known symbologies, 479 | 15360 in all; bits 5 and 9 are unassigned")
+        if symbologies & ~(479 | 15360 | 32768):
+            raise ValueError(f"symbologies {symbologies}: bits 0..4, 6..8, 10..13 and 15 (EAN-13, EAN-8, Code 128, ITF, Code 39; UPC-E, Code 93, "
+                             "Codabar; POSTNET, PLANET, RM4SCC, KIX; Data Matrix) are the known symbologies, 479 | 15360 | 32768 in all; "
+                             "bits 5, 9 and 14 are unassigned")
+        if symbologies & 32768 and not (32 <= int(patch_size[0]) <= 128 and 32 <= int(patch_size[1]) <= 128):
+            raise ValueError(f"patch_size {tuple(patch_size)}: the Data Matrix decoder (bit 15) takes patch sides of 32..128; use (128, 128)")
         return self._predict_images(model, images, batch_size, (int(patch_size[0]), int(patch_size[1]), float(expand)), decode=params)
 
     def _predict_images(self, model, images, batch_size, patch, decode=None):
@@ -351,22 +357,24 @@ class ModelRunner:
     @staticmethod
     def _decode_records(on_device, counts, counts_h, decode):
         """the records of one group's device patches; bits 2 and 7 of ``symbologies`` add the text kernel on the same patches,
-        bits 3, 4 and 8 the two-width kernel, bits 10..13 the postal kernel"""
+        bits 3, 4 and 8 the two-width kernel, bits 10..13 the postal kernel, bit 15 the Data Matrix kernel"""
         from .barcode_decoder import decode_patches_on_device, results_to_records, decode_text_patches_on_device, \
             text_results_to_records, decode_width_patches_on_device, width_results_to_records, decode_postal_patches_on_device, \
-            postal_results_to_records, DEFAULT_PARAMS, EAN13, EAN8, CODE128, ITF, CODE39, UPCE, CODE93, CODABAR, POSTAL_SYMBOLOGIES
+            postal_results_to_records, decode_matrix_patches_on_device, matrix_results_to_records, DEFAULT_PARAMS, EAN13, EAN8, \
+            CODE128, ITF, CODE39, UPCE, CODE93, CODABAR, POSTAL_SYMBOLOGIES, MATRIX_SYMBOLOGIES
         symbologies = int(decode.get("symbologies", DEFAULT_PARAMS["symbologies"]))
-        if not symbologies & (CODE128 | CODE93 | ITF | CODE39 | CODABAR | POSTAL_SYMBOLOGIES):
+        if not symbologies & (CODE128 | CODE93 | ITF | CODE39 | CODABAR | POSTAL_SYMBOLOGIES | MATRIX_SYMBOLOGIES):
             return results_to_records(decode_patches_on_device(on_device, counts, **decode), counts_h)
         launched = []                                   # every kernel is launched before the first result is read
         for bits, launch, to_records in (((EAN13 | EAN8 | UPCE), decode_patches_on_device, results_to_records),
                                          ((CODE128 | CODE93), decode_text_patches_on_device, text_results_to_records),
                                          ((ITF | CODE39 | CODABAR), decode_width_patches_on_device, width_results_to_records),
-                                         (POSTAL_SYMBOLOGIES, decode_postal_patches_on_device, postal_results_to_records)):
+                                         (POSTAL_SYMBOLOGIES, decode_postal_patches_on_device, postal_results_to_records),
+                                         (MATRIX_SYMBOLOGIES, decode_matrix_patches_on_device, matrix_results_to_records)):
             if symbologies & bits:
                 launched.append((launch(on_device, counts, **dict(decode, symbologies=symbologies & bits)), to_records))
         records = None
-        for results, to_records in launched:            # in the order of preference: retail, text, two-width, postal
+        for results, to_records in launched:            # in the order of preference: retail, text, two-width, postal, Data Matrix
             more = to_records(results, counts_h)
             records = more if records is None else [[a if a is not None else b for a, b in zip(ra, rb)] for ra, rb in zip(records, more)]
         return records
